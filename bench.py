@@ -16,13 +16,23 @@ of /root/reference/examples/acopf/opf.jl:76-79.  Inputs are resident in HBM befo
 exchange iterates; the timed region ends with one all-gather of (ret, iter, done) per instance over RCCL
 (sqphip_gather_status).  Prints ONE JSON line on rank 0.
 
-Besides the contract's fields the line carries (rank 0, outside the timed region):
+Besides the contract's fields every line carries (rank 0, from the counters and HIP events of the timed steps):
   roofline       the multifrontal factor + solve kernels against the HBM roof (B_sparse)
+A plain run stops there.  With --full it also runs, outside the timed region, the records that take runs of their own:
+  kernels        per-kernel-class records over three more outer iterations; roofline.onbox_mfma_probe_tflops
   dense_ldlt     the dense MFMA LDL^T of round 1 on its own (N = 2813, 64 instances): ms and TFLOP/s of N^3/3 vs 78.6
+  scaling_prediction   the same timed steps over 1/2, 1/4 and 1/8 of the scenarios
   termination    the same 512 scenarios run until every instance has terminated (at most 60 outer iterations), with
                  the reference's Hessian sign (literal_quirks = 1: the sub-problems are non-convex and most runs hit
                  the limit) and with the textbook sign (literal_quirks = 0: nearly all converge)
+  screening      the scenario queue run to termination
   cpu_baseline   the CPU restatement (oracle/, its own sparse LDL^T), instances spread over the host cores
+(--quick and the --no-* switches drop legs of --full.)
+
+--dump-outputs DIR writes, after the timed steps, what a caller of the timed path receives after its last step, as
+float64 .npy files (rank 0's block at N > 1): per instance the iterate x, the constraint values g, the multipliers
+mult_g / mult_x_L / mult_x_U, obj_val, status and iter (sqphip_sqp_get), with the global scenario id in `instance`;
+and the gathered (ret, iter, done) table of the whole job.  Past 56 MB the instances are a fixed, seeded sample.
 """
 from __future__ import annotations
 
@@ -95,7 +105,12 @@ def main():
     ap.add_argument("--scaling", default="strong", choices=["strong", "weak"],
                     help="strong (default, BASELINE configs[3]): the job's scenarios are split over the GPUs; weak: every GPU "
                          "holds --batch scenarios (ids rank * batch ...), the job grows with N")
-    ap.add_argument("--quick", action="store_true", help="development runs: timed steps only (implies --no-cpu-baseline --no-termination --no-dense-ldlt --no-screening)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the records that take runs of their own (kernels, dense_ldlt, scaling_prediction, termination, "
+                         "screening, cpu_baseline, the MFMA probe); a plain run times the steps and prints the headline line only")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the timed path computed in its last step as DIR/<name>.npy (float64)")
+    ap.add_argument("--quick", action="store_true", help="with --full: timed steps only (implies --no-cpu-baseline --no-termination --no-dense-ldlt --no-screening)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-termination", action="store_true", help="skip the run-to-termination legs")
     ap.add_argument("--no-dense-ldlt", action="store_true", help="skip the dense LDL^T record")
@@ -126,7 +141,9 @@ def main():
     if args.steps is None: args.steps = 4 if dense_wl else 6          # (the dense NLP converges in six or seven outer iterations)
     if args.warmup is None: args.warmup = 1
     if args.kkt_mode is None: args.kkt_mode = 1 if dense_wl else 0
-    if args.quick:
+    if args.steps < 1:
+        ap.error("--steps must be at least 1 (sqphip_sqp_run(0) would run to termination)")
+    if args.quick or not args.full:
         args.no_cpu_baseline = args.no_termination = args.no_dense_ldlt = args.no_screening = args.no_batch_curve = True
 
     rank = int(os.environ.get("RANK", "0"))
@@ -359,6 +376,22 @@ def main():
     elapsed = float(elapsed.item())
     n_qp, n_ipm, n_fac = (float(v) for v in stats.tolist())
 
+    # ---- what the timed path computed in its last step (before any record below runs the context further)
+    if rank == 0 and args.dump_outputs:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        per_instance = 8 * (3 * lay0.n + 2 * lay0.m)
+        k = min(B, max(1, (56 << 20) // per_instance))
+        ids = np.arange(B) if k == B else np.sort(np.random.default_rng(0).choice(B, k, replace=False))
+        rows = [ctx.sqp_get(int(b)) for b in ids]
+        dump = {"instance": lo + ids}
+        for key in ("x", "g", "mult_g", "mult_x_L", "mult_x_U"):
+            dump[key] = np.stack([r[key] for r in rows])
+        for key in ("obj_val", "status", "iter"):
+            dump[key] = np.array([r[key] for r in rows])
+        dump.update(gathered_ret=g_ret, gathered_iter=g_it, gathered_done=g_done)
+        for key, a in dump.items():
+            np.save(os.path.join(args.dump_outputs, key + ".npy"), np.asarray(a, dtype=np.float64))
+
     # ---- roofline of the dominant kernels, rank-0 local measurement (HIP events on the library's stream)
     N_full = lay0.n + lay0.m
     N = int(c1["kkt_order"])
@@ -366,7 +399,7 @@ def main():
     fac_sec = c1["ldlt_seconds"] - c0["ldlt_seconds"]
     sol_sec = c1["solve_seconds"] - c0["solve_seconds"]
     probe = None
-    if rank == 0:
+    if rank == 0 and args.full:
         import ctypes as C
         v = C.c_double()
         if _lib.lib().sqphip_mfma_f64_peak(local_rank, C.byref(v)) == 0:
@@ -428,7 +461,7 @@ def main():
     # sweep).  achieved = ALGORITHMIC bytes of what the class touches x the units it processed / its time on the stream
     # (averaged over the instance groups, which overlap), against the HBM peak; DESIGN.md section 6 has the byte counts.
     kernels = None
-    if rank == 0 and c1["sparse"] and not args.no_kernel_timing:
+    if rank == 0 and args.full and c1["sparse"] and not args.no_kernel_timing:
         try:
             kt0, cc0 = ctx.kernel_times(), ctx.counters()
             ctx.set_timing(2)
@@ -685,7 +718,7 @@ def main():
                                        "asserted on converging runs (literal_quirks = 0), DESIGN.md section 8"),
                        "note": "with literal_quirks = 1 (the reference's JuMP-sign Hessian, SURVEY.md App. C #2) the "
                                "sub-problems are non-convex and most scenarios never meet the termination test; see "
-                               "`termination` for both sign conventions run to the end"},
+                               "`termination` (--full) for both sign conventions run to the end"},
             "roofline": roofline,
             "kernels": kernels,
             "dense_ldlt": dense,

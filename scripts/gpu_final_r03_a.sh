@@ -4,7 +4,7 @@ R=$GRAFT_REPO_ROOT
 F=$R/gpurun_out/final_r03
 mkdir -p $F
 cd $R
-b() { out=$1; shift; timeout -k 10 600 python bench.py "$@" > $F/$out 2> $F/${out%.json}.err || { echo "FAILED $out"; tail -3 $F/${out%.json}.err; exit 1; }; python scripts/print_bench.py $F/$out; }
+b() { out=$1; shift; timeout -k 10 600 python bench.py --full "$@" > $F/$out 2> $F/${out%.json}.err || { echo "FAILED $out"; tail -3 $F/${out%.json}.err; exit 1; }; python scripts/print_bench.py $F/$out; }
 b r03_bench_steps20.json --steps 20 --warmup 5
 b r03_bench_default.json
 b r03_bench_textbook_sign.json --literal-quirks 0 --no-termination --no-dense-ldlt --no-screening --no-batch-curve

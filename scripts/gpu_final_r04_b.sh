@@ -17,7 +17,7 @@ python3 $R/scripts/trace_by_position.py $F/trace 60 160 > $F/r04_sweep_timeline.
 rm -rf $F/trace
 cd $R
 bash scripts/gpu_r04_stats.sh c118_b64_final --steps 20 --warmup 5 --quick --batch 64 > /dev/null && cp gpurun_out/stats_c118_b64_final/kernel_stats.csv $F/r04_bench_batch64_kernel_stats.csv
-b() { out=$1; shift; timeout -k 10 600 python bench.py "$@" > $F/$out 2> $F/${out%.json}.err || { echo "FAILED $out"; tail -3 $F/${out%.json}.err; exit 1; }; python scripts/print_bench.py $F/$out; }
+b() { out=$1; shift; timeout -k 10 600 python bench.py --full "$@" > $F/$out 2> $F/${out%.json}.err || { echo "FAILED $out"; tail -3 $F/${out%.json}.err; exit 1; }; python scripts/print_bench.py $F/$out; }
 b r04_bench_case14.json --workload case14
 b r04_bench_dense.json --workload dense
 b r04_bench_dense_n1920.json --workload dense --dense-n 1920 --no-cpu-baseline

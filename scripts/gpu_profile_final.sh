@@ -5,7 +5,7 @@ R=$GRAFT_REPO_ROOT
 F=$R/gpurun_out/final
 rm -rf $F && mkdir -p $F
 cd $R
-b() { out=$1; shift; timeout -k 10 600 python bench.py "$@" > $F/$out 2> $F/${out%.json}.err || { echo "FAILED $out"; tail -3 $F/${out%.json}.err; exit 1; }; python scripts/print_bench.py $F/$out; }
+b() { out=$1; shift; timeout -k 10 600 python bench.py --full "$@" > $F/$out 2> $F/${out%.json}.err || { echo "FAILED $out"; tail -3 $F/${out%.json}.err; exit 1; }; python scripts/print_bench.py $F/$out; }
 b r02_bench_default.json
 b r02_bench_steps20.json --steps 20 --warmup 5
 b r02_bench_textbook_sign.json --literal-quirks 0 --no-termination --no-dense-ldlt

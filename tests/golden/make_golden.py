@@ -91,7 +91,22 @@ def main():
                                       "objective": 5906.88, "objective_source": "this build's optimum, consistent with "
                                       "the value PowerModels documents for the case (5907)"}},
                   open(os.path.join(HERE, "case3_dispatch.json"), "w"), indent=1)
+        write_case3_read(m3)
     print("wrote", os.listdir(HERE))
+
+
+def write_case3_read(m3):
+    """case3_reference_read.json: every field read_matpower returns for the reference's examples/acopf/case3.m (matrices
+    as rows of float64, scalars, strings); tests/test_matpower.py rebuilds the case from it without the reference."""
+    fields = {}
+    for k, v in m3.items():
+        if isinstance(v, np.ndarray):
+            fields[k] = {"kind": "matrix", "shape": list(v.shape), "rows": v.tolist()}
+        else:
+            fields[k] = {"kind": "string" if isinstance(v, str) else "number", "value": v}
+    json.dump({"source": "read_matpower of examples/acopf/case3.m of the reference (SqpSolver.jl), recorded by "
+                         "tests/golden/make_golden.py", "fields": fields},
+              open(os.path.join(HERE, "case3_reference_read.json"), "w"), indent=1)
 
 
 if __name__ == "__main__":

@@ -276,6 +276,18 @@ def test_bench_starts_its_own_ranks_and_refuses_a_mismatched_launcher():
     assert r.returncode == 2 and "torch.distributed.run" in r.stderr and r.stdout.strip() == ""
 
 
+def test_bench_refuses_zero_steps_and_takes_full_and_dump_outputs():
+    """--steps sets the number of timed steps, so 0 (which sqphip_sqp_run reads as "to termination") is refused before
+    anything touches a GPU; --full and --dump-outputs are options of every run."""
+    import subprocess
+    import sys
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], capture_output=True, text=True,
+                       timeout=120)
+    assert r.returncode == 2 and "--steps must be at least 1" in r.stderr and r.stdout.strip() == ""
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0 and "--full" in r.stdout and "--dump-outputs" in r.stdout
+
+
 def test_acceptable_termination_rules_are_the_same_in_oracle_and_device():
     """The interior-point method ends on `e0 <= tol` or acceptably: 8 iterates within 100 x tol, 15 within 1000 x, 25 within
     10^4 x (the third rule is what lets the 9241-bus line-outage scenarios get past their flat QPs).

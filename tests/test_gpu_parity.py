@@ -15,7 +15,7 @@ import scipy.sparse as sp
 
 import sqpsolver_jl_amd as pkg
 from sqpsolver_jl_amd import _lib
-from sqpsolver_jl_amd.acopf_synth import acopf_synth, acopf_layout, acr_layout, acwr_layout, contingency, renumber_buses, CASES
+from sqpsolver_jl_amd.acopf_synth import acopf_synth, acopf_layout, acr_layout, acwr_layout, contingency, renumber_buses, synth_case, CASES
 from oracle import oracle as O
 import host_mirror as HM          # tests/host_mirror.py: stand-in for the Julia host of the drop-in seat (test harness)
 
@@ -272,6 +272,38 @@ def test_bench_typed_with_two_gpus_starts_its_ranks_and_prints_one_line(tmp_path
     lines = [json.loads(ln) for ln in r.stdout.splitlines() if ln.strip().startswith("{")]
     assert len(lines) == 1 and lines[0]["n_gpus"] == 2 and lines[0]["scaling"] == "weak"
     assert lines[0]["config"]["instances_per_gpu"] == 8 and lines[0]["config"]["instances_total"] == 16
+
+
+def test_bench_dump_outputs_are_the_results_of_the_last_timed_step(tmp_path):
+    """`bench.py --dump-outputs DIR`: float64 arrays of what sqphip_sqp_get returns for every instance after the timed
+    steps, and the gathered status table; the same bits from run to run (seeded inputs) and whether or not --full runs its
+    records afterwards.  A plain run carries no record of --full; --steps is the number of timed steps."""
+    import subprocess, sys as _sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    common = ["--gpus", "1", "--workload", "case14", "--batch", "8", "--steps", "3", "--warmup", "1"]
+    lines = {}
+    for tag, extra in (("a", []), ("b", []), ("full", ["--full", "--quick"])):
+        r = subprocess.run([_sys.executable, os.path.join(root, "bench.py")] + common + extra + ["--dump-outputs", str(tmp_path / tag)],
+                           cwd=root, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-800:]
+        lines[tag] = json.loads(r.stdout.strip().splitlines()[-1])
+    a = lines["a"]
+    assert a["steps"] == 3 and a["ms_per_step"] > 0 and a["kernels"] is None and a["roofline"]["onbox_mfma_probe_tflops"] is None
+    assert lines["full"]["kernels"] is not None
+    for k in ("qp_solved", "ipm_iterations", "kkt_factorisations", "sweeps"):
+        assert a["config"][k] == lines["b"]["config"][k] == lines["full"]["config"][k], k
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == sorted(f"{n}.npy" for n in ("instance", "x", "g", "mult_g", "mult_x_L", "mult_x_U", "obj_val", "status", "iter",
+                                                "gathered_ret", "gathered_iter", "gathered_done"))
+    for n in names:
+        ref = np.load(tmp_path / "a" / n)
+        assert ref.dtype == np.float64 and ref.shape[0] == 8, n
+        for tag in ("b", "full"):
+            assert np.array_equal(ref, np.load(tmp_path / tag / n)), (tag, n)
+    load = lambda n: np.load(tmp_path / "a" / f"{n}.npy")
+    assert np.isfinite(load("x")).all() and load("x").shape[1] == acopf_layout(synth_case("case14", None)).n
+    assert np.array_equal(load("instance"), np.arange(8))
+    assert np.array_equal(load("status"), load("gathered_ret")) and np.array_equal(load("iter"), load("gathered_iter"))
 
 
 # ------------------------------------------------------------------ K1: device ACOPF evaluator
