@@ -267,8 +267,9 @@ int sqphip_acopf_set_dclines(sqphip_ctx *ctx, int32_t ndc, const double *loss1);
  * host (sqpsolver.jl_amd/acopf_synth.py, Network.branch_coeffs); an outaged branch is 12 zeros. */
 int sqphip_acopf_set_instance(sqphip_ctx *ctx, int32_t inst, const double *ohm, const double *c2, const double *c1,
                               const double *x0);
-/* Evaluate the five callbacks on the device for instance `inst` at host point x (parity tests).
- * Any output may be NULL. lambda/sigma only matter for hval. */
+/* Evaluate the five callbacks on the device for instance `inst` at host point x (parity tests): the attached device
+ * callbacks, whichever attach provided them (ACOPF, dense, QCQP).  Any output may be NULL. lambda/sigma only matter for
+ * hval. */
 int sqphip_acopf_eval(sqphip_ctx *ctx, int32_t inst, const double *x, double sigma,
                       const double *lambda, double *f, double *grad, double *g, double *jval,
                       double *hval);
@@ -282,6 +283,31 @@ int sqphip_acopf_eval(sqphip_ctx *ctx, int32_t inst, const double *x, double sig
  * Newton matrix of order n + m on the MFMA path (ldlt.hip). */
 int sqphip_dense_attach(sqphip_ctx *ctx, const double *Q, const double *A, double kappa);
 int sqphip_dense_set_instance(sqphip_ctx *ctx, int32_t inst, const double *c, const double *x0);
+/* A general sparse QCQP for the batched run -- any user model whose objective and rows are at most quadratic:
+ *     min  f0 + c'x + 1/2 x'Q0 x    s.t.  gL_i <= g0_i + a_i'x + 1/2 x'Q_i x <= gU_i  (i = 1..m),   xL <= x <= xU
+ * Terms are triplets with 1-based indices: Q0 as (q0r, q0c, q0v), A as (ar = row, ac = column, av), every Q_i as
+ * (qi = row, qr, qc, qv).  A Q entry may sit in either triangle and duplicates are summed; it folds into the lower
+ * triangle with the value convention of the Hessian COO: an off-diagonal v contributes v x_r x_c, a diagonal v
+ * contributes 1/2 v x_r^2.  The context must have been created with a Jacobian COO that holds every entry the terms need
+ * (A's, and (i, r), (i, c) of every Q_i term) and a Hessian COO that holds the lower entry of every Q0 / Q_i term (with
+ * nnzH = 0 only the Jacobian is checked: the SLP path); rows 1..num_linear must carry no quadratic term.  The values
+ * given here (c [n] and g0 [m] may be NULL: zeros) start every instance.  Once, on the host, the call builds gather
+ * plans from the terms and the COO structures (per row, per variable, per Jacobian and per Hessian COO slot); the
+ * device evaluates them per instance with fixed summation orders (bit-reproducible, independent of the slot).
+ * Returns SQPHIP_EINVAL, sqphip_last_error naming the first offending term, on an index out of range, an entry the COO
+ * structures lack or a quadratic term in a linear row; SQPHIP_ESTATE on a context attached before (any *_attach).
+ * On a QCQP context sqphip_acopf_set_instance, _set_shunts, _set_dclines and sqphip_sqp_stream_begin / _set return
+ * SQPHIP_EINVAL: the scenario queue does not carry QCQP values.  sqphip_acopf_eval probes the attached device
+ * callbacks, the QCQP evaluator included. */
+int sqphip_qcqp_attach(sqphip_ctx *ctx, int64_t nnzQ0, const int64_t *q0r, const int64_t *q0c, const double *q0v,
+                       int64_t nnzA, const int64_t *ar, const int64_t *ac, const double *av,
+                       int64_t nnzQ, const int64_t *qi, const int64_t *qr, const int64_t *qc, const double *qv,
+                       const double *c, const double *g0, double f0);
+/* Per-instance values, in the term order of the attach (f0 one value, c [n], q0v [nnzQ0], g0 [m], av [nnzA],
+ * qv [nnzQ]) and the start x0 [n]; any pointer may be NULL: keep.  Same structure, other coefficients (zeros allowed):
+ * contingency-style scenarios.  Bounds go through sqphip_set_bounds. */
+int sqphip_qcqp_set_instance(sqphip_ctx *ctx, int32_t inst, const double *f0, const double *c, const double *q0v,
+                             const double *g0, const double *av, const double *qv, const double *x0);
 /* Run SQP-TR for every instance until each has terminated or done `max_outer` more outer
  * iterations (0 = no cap beyond options.max_iter).  Restartable: state stays on the device. */
 int sqphip_sqp_reset(sqphip_ctx *ctx);

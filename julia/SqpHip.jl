@@ -180,6 +180,26 @@ hip_acopf_attach_acwr(ctx::Ptr{Cvoid}, nb, ng, nl, f_bus::Vector{Int32}, t_bus::
                        Ptr{Cdouble}, Int32, Int32, Ptr{Int32}, Ptr{Int32}, Ptr{Int32}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}),
                       ctx, nb, ng, nl, f_bus, t_bus, gen_bus, bal_ptr, bal_colP, bal_colQ, bal_coef, ref_bus,
                       length(bp_i), bp_i, bp_j, br_bp, br_sig, bp_tmin, bp_tmax))
+# ---- a general sparse QCQP in the batched run (sqphip_qcqp_attach): any model whose objective and constraints are at most
+# quadratic -- MOI ScalarQuadraticFunction / ScalarAffineFunction rows (INTEGRATION.md section 4).  1-based triplets; a Q
+# entry (either triangle, duplicates summed) contributes v x_r x_c off the diagonal and v x_r^2 / 2 on it.  The context's
+# Jacobian / Hessian COO must hold every entry the terms need; rows 1..num_linear carry no quadratic term.  Quadratic
+# functions only; the scenario queue does not carry QCQP values (hip_stream_* refuse a QCQP context).
+hip_qcqp_attach(ctx::Ptr{Cvoid}, q0r::Vector{Int64}, q0c::Vector{Int64}, q0v::Vector{Float64}, ar::Vector{Int64},
+                ac::Vector{Int64}, av::Vector{Float64}, qi::Vector{Int64}, qr::Vector{Int64}, qc::Vector{Int64},
+                qv::Vector{Float64}, c::Vector{Float64}, g0::Vector{Float64}, f0::Real) =
+    _check(ctx, ccall((:sqphip_qcqp_attach, LIBSQPHIP), Cint,
+                      (Ptr{Cvoid}, Int64, Ptr{Int64}, Ptr{Int64}, Ptr{Cdouble}, Int64, Ptr{Int64}, Ptr{Int64}, Ptr{Cdouble},
+                       Int64, Ptr{Int64}, Ptr{Int64}, Ptr{Int64}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Cdouble),
+                      ctx, length(q0v), q0r, q0c, q0v, length(av), ar, ac, av, length(qv), qi, qr, qc, qv, c, g0, f0))
+# per-instance values in the attach's term order; `nothing` keeps what the instance has (inst is 0-based)
+_vals(v) = v === nothing ? Ptr{Cdouble}(C_NULL) : v
+hip_qcqp_set_instance(ctx::Ptr{Cvoid}, inst::Integer; f0 = nothing, c = nothing, q0v = nothing, g0 = nothing, av = nothing,
+                      qv = nothing, x0 = nothing) =
+    _check(ctx, ccall((:sqphip_qcqp_set_instance, LIBSQPHIP), Cint,
+                      (Ptr{Cvoid}, Int32, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble},
+                       Ptr{Cdouble}), ctx, inst, _vals(f0 === nothing ? nothing : Float64[f0]), _vals(c), _vals(q0v), _vals(g0),
+                      _vals(av), _vals(qv), _vals(x0)))
 hip_sqp_run(ctx::Ptr{Cvoid}, max_outer::Integer = 0) =
     _check(ctx, ccall((:sqphip_sqp_run, LIBSQPHIP), Cint, (Ptr{Cvoid}, Int32), ctx, max_outer))
 hip_stream_begin(ctx::Ptr{Cvoid}, n_scenarios::Integer) =

@@ -2,6 +2,7 @@
 #pragma once
 #include "ctx.hpp"
 #include "dev_util.hpp"
+#include "qcqp_dev.hpp"
 #include <cmath>
 
 namespace sqphip {
@@ -306,8 +307,8 @@ static __device__ __forceinline__ void dense_eval(const DV &d, int inst, const d
         }
 }
 
-// any of f_out, grad, gv, jv, hv may be null
-static __device__ __forceinline__ void acopf_eval(const DV &d, int inst, const double *__restrict__ x, double sigma,
+// the dedicated evaluators (ACOPF forms, dense NLP); any of f_out, grad, gv, jv, hv may be null
+static __device__ __forceinline__ void acopf_eval_dedicated(const DV &d, int inst, const double *__restrict__ x, double sigma,
                            const double *__restrict__ lam, double *f_out, double *grad, double *gv,
                            double *jv, double *hv)
 {
@@ -436,6 +437,15 @@ static __device__ __forceinline__ void acopf_eval(const DV &d, int inst, const d
             }
         }
     }
+}
+
+// the attached device callbacks, whichever attach provided them; any of f_out, grad, gv, jv, hv may be null
+static __device__ __forceinline__ void acopf_eval(const DV &d, int inst, const double *__restrict__ x, double sigma,
+                           const double *__restrict__ lam, double *f_out, double *grad, double *gv,
+                           double *jv, double *hv)
+{
+    if (d.qc) { qcqp_eval(d, inst, x, sigma, lam, f_out, grad, gv, jv, hv); return; }          // uniform over the launch
+    acopf_eval_dedicated(d, inst, x, sigma, lam, f_out, grad, gv, jv, hv);
 }
 
 }  // namespace sqphip

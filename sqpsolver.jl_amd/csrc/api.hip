@@ -3,11 +3,14 @@
 // /root/reference/src/algorithms/sqp_trust_region.jl:47-48,56-57 plus the symmetric mirroring of
 // sqp.jl:96-101), lays the batch out in HBM and forwards to the kernels.
 #include "ctx.hpp"
+#include "qcqp_dev.hpp"
 #include <algorithm>
+#include <array>
 #include <chrono>
 #include <cmath>
 #include <cstring>
 #include <tuple>
+#include <unordered_map>
 
 using namespace sqphip;
 
@@ -136,6 +139,7 @@ void make_lanes(Ctx &C)
         L->mfp_ = C.mfp_;
         L->trans_period = C.trans_period; L->mf_big_lds = C.mf_big_lds; L->post_split = C.post_split; L->side_mode = C.side_mode; L->spec_tail = C.spec_tail; L->spec_mode0 = C.spec_mode0;
         L->d = group_view(C.d, lo, hi - lo, g);
+        if (L->d.qcv) L->d.qcv += (long)lo * C.qc_nv;
         // the first group runs on the owner's stream (idle during sqphip_sqp_run): HIP maps streams onto four hardware
         // queues by default, and a fifth stream would share one -- measured: 3131 QP/s with five streams against 5216
         // with four (or with GPU_MAX_HW_QUEUES=8)
@@ -218,6 +222,8 @@ extern "C" int sqphip_create(sqphip_ctx **out, int64_t n, int64_t m, int64_t num
         DV &d = C.d;
         std::memset(&d, 0, sizeof(d));
         C.n = n; C.m = m;
+        C.h_jrow.assign(jrow, jrow + nnzJ); C.h_jcol.assign(jcol, jcol + nnzJ);
+        C.h_hrow.assign(hrow, hrow + nnzH); C.h_hcol.assign(hcol, hcol + nnzH);
         const int B = batch;
         d.n = (int)n; d.m = (int)m; d.nlin = (int)num_linear; d.N = (int)(n + m);
         d.Npad = (d.N + 63) / 64 * 64; d.B = B;
@@ -882,9 +888,16 @@ extern "C" int sqphip_acopf_attach_acwr(sqphip_ctx *h, int32_t nb, int32_t ng, i
     });
 }
 
+static int qcqp_refuse(sqphip_ctx *h, const char *fn)
+{
+    h->c.err = std::string(fn) + ": not available on a QCQP context (sqphip_qcqp_attach; use sqphip_qcqp_set_instance)";
+    return SQPHIP_EINVAL;
+}
+
 extern "C" int sqphip_acopf_set_shunts(sqphip_ctx *h, int32_t nsh, const int32_t *sh_bus, const double *gs,
                                        const double *bs)
 {
+    if (h && h->c.d.qc) return qcqp_refuse(h, "sqphip_acopf_set_shunts");
     if (!h || !h->c.acopf_attached || nsh < 0) return SQPHIP_EINVAL;
     Ctx &C0 = h->c;
     const int nl = C0.d.nl, ng = C0.d.ng, nb = C0.d.nb;
@@ -914,6 +927,7 @@ extern "C" int sqphip_acopf_set_shunts(sqphip_ctx *h, int32_t nsh, const int32_t
 
 extern "C" int sqphip_acopf_set_dclines(sqphip_ctx *h, int32_t ndc, const double *loss1)
 {
+    if (h && h->c.d.qc) return qcqp_refuse(h, "sqphip_acopf_set_dclines");
     if (!h || !h->c.acopf_attached || ndc != h->c.d.ndc || (ndc > 0 && !loss1)) return SQPHIP_EINVAL;
     if (ndc == 0) return SQPHIP_OK;
     return guarded(h, [&](Ctx &C) {
@@ -927,6 +941,7 @@ extern "C" int sqphip_acopf_set_dclines(sqphip_ctx *h, int32_t ndc, const double
 extern "C" int sqphip_acopf_set_instance(sqphip_ctx *h, int32_t inst, const double *ohm, const double *c2,
                                          const double *c1, const double *x0)
 {
+    if (h && h->c.d.qc) return qcqp_refuse(h, "sqphip_acopf_set_instance");
     if (!h || !h->c.acopf_attached || inst < 0 || inst >= h->c.d.B) return SQPHIP_EINVAL;
     return guarded(h, [&](Ctx &C) {
         DV &d = C.d;
@@ -965,6 +980,174 @@ extern "C" int sqphip_dense_set_instance(sqphip_ctx *h, int32_t inst, const doub
     return guarded(h, [&](Ctx &C) {
         DV &d = C.d;
         h2d(C, d.dnc + (size_t)inst * d.n, c, d.n);
+        h2d(C, d.x0 + (size_t)inst * d.n, x0, d.n);
+        SQPHIP_HIP_OK(hipStreamSynchronize(C.stream));
+        return SQPHIP_OK;
+    });
+}
+
+// ---- a general sparse QCQP (qcqp_dev.hpp qcqp_eval): the gather plans are built here, once, from the terms and the COO
+// structures of sqphip_create
+static int qcqp_fail(sqphip_ctx *h, const std::string &msg)
+{
+    h->c.err = "sqphip_qcqp_attach: " + msg;
+    return SQPHIP_EINVAL;
+}
+
+static std::string qcqp_term(const char *kind, int64_t t, int64_t a, int64_t b, int64_t c = 0)
+{
+    std::string s = std::string(kind) + " term " + std::to_string(t) + " (" + std::to_string(a) + ", " + std::to_string(b);
+    if (c) s += ", " + std::to_string(c);
+    return s + ")";
+}
+
+// a gather plan: (owner, value index, variable or row) entries in the order they were produced -> CSR by owner, the
+// entries of one owner kept in that order
+struct PlanCsr {
+    std::vector<std::array<int, 3>> ent;
+    void finish(int owners, std::vector<int> &ptr, std::vector<int> &v, std::vector<int> &w) const
+    {
+        ptr.assign(owners + 1, 0);
+        for (auto &e : ent) ptr[e[0] + 1]++;
+        for (int r = 0; r < owners; ++r) ptr[r + 1] += ptr[r];
+        std::vector<int> fill(ptr.begin(), ptr.end() - 1);
+        v.assign(ent.size() ? ent.size() : 1, 0); w.assign(v.size(), 0);
+        for (auto &e : ent) { const int k = fill[e[0]]++; v[k] = e[1]; w[k] = e[2]; }
+    }
+};
+
+extern "C" int sqphip_qcqp_attach(sqphip_ctx *h, int64_t nnzQ0, const int64_t *q0r, const int64_t *q0c, const double *q0v,
+                                  int64_t nnzA, const int64_t *ar, const int64_t *ac, const double *av, int64_t nnzQ,
+                                  const int64_t *qi, const int64_t *qr, const int64_t *qc, const double *qv,
+                                  const double *c, const double *g0, double f0)
+{
+    if (!h) return SQPHIP_EINVAL;
+    Ctx &C0 = h->c;
+    if (C0.acopf_attached) {
+        C0.err = "sqphip_qcqp_attach: the context already has device callbacks (an earlier *_attach)";
+        return SQPHIP_ESTATE;
+    }
+    if (nnzQ0 < 0 || nnzA < 0 || nnzQ < 0) return qcqp_fail(h, "negative term count");
+    if ((nnzQ0 > 0 && (!q0r || !q0c || !q0v)) || (nnzA > 0 && (!ar || !ac || !av)) ||
+        (nnzQ > 0 && (!qi || !qr || !qc || !qv))) return qcqp_fail(h, "null term array");
+    const int64_t n = C0.d.n, m = C0.d.m, nlin = C0.d.nlin, nnzJ = C0.d.nnzj_coo, nnzH = C0.d.nnzh_coo;
+    // first COO slot of every structural entry (later duplicates get no plan entries: 0, gather_csc sums them)
+    std::unordered_map<int64_t, int> jslot, hslot;
+    for (int64_t k = nnzJ - 1; k >= 0; --k) jslot[(C0.h_jrow[k] - 1) * n + (C0.h_jcol[k] - 1)] = (int)k;
+    for (int64_t k = nnzH - 1; k >= 0; --k) {
+        const int64_t r = C0.h_hrow[k] - 1, cc = C0.h_hcol[k] - 1;
+        hslot[std::max(r, cc) * n + std::min(r, cc)] = (int)k;
+    }
+    auto jfind = [&](int64_t i, int64_t j) { auto it = jslot.find(i * n + j); return it == jslot.end() ? -1 : it->second; };
+    auto hfind = [&](int64_t r, int64_t cc) {
+        auto it = hslot.find(std::max(r, cc) * n + std::min(r, cc)); return it == hslot.end() ? -1 : it->second; };
+    const std::string jmiss = " needs a Jacobian entry that the structure of sqphip_create lacks",
+                      hmiss = " needs a Hessian entry that the structure of sqphip_create lacks";
+    // values of an instance: f0 | c | Q0 | g0 | A | Q
+    const int off_c = 1, off_q0 = off_c + (int)n, off_g0 = off_q0 + (int)nnzQ0, off_a = off_g0 + (int)m,
+              off_q = off_a + (int)nnzA;
+    const long nv = (long)off_q + nnzQ;
+    PlanCsr G, F, J, H;
+    for (int64_t t = 0; t < nnzQ0; ++t) {
+        const int64_t r = q0r[t] - 1, cc = q0c[t] - 1;
+        if (r < 0 || r >= n || cc < 0 || cc >= n) return qcqp_fail(h, qcqp_term("Q0", t + 1, q0r[t], q0c[t]) + ": index out of range");
+        const int hs = hfind(r, cc);
+        if (nnzH > 0 && hs < 0) return qcqp_fail(h, qcqp_term("Q0", t + 1, q0r[t], q0c[t]) + hmiss);
+        const int v = off_q0 + (int)t;
+        F.ent.push_back({(int)r, v, (int)cc});
+        if (r != cc) F.ent.push_back({(int)cc, v, (int)r});
+        if (hs >= 0) H.ent.push_back({hs, v, -1});
+    }
+    for (int64_t t = 0; t < nnzA; ++t) {
+        const int64_t i = ar[t] - 1, j = ac[t] - 1;
+        if (i < 0 || i >= m || j < 0 || j >= n) return qcqp_fail(h, qcqp_term("A", t + 1, ar[t], ac[t]) + ": index out of range");
+        const int js = jfind(i, j);
+        if (js < 0) return qcqp_fail(h, qcqp_term("A", t + 1, ar[t], ac[t]) + jmiss);
+        const int v = off_a + (int)t;
+        G.ent.push_back({(int)i, v, (int)j});
+        J.ent.push_back({js, v, -1});
+    }
+    std::vector<int> gsecond(nnzA, -1);       // second variable of every row-plan entry (-1: linear), in production order
+    for (int64_t t = 0; t < nnzQ; ++t) {
+        const int64_t i = qi[t] - 1, r = qr[t] - 1, cc = qc[t] - 1;
+        const std::string what = qcqp_term("Q", t + 1, qi[t], qr[t], qc[t]);
+        if (i < 0 || i >= m || r < 0 || r >= n || cc < 0 || cc >= n) return qcqp_fail(h, what + ": index out of range");
+        if (i < nlin) return qcqp_fail(h, what + ": a quadratic term in row " + std::to_string(i + 1) +
+                                              ", one of the num_linear = " + std::to_string(nlin) + " linear rows");
+        const int jr = jfind(i, r), jc = jfind(i, cc), hs = hfind(r, cc);
+        if (jr < 0 || jc < 0) return qcqp_fail(h, what + jmiss);
+        if (nnzH > 0 && hs < 0) return qcqp_fail(h, what + hmiss);
+        const int v = off_q + (int)t;
+        G.ent.push_back({(int)i, v, (int)r}); gsecond.push_back((int)cc);
+        J.ent.push_back({jr, v, (int)cc});
+        if (r != cc) J.ent.push_back({jc, v, (int)r});
+        if (hs >= 0) H.ent.push_back({hs, v, (int)i});
+    }
+    std::vector<int> g_ptr, g_v, g_a, g_b, f_ptr, f_v, f_x, j_ptr, j_v, j_x, h_ptr, h_v, h_r;
+    G.finish((int)m, g_ptr, g_v, g_a);
+    {   // the second variables follow their entries through the same placement
+        std::vector<int> fill(g_ptr.begin(), g_ptr.end() - 1);
+        g_b.assign(g_v.size(), -1);
+        for (size_t e = 0; e < G.ent.size(); ++e) g_b[fill[G.ent[e][0]]++] = gsecond[e];
+    }
+    F.finish((int)n, f_ptr, f_v, f_x);
+    J.finish((int)nnzJ, j_ptr, j_v, j_x);
+    H.finish((int)nnzH, h_ptr, h_v, h_r);
+    std::vector<double> val0(nv, 0.0);
+    val0[0] = f0;
+    if (c) std::copy(c, c + n, val0.begin() + off_c);
+    if (nnzQ0) std::copy(q0v, q0v + nnzQ0, val0.begin() + off_q0);
+    if (g0) std::copy(g0, g0 + m, val0.begin() + off_g0);
+    if (nnzA) std::copy(av, av + nnzA, val0.begin() + off_a);
+    if (nnzQ) std::copy(qv, qv + nnzQ, val0.begin() + off_q);
+    std::vector<int2> q0(nnzQ0 ? nnzQ0 : 1, int2{0, 0});
+    for (int64_t t = 0; t < nnzQ0; ++t) q0[t] = int2{(int)std::max(q0r[t], q0c[t]) - 1, (int)std::min(q0r[t], q0c[t]) - 1};
+    // packed plans: the row pointers back to back, the entries as int2 / int4
+    std::vector<int> ptr(g_ptr);
+    const int fp = (int)ptr.size(); ptr.insert(ptr.end(), f_ptr.begin(), f_ptr.end());
+    const int jp = (int)ptr.size(); ptr.insert(ptr.end(), j_ptr.begin(), j_ptr.end());
+    const int hp = (int)ptr.size(); ptr.insert(ptr.end(), h_ptr.begin(), h_ptr.end());
+    auto pack2 = [](const std::vector<int> &a, const std::vector<int> &b) {
+        std::vector<int2> o(a.size());
+        for (size_t k = 0; k < a.size(); ++k) o[k] = int2{a[k], b[k]};
+        return o;
+    };
+    std::vector<int4> ge(g_v.size());
+    for (size_t k = 0; k < g_v.size(); ++k) ge[k] = int4{g_v[k], g_a[k], g_b[k], 0};
+    return guarded(h, [&](Ctx &C) {
+        DV &d = C.d;
+        QcqpDev P = {};
+        P.n = (int)n; P.m = (int)m; P.nv = (int)nv; P.nq0 = (int)nnzQ0;
+        P.off_c = off_c; P.off_q0 = off_q0; P.off_g0 = off_g0;
+        P.f_ptr = fp; P.j_ptr = jp; P.h_ptr = hp;
+        P.ptr = C.upload(ptr); P.q0 = C.upload(q0); P.ge = C.upload(ge);
+        P.fe = C.upload(pack2(f_v, f_x)); P.je = C.upload(pack2(j_v, j_x)); P.he = C.upload(pack2(h_v, h_r));
+        QcqpDev *pd = (QcqpDev *)C.dalloc<char>(sizeof(QcqpDev));
+        SQPHIP_HIP_OK(hipMemcpyAsync(pd, &P, sizeof(QcqpDev), hipMemcpyHostToDevice, C.stream));
+        std::vector<double> all((size_t)d.B * nv);
+        for (int b = 0; b < d.B; ++b) std::copy(val0.begin(), val0.end(), all.begin() + (size_t)b * nv);
+        d.qcv = C.upload(all);
+        d.qc = pd;
+        C.qc_nv = nv;
+        const long off[7] = {0, off_c, off_q0, off_g0, off_a, off_q, nv};
+        std::copy(off, off + 7, C.qc_off);
+        SQPHIP_HIP_OK(hipStreamSynchronize(C.stream));
+        C.acopf_attached = true;           // (the batched run! has its device callbacks)
+        make_lanes(C);
+        return SQPHIP_OK;
+    });
+}
+
+extern "C" int sqphip_qcqp_set_instance(sqphip_ctx *h, int32_t inst, const double *f0, const double *c, const double *q0v,
+                                        const double *g0, const double *av, const double *qv, const double *x0)
+{
+    if (!h || !h->c.d.qc || inst < 0 || inst >= h->c.d.B) return SQPHIP_EINVAL;
+    return guarded(h, [&](Ctx &C) {
+        DV &d = C.d;
+        const long *o = C.qc_off;           // f0 | c | Q0 | g0 | A | Q | end
+        double *v = d.qcv + (size_t)inst * C.qc_nv;
+        const double *src[6] = {f0, c, q0v, g0, av, qv};
+        for (int k = 0; k < 6; ++k) h2d(C, v + o[k], src[k], (size_t)(o[k + 1] - o[k]));
         h2d(C, d.x0 + (size_t)inst * d.n, x0, d.n);
         SQPHIP_HIP_OK(hipStreamSynchronize(C.stream));
         return SQPHIP_OK;
@@ -1227,6 +1410,7 @@ extern "C" int sqphip_sqp_last_request(sqphip_ctx *h, int32_t inst, int32_t *mod
 // ---- scenario queue: more scenarios than slots ----------------------------------------------------------------
 extern "C" int sqphip_sqp_stream_begin(sqphip_ctx *h, int32_t n_scenarios)
 {
+    if (h && h->c.d.qc) return qcqp_refuse(h, "sqphip_sqp_stream_begin");
     if (!h || !h->c.acopf_attached || n_scenarios <= 0) return SQPHIP_EINVAL;
     return guarded(h, [&](Ctx &C) {
         DV &d = C.d;
@@ -1263,6 +1447,7 @@ extern "C" int sqphip_sqp_stream_set(sqphip_ctx *h, int32_t scen, const double *
                                      const double *gU, const double *ohm, const double *c2, const double *c1,
                                      const double *x0)
 {
+    if (h && h->c.d.qc) return qcqp_refuse(h, "sqphip_sqp_stream_set");
     if (!h || scen < 0 || scen >= h->c.d.stream.M || !xL || !xU || !gL || !gU || !ohm || !c2 || !c1 || !x0) return SQPHIP_EINVAL;
     for (int i = 0; i < h->c.d.m; ++i) {
         if (gL[i] == -INFINITY && gU[i] == INFINITY) return SQPHIP_EINVAL;

@@ -108,6 +108,8 @@ struct StreamDev {
     int *rstat, *riter;                               // ... run! status (src/status.jl), iterations
 };
 
+struct QcqpDev;                           // qcqp_dev.hpp
+
 // everything kernels need, by value
 struct DV {
     int n, m, nlin, N, Npad, ld, B;       // N = n + m, Npad = stride of the full-length vectors rhs / sol / wN
@@ -181,6 +183,9 @@ struct DV {
     // options
     double tol_direction, tol_residual, tol_infeas, init_mu, tr_size;
     int max_iter, use_soc, literal_quirks;
+    // ---- general sparse QCQP evaluator data
+    const QcqpDev *qc;                    // non-null: a general sparse QCQP (qcqp_dev.hpp qcqp_eval; sqphip_qcqp_attach), its plans in HBM
+    double *qcv;                          // ... its values [B][qc->nv]
 };
 
 // phase codes by the side a kernel runs on (see the enum)
@@ -223,6 +228,9 @@ struct Ctx {
     hipStream_t stream = nullptr;
     int *h_counters = nullptr;  // pinned
     std::vector<int> h_kpos;    // host copy of DV::kpos (row -> kept position or -1)
+    std::vector<int64_t> h_jrow, h_jcol, h_hrow, h_hcol;   // host copies of the COO structures of sqphip_create (1-based)
+    long qc_nv = 0;             // values per instance of an attached QCQP (DV::qcv) ...
+    long qc_off[7] = {};        // ... and where its parts start: f0, c, Q0, g0, A, Q, end
     bool acopf_attached = false;
     bool mf_big_lds = false;        // the multifrontal kernels were granted 160 KB of dynamic LDS on this context's device (mf_device_setup)
     bool stream_started = false;    // scenario queue: the slots have been armed (sqphip_sqp_stream_run / _run_some)

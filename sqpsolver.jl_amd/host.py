@@ -287,6 +287,28 @@ class Context:
         self._ck(self.L.sqphip_set_bounds(self.h, inst, _d(_f(lay.xL)), _d(_f(lay.xU)), _d(_f(lay.gL)), _d(_f(lay.gU))))
         self._ck(self.L.sqphip_dense_set_instance(self.h, inst, _d(_f(nlp.c)), _d(_f(lay.x0 if x0 is None else x0))))
 
+    # ---- a general sparse QCQP (qcqp.py; csrc/qcqp_dev.hpp qcqp_eval)
+    def qcqp_attach(self, q):
+        """Structure of the batch and the values every instance starts with (sqphip_qcqp_attach)."""
+        t = [np.ascontiguousarray(a, dtype=np.int64) for a in (q.q0r, q.q0c, q.ar, q.ac, q.qi, q.qr, q.qc)]
+        v = [_f(a) for a in (q.q0v, q.av, q.qv, q.c, q.g0)]
+        self._ck(self.L.sqphip_qcqp_attach(self.h, len(v[0]), _l(t[0]), _l(t[1]), _d(v[0]), len(v[1]), _l(t[2]), _l(t[3]),
+                                           _d(v[1]), len(v[2]), _l(t[4]), _l(t[5]), _l(t[6]), _d(v[2]), _d(v[3]), _d(v[4]),
+                                           float(q.f0)))
+
+    def qcqp_set_instance(self, inst, q=None, x0=None, **values):
+        """Per-instance values (sqphip_qcqp_set_instance).  With a Qcqp q: its bounds, every value and its start; keywords
+        f0, c, q0v, g0, av, qv override single parts, and what is given neither way is kept."""
+        if q is not None:
+            self.set_bounds(inst, q)
+            values = {**{k: getattr(q, k) for k in ("f0", "c", "q0v", "g0", "av", "qv")}, **values}
+            x0 = q.x0 if x0 is None else x0
+        bad = set(values) - {"f0", "c", "q0v", "g0", "av", "qv"}
+        if bad:
+            raise TypeError(f"qcqp_set_instance: unknown values {sorted(bad)}")
+        arr = [None if values.get(k) is None else _f(np.atleast_1d(values[k])) for k in ("f0", "c", "q0v", "g0", "av", "qv")]
+        self._ck(self.L.sqphip_qcqp_set_instance(self.h, inst, *[_d(a) for a in arr], _d(_f(x0))))
+
     def acopf_eval(self, inst, x, sigma=1.0, lam=None):
         f = C.c_double(); grad = np.zeros(self.n); g = np.zeros(self.m)
         jv = np.zeros(self.nnzj); hv = np.zeros(self.nnzh) if lam is not None else None
