@@ -35,6 +35,29 @@ double sqphip_mf_host_spine_err(void);
 int sqphip_mf_solve_test(sqphip_ctx *ctx, int32_t inst, const double *Jval, const double *Hval, const double *Dd,
                          const double *sigp, const double *hd, const int32_t *rtype, double hsc, double dw,
                          const double *rhs, double *sol_fused, double *sol_standalone, double *dinv_by_unknown);
+/* Batched twin of sqphip_mf_solve_test: every instance with active[b] != 0 gets its own values and interior-point state
+ * (Hessian scale, delta_w, last accepted delta_w, failed factorisations so far) and goes through one sweep's factorisation
+ * (both candidate shifts, right-hand side fused in), inertia test (by the path the sweep takes) and backward solve; then the
+ * stand-alone forward / backward solve of the same right-hand side.  Per-instance arrays back to back: Jval [B][nnzJ],
+ * Hval [B][nnzH], Dd / rtype [B][m], sigp / hd [B][n], rhs and outputs [B][nu] in unknown order.  decision [B][5]: outcome
+ * (0 idle, 1 another shift needed, 2 passed, 3 given up), sel, n_factor, fac_attempt and -- derived on the host from the
+ * inputs by the rule of mf_speculates, not reported by the device -- whether the instance speculates; dw_out [B]: delta_w
+ * after the decision.  dinv1: pivots of the second candidate (zero where the context keeps none).  Leaves every instance idle. */
+int sqphip_mf_batch_test(sqphip_ctx *ctx, const int32_t *active, const double *Jval, const double *Hval, const double *Dd,
+                         const double *sigp, const double *hd, const int32_t *rtype, const double *hsc, const double *dw,
+                         const double *dw_last, const int32_t *fac_attempt, const double *rhs, double *sol_fused,
+                         double *sol_standalone, double *dinv0, double *dinv1, int32_t *decision, double *dw_out);
+/* Launch census of the multifrontal path: launches enqueued per kernel instantiation (factor, solve, inertia test) since the
+ * context was created.  counts[cap]; names (may be null): cap x 64 characters; *n_kernels = number of instantiations. */
+int sqphip_mf_census(const sqphip_ctx *ctx, int64_t *counts, char *names, int32_t cap, int32_t *n_kernels);
+/* Host-only (no GPU): the shape of the multifrontal plan sqphip_create builds for the structure, condense option and batch
+ * (and the SQPHIP_MF_SMALL_FRONT / _ZERO_FRAC / _ROWS_AFTER overrides it reads): fronts[cap_fronts][3] = (columns, rows,
+ * level), launches[cap_launches][4] = factor launches (level, tiles of the kernel, fronts, tiles of the smallest front);
+ * *top2_lds_bytes: LDS of the streamed top-of-tree solve (0: none); *spine_fronts: fronts of the spine kernel (0: none). */
+int sqphip_mf_plan_info(int64_t n, int64_t m, int64_t nnzJ, const int64_t *jrow, const int64_t *jcol, int64_t nnzH,
+                        const int64_t *hrow, const int64_t *hcol, const double *gL, const double *gU, int32_t condense,
+                        int32_t batch, int32_t *fronts, int32_t cap_fronts, int32_t *n_fronts, int32_t *launches,
+                        int32_t cap_launches, int32_t *n_launches, int64_t *top2_lds_bytes, int32_t *spine_fronts);
 /* ---- kernel-level entry points (parity tests, micro-benchmarks) -------------------------------
  * Batched dense LDL^T without pivoting of `batch` symmetric N x N matrices given as full
  * column-major host arrays A[batch][N*N] (lower triangle read).  On return L (unit lower) is in the

@@ -118,6 +118,8 @@ DV group_view(const DV &d, int i0, int Bg, int g)
 // (re)build the lanes from the owner's current device view (after sqphip_create and after sqphip_acopf_attach)
 void make_lanes(Ctx &C)
 {
+    for (const auto &L : C.lanes)           // (the launch census of the groups being replaced stays with the context)
+        for (int k = 0; k < MFK_COUNT; ++k) C.mf_census[k] += L->mf_census[k];
     C.lanes.clear();
     int G = 1;
     // (round 3, with the shorter solve kernels: four groups from 64 instances on -- 64 resident scenarios 1 955 -> 2 015 QP/s;
@@ -182,6 +184,19 @@ __global__ void k_mf_test_setup(DV d, int inst, double hsc, double dw, int ph)
     for (int i = threadIdx.x; i < d.B; i += blockDim.x) { d.phase[i] = PH_IDLE; d.ist[i].start = 0; }
     __syncthreads();
     if (threadIdx.x == 0) { d.ist[inst].hsc = hsc; d.ist[inst].dw = dw; d.ist[inst].stage = 0; d.ist[inst].sel = 0; d.ist[inst].fac_attempt = 0; d.phase[inst] = ph; }
+}
+
+// test hook (sqphip_mf_batch_test): instance `inst` on its own -- a start request (start = 1: k_qp_gather converts its COO
+// values) or the interior-point state a sweep factorises with: phase `ph`, Hessian scale, delta_w, the last accepted delta_w
+// and the failed factorisations so far
+__global__ void k_mf_inst_set(DV d, int inst, int start, int ph, double hsc, double dw, double dw_last, int fac_attempt)
+{
+    if (threadIdx.x != 0) return;
+    IpmState &I = d.ist[inst];
+    I.start = start;
+    if (start) { I.mode = 0; I.delta = 1.0; I.mu_pen = 1.0; I.rho_big = 1e4; I.ipm_iters = 0; I.n_solve = 0; I.status = 0; }
+    I.stage = 0; I.hsc = hsc; I.dw = dw; I.dw_last = dw_last; I.sel = 0; I.fac_attempt = fac_attempt; I.n_factor = 0; I.rc = 0;
+    d.phase[inst] = ph;
 }
 
 }  // namespace
@@ -265,11 +280,7 @@ extern "C" int sqphip_create(sqphip_ctx **out, int64_t n, int64_t m, int64_t num
                 // multifrontal plan of the sparse matrix (full form: every row is its own unknown)
                 std::vector<int> kp(kpos);
                 if (!d.condense) for (int64_t i = 0; i < m; ++i) kp[i] = (int)i;
-                SymOptions so;
-                if (const char *e = getenv("SQPHIP_MF_SMALL_FRONT")) so.small_front = atoi(e);
-                if (const char *e = getenv("SQPHIP_MF_ZERO_FRAC")) so.zero_frac = atof(e);
-                if (const char *e = getenv("SQPHIP_MF_ROWS_AFTER")) so.rows_after_vars = atoi(e);
-                so.merge_tiles = B <= 64 ? 4 : 0;        // (small batches: one launch per level of small fronts, mfplan.hip)
+                const SymOptions so = mf_sym_options(B);   // (small batches: one launch per level of small fronts, mfplan.hip)
                 C.mfp_ = std::make_shared<MfPlan>(mf_build_plan(d.n, (int)m, kp, d.condense ? d.mk : (int)m, PH.colptr, PH.rowval, rptr, rcol, rslot, so));
                 const SparseSym &S = C.mfp().S;
                 // auto: the sparse factorisation when it does a quarter of the dense work or less and no front
@@ -338,10 +349,7 @@ extern "C" int sqphip_create(sqphip_ctx **out, int64_t n, int64_t m, int64_t num
                 // scenarios (1.4 % fewer sweeps, identical work counters), 6 614 / 6 682 / 6 708 / 6 692 / 6 552 / 6 561 at 256
                 C.spec_tail = d.spec_mode == 0 && small_arena ? (getenv("SQPHIP_MF_SPEC_TAIL") ? atoi(getenv("SQPHIP_MF_SPEC_TAIL")) : (getenv("SQPHIP_MF_SPEC") ? 0 : 32)) : 0;
                 C.spec_mode0 = d.spec_mode;
-                if (d.spec_mode != 0 || C.spec_tail > 0) {
-                    M.vals1 = C.dalloc<double>((size_t)B * P.nnzK);
-                    M.fronts1 = C.dalloc<double>((size_t)B * P.stride);
-                }
+                // (the arenas of the second candidate are allocated below, once the way the values are assembled is known)
             } else if (d.condense && opt->kkt_tile_order) {
                 KktOrder o = kkt_order(d.n, (int)m, kpos, d.mk, PH.colptr, PH.rowval, rptr, rcol, /*rows_last=*/true);
                 upos = o.pos; d.Ts = o.Ts; d.Nf = o.Nf;
@@ -392,7 +400,6 @@ extern "C" int sqphip_create(sqphip_ctx **out, int64_t n, int64_t m, int64_t num
         d.rhs = C.dalloc<double>(BN); d.sol = C.dalloc<double>(BN); d.wN = C.dalloc<double>(BN);
         const size_t BF = (size_t)B * d.Fpad;          // solve vectors and pivots live in the factorised order
         d.xv = C.dalloc<double>(BF); d.vv = C.dalloc<double>(BF); d.dinv = C.dalloc<double>(BF);
-        if (d.sparse && d.mf.fronts1) { d.vv1 = C.dalloc<double>(BF); d.dinv1 = C.dalloc<double>(BF); }
         d.K = C.dalloc<double>(d.sparse ? 1 : (size_t)B * d.ld * d.Fpad);
         d.ist = C.dalloc<IpmState>(B); d.sst = C.dalloc<SqpState>(B);
         d.phase = C.dalloc<int>(B); d.counters = C.dalloc<int>(64);
@@ -407,6 +414,14 @@ extern "C" int sqphip_create(sqphip_ctx **out, int64_t n, int64_t m, int64_t num
         //  chain item list -> items -> operands -- takes longer than the flat k_mf_values launch it saves: 7 528 against 7 706
         //  QP/s at 512 x IEEE-118, 1 880 against 2 002 at 64, +2 % on IEEE-14; on request only)
         d.vals_inline = d.sparse && !d.flat && getenv("SQPHIP_MF_VALS_INLINE") && atoi(getenv("SQPHIP_MF_VALS_INLINE")) == 1;
+        // the stage kernel assembles the values of sweep k + 1 during sweep k, under that sweep's spec_mode: a second candidate
+        // switched on between the two (spec_tail) would be factorised from values1 never written for it
+        if (d.vals_inline) C.spec_tail = 0;
+        if (d.sparse && (d.spec_mode != 0 || C.spec_tail > 0)) {
+            d.mf.vals1 = C.dalloc<double>((size_t)B * C.mfp().nnzK);
+            d.mf.fronts1 = C.dalloc<double>((size_t)B * C.mfp().stride);
+            d.vv1 = C.dalloc<double>(BF); d.dinv1 = C.dalloc<double>(BF);
+        }
         if (d.flat) {
             d.vstage = 0;
             d.fH = C.dalloc<double>(Bn); d.fJt = C.dalloc<double>(Bn); d.fJ = C.dalloc<double>(Bm); d.fX = C.dalloc<double>(Bm);
@@ -552,6 +567,103 @@ extern "C" int sqphip_mf_solve_test(sqphip_ctx *h, int32_t inst, const double *J
         if (sol_standalone) for (int u = 0; u < S.nu; ++u) sol_standalone[u] = out[S.pos[u]];
         return SQPHIP_OK;
     });
+}
+
+// Batched twin of sqphip_mf_solve_test: every instance with active[b] != 0 gets its own values and interior-point state
+// and goes through what one sweep does to it (ipm.hip, ipm_sweep): factorisation of both candidate shifts with the
+// right-hand side fused in, the inertia test by the path the sweep takes (in k_mf_solve_top2, or k_inertia), the backward
+// solve of the instances that passed; then the stand-alone forward / backward solve of the same right-hand side.  Arrays
+// per instance, back to back: Jval [B][nnzJ], Hval [B][nnzH], Dd / rtype [B][m], sigp / hd [B][n], rhs / outputs [B][nu]
+// (unknown order); hsc, dw, dw_last, fac_attempt [B].  decision [B][5]: outcome (0 idle, 1 another shift needed, 2 passed,
+// 3 given up), sel, n_factor, fac_attempt, and 1 if the instance speculates -- derived here from the inputs by the rule of
+// mf_speculates, not reported by the device; dw_out [B]: delta_w after the decision.  dinv1
+// (may be null): the pivots of candidate 1, zero where the context keeps no second candidate.  Leaves every instance idle.
+extern "C" int sqphip_mf_batch_test(sqphip_ctx *h, const int32_t *active, const double *Jval, const double *Hval,
+                                    const double *Dd, const double *sigp, const double *hd, const int32_t *rtype,
+                                    const double *hsc, const double *dw, const double *dw_last, const int32_t *fac_attempt,
+                                    const double *rhs, double *sol_fused, double *sol_standalone, double *dinv0,
+                                    double *dinv1, int32_t *decision, double *dw_out)
+{
+    if (!h || !active || !Jval || !Dd || !sigp || !hd || !rtype || !hsc || !dw || !dw_last || !fac_attempt || !rhs)
+        return SQPHIP_EINVAL;
+    if (!h->c.d.sparse) { h->c.err = "sqphip_mf_batch_test: the context does not use the sparse solver"; return SQPHIP_ESTATE; }
+    return guarded(h, [&](Ctx &C) {
+        DV &d = C.d;
+        const SparseSym &S = C.mfp().S;
+        const int B = d.B, nu = S.nu;
+        std::vector<double> xp((size_t)B * d.Fpad, 0.0), out((size_t)B * d.Fpad), dv((size_t)B * d.Fpad), dv1((size_t)B * d.Fpad, 0.0);
+        for (int b = 0; b < B; ++b) {
+            const size_t on = (size_t)b * d.n, om = (size_t)b * d.m;
+            h2d(C, d.jcoo + (size_t)b * d.nnzj_coo, Jval + (size_t)b * d.nnzj_coo, d.nnzj_coo);
+            if (Hval) h2d(C, d.hcoo + (size_t)b * d.nnzh_coo, Hval + (size_t)b * d.nnzh_coo, d.nnzh_coo);
+            else SQPHIP_HIP_OK(hipMemsetAsync(d.hcoo + (size_t)b * d.nnzh_coo, 0, sizeof(double) * (size_t)d.nnzh_coo, C.stream));
+            h2d(C, d.Dd + om, Dd + om, d.m); h2d(C, d.sigp + on, sigp + on, d.n); h2d(C, d.hd + on, hd + on, d.n);
+            SQPHIP_HIP_OK(hipMemcpyAsync(d.rtype + om, rtype + om, sizeof(int) * (size_t)d.m, hipMemcpyHostToDevice, C.stream));
+            for (int u = 0; u < nu; ++u) xp[(size_t)b * d.Fpad + S.pos[u]] = rhs[(size_t)b * nu + u];
+            hipLaunchKernelGGL(k_mf_inst_set, dim3(1), dim3(64), 0, C.stream, d, b, active[b] ? 1 : 0, (int)PH_IDLE, 0.0, 0.0, 0.0, 0);
+        }
+        h2d(C, d.xv, xp.data(), xp.size());
+        launch_qp_gather(C);                       // COO -> CSC values of the active instances (start flag set, stage 0)
+        for (int b = 0; b < B; ++b)
+            hipLaunchKernelGGL(k_mf_inst_set, dim3(1), dim3(64), 0, C.stream, d, b, 0, active[b] ? (int)PH_FACTOR : (int)PH_IDLE,
+                               hsc[b], dw[b], dw_last[b], (int)fac_attempt[b]);
+        // what the sweep does (ipm_sweep): factorise, test the inertia, solve the instances that passed
+        const bool top_inertia = mf_solve_tests_inertia(C);
+        mf_factor(C, PH_FACTOR, true);
+        if (!top_inertia) launch_inertia(C);
+        mf_solve(C, PH_SOLVE, true, top_inertia);
+        d2h(C, out.data(), d.xv, out.size()); d2h(C, dv.data(), d.dinv, dv.size());
+        if (d.dinv1) d2h(C, dv1.data(), d.dinv1, dv1.size());
+        std::vector<IpmState> st(B);
+        std::vector<int> ph(B);
+        SQPHIP_HIP_OK(hipMemcpyAsync(st.data(), d.ist, sizeof(IpmState) * (size_t)B, hipMemcpyDeviceToHost, C.stream));
+        SQPHIP_HIP_OK(hipMemcpyAsync(ph.data(), d.phase, sizeof(int) * (size_t)B, hipMemcpyDeviceToHost, C.stream));
+        SQPHIP_HIP_OK(hipStreamSynchronize(C.stream));
+        for (int b = 0; b < B; ++b) {
+            const size_t f = (size_t)b * d.Fpad, o = (size_t)b * nu;
+            for (int u = 0; u < nu; ++u) {
+                if (sol_fused) sol_fused[o + u] = out[f + S.pos[u]];
+                if (dinv0) dinv0[o + u] = dv[f + S.pos[u]];
+                if (dinv1) dinv1[o + u] = dv1[f + S.pos[u]];
+            }
+            const IpmState &I = st[b];
+            const bool spec = d.mf.fronts1 != nullptr && d.spec_mode != 0 && (fac_attempt[b] > 0 || (d.spec_mode == 1 && dw[b] > 0.0));
+            if (decision) {
+                int32_t *r = decision + 5 * (size_t)b;
+                r[0] = !active[b] ? 0 : ph[b] == PH_FACTOR ? 1 : ph[b] == PH_SOLVE ? 2 : 3;
+                r[1] = I.sel; r[2] = I.n_factor; r[3] = I.fac_attempt; r[4] = active[b] && spec ? 1 : 0;
+            }
+            if (dw_out) dw_out[b] = I.dw;
+        }
+        // the stand-alone forward and backward solves on the factors the decision selected
+        h2d(C, d.xv, xp.data(), xp.size());
+        mf_solve(C, PH_SOLVE, false);
+        d2h(C, out.data(), d.xv, out.size());
+        for (int b = 0; b < B; ++b)
+            hipLaunchKernelGGL(k_mf_inst_set, dim3(1), dim3(64), 0, C.stream, d, b, 0, (int)PH_IDLE, 0.0, 0.0, 0.0, 0);
+        SQPHIP_HIP_OK(hipStreamSynchronize(C.stream));
+        SQPHIP_HIP_OK(hipGetLastError());
+        if (sol_standalone)
+            for (int b = 0; b < B; ++b)
+                for (int u = 0; u < nu; ++u) sol_standalone[(size_t)b * nu + u] = out[(size_t)b * d.Fpad + S.pos[u]];
+        return SQPHIP_OK;
+    });
+}
+
+// Launch census of the multifrontal path: launches enqueued per kernel instantiation since the context was created, summed
+// over its instance groups.  counts[cap]; names (may be null): cap x 64 characters, NUL-terminated; *n_kernels = how many
+// there are (fewer than cap: the first cap).
+extern "C" int sqphip_mf_census(const sqphip_ctx *h, int64_t *counts, char *names, int32_t cap, int32_t *n_kernels)
+{
+    if (!h || cap < 0 || (cap > 0 && !counts)) return SQPHIP_EINVAL;
+    if (n_kernels) *n_kernels = MFK_COUNT;
+    for (int k = 0; k < MFK_COUNT && k < cap; ++k) {
+        long c = h->c.mf_census[k];
+        for (const auto &L : h->c.lanes) c += L->mf_census[k];
+        counts[k] = c;
+        if (names) { std::strncpy(names + 64 * (size_t)k, mf_kernel_names[k], 63); names[64 * (size_t)k + 63] = 0; }
+    }
+    return SQPHIP_OK;
 }
 
 extern "C" int sqphip_qp_stats(const sqphip_ctx *h, int32_t *ipm_iters, int32_t *n_factor)

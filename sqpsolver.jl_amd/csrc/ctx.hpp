@@ -24,6 +24,17 @@ enum { PH_IDLE = 0, PH_PREP = 1, PH_FACTOR = 2, PH_SOLVE = 3, PH_STEP = 4, PH_MP
        PH_PEND = 10, PH_DONE2 = 11, PH_PREP_S = 12 };
 enum { ROW_FREE = 0, ROW_EQ = 1, ROW_INEQ = 2 };
 
+// Launch census of the multifrontal path: one host counter per kernel instantiation that mf_factor, mf_solve and the
+// inertia test can enqueue (Ctx::mf_census, incremented at enqueue; read by the test hook sqphip_mf_census, which names them
+// through mf_kernel_names, mfront.hip).  k_mf_front<T, NW, LDSIMG>: FRONT_<T>[_<NW>][_IMG] (T <= 3: one wave, image in LDS).
+enum MfKernel { MFK_VALUES, MFK_FACTOR_R1, MFK_F2_1_3, MFK_F2_2_5, MFK_F2_4_4, MFK_F2_4_9, MFK_F2_8_12,
+                MFK_FRONT_1, MFK_FRONT_2, MFK_FRONT_3, MFK_FRONT_4_2, MFK_FRONT_4_4, MFK_FRONT_5_2, MFK_FRONT_5_4,
+                MFK_FRONT_6_4, MFK_FRONT_6_4_IMG, MFK_FRONT_6_8_IMG, MFK_FRONT_7_4, MFK_FRONT_7_4_IMG, MFK_FRONT_7_8_IMG,
+                MFK_FRONT_8_4, MFK_FRONT_8_4_IMG, MFK_FRONT_8_8_IMG, MFK_FRONT_9, MFK_FRONT_10, MFK_FRONT_11, MFK_FRONT_12,
+                MFK_SPINE, MFK_SOLVE_INST, MFK_FWD, MFK_FWD2, MFK_FWD2_BIG, MFK_SOLVE_TOP, MFK_SOLVE_TOP2, MFK_BWD, MFK_BWD2,
+                MFK_BWD2_BIG, MFK_INERTIA, MFK_COUNT };
+extern const char *const mf_kernel_names[];        // [MFK_COUNT] (checked where it is defined)
+
 struct IpmState {
     // request
     int mode, start, stage;        // stage 0 = programme itself, 1 = phase-1 feasibility check
@@ -207,6 +218,7 @@ struct Ctx {
     std::vector<std::unique_ptr<Ctx>> lanes;
     bool is_lane = false, owns_stream = true;
     long mf_factor_launches = 0, n_sweeps = 0;
+    long mf_census[MFK_COUNT] = {};   // launches enqueued per multifrontal kernel (MfKernel) by this context or lane
     // Transitions between sub-problems run every trans_period-th sweep of a RUN (ipm_sweep): run_sweep counts the sweeps
     // of the current sqphip_sqp_run / _stream_run call, so the first sweep of every run is a transition sweep -- slots
     // armed by the scenario queue draw their scenario there, whatever the lifetime counter n_sweeps says.
@@ -277,6 +289,7 @@ void mf_device_setup(Ctx &C);
 void mf_factor(Ctx &C, int want, bool with_rhs, bool values_done = false);
 void mf_solve(Ctx &C, int want, bool skip_fwd, bool inertia = false);   // inertia: the streamed top kernel tests the inertia of PH_FACTOR instances first
 bool mf_solve_tests_inertia(const Ctx &C);     // ... which it can when the plan has a streamed top (k_mf_solve_top2)
+void launch_inertia(Ctx &C);                   // ipm.hip: k_inertia over the batch (pivot signs -> PH_SOLVE, or the next shift)
 // acopf.hip
 void launch_acopf_eval_point(Ctx &C, int inst, const double *x_dev, double sigma, const double *lam_dev,
                              double *f_dev, double *grad_dev, double *g_dev, double *jcoo_dev,

@@ -1180,6 +1180,12 @@ __global__ __launch_bounds__(TPB, SQPHIP_VEC_WAVES_PER_EU) void k_ipm_tail_b(DV 
 }
 __global__ __launch_bounds__(TPB, SQPHIP_VEC_WAVES_PER_EU) void k_ipm_prepare(DV d) { b_ipm_prepare(d); }
 
+void launch_inertia(Ctx &C)
+{
+    C.mf_census[MFK_INERTIA]++;
+    hipLaunchKernelGGL(k_inertia, dim3(C.d.B), dim3(TPB), 0, C.stream, C.d);
+}
+
 void launch_qp_gather(Ctx &C)
 {
     hipLaunchKernelGGL(k_qp_gather, dim3(C.d.B), dim3(TPB), 0, C.stream, C.d);
@@ -1273,7 +1279,7 @@ void ipm_sweep(Ctx &C, bool sqp_level)
         if (d.sparse) mf_solve(C, want, skip_fwd, top_inertia && want == PH_SOLVE);
         else ldlt_solve(C.plan, d.K, d.dinv, d.xv, d.vv, d.phase, want, skip_fwd);
     };
-    if (!top_inertia) hipLaunchKernelGGL(k_inertia, gB, bT, 0, s, d);
+    if (!top_inertia) launch_inertia(C);
     if (C.tm.enabled) { ev = C.tm.get(); hipEventRecord(ev.first, s); }
     // backward half of the solve (the forward half happened inside the factorisation), then the residual against
     // the sparse operator.  No iterative refinement: one step of it (the policy until late in round 1, two more

@@ -578,16 +578,15 @@ void mf_host_factor_solve(const MfPlan &P, const MfValues &V, const double *rhs,
 extern "C" double sqphip_mf_host_top2_err(void) { return sqphip::g_top2_err; }
 extern "C" double sqphip_mf_host_spine_err(void) { return sqphip::g_spine_err; }
 
-// C-ABI test hook (host only, no GPU): plan + host reference of the numeric phase for the NLP structure given as in
-// sqphip_create; values in the library's internal layouts (see include/sqphip.h).
-extern "C" int sqphip_mf_host_solve(int64_t n, int64_t m, int64_t nnzJ, const int64_t *jrow, const int64_t *jcol,
-                                    int64_t nnzH, const int64_t *hrow, const int64_t *hcol, const double *gL,
-                                    const double *gU, int32_t condense, const double *Jval, const double *Hval,
-                                    const double *Dd, const double *sigp, const double *hd, const int32_t *rtype,
-                                    double hsc, double dw, const double *rhs, double *sol, double *dinv_by_unknown,
-                                    int32_t *npos)
+namespace {
+
+// the plan sqphip_create builds for an NLP structure (given as there), and -- Jval / Hval not null -- the values in the CSC
+// layouts the plan's items index
+sqphip::MfPlan host_plan(int64_t n, int64_t m, int64_t nnzJ, const int64_t *jrow, const int64_t *jcol, int64_t nnzH,
+                         const int64_t *hrow, const int64_t *hcol, const double *gL, const double *gU, int32_t condense,
+                         const sqphip::SymOptions &so, const double *Jval, const double *Hval, std::vector<double> &jv,
+                         std::vector<double> &hv)
 {
-    if (n <= 0 || m < 0 || !rhs || !sol) return SQPHIP_EINVAL;
     using namespace sqphip;
     // CSC of J with duplicate summation and the full symmetric CSC of H, as sqphip_create builds them
     struct Ent { int c, r; double v; };
@@ -595,8 +594,8 @@ extern "C" int sqphip_mf_host_solve(int64_t n, int64_t m, int64_t nnzJ, const in
                     std::vector<int> &colptr, std::vector<int> &rowval, std::vector<double> &vals) {
         std::vector<Ent> e;
         for (int64_t k = 0; k < nnz; ++k) {
-            e.push_back({(int)col[k] - 1, (int)row[k] - 1, val[k]});
-            if (sym && row[k] != col[k]) e.push_back({(int)row[k] - 1, (int)col[k] - 1, val[k]});
+            e.push_back({(int)col[k] - 1, (int)row[k] - 1, val ? val[k] : 0.0});
+            if (sym && row[k] != col[k]) e.push_back({(int)row[k] - 1, (int)col[k] - 1, val ? val[k] : 0.0});
         }
         std::stable_sort(e.begin(), e.end(), [](const Ent &a, const Ent &b) { return std::tie(a.c, a.r) < std::tie(b.c, b.r); });
         colptr.assign(ncols + 1, 0);
@@ -607,7 +606,6 @@ extern "C" int sqphip_mf_host_solve(int64_t n, int64_t m, int64_t nnzJ, const in
         for (int64_t j = 0; j < ncols; ++j) colptr[j + 1] += colptr[j];
     };
     std::vector<int> jcp, jrv, hcp, hrv;
-    std::vector<double> jv, hv;
     build(n, nnzJ, jrow, jcol, Jval, false, jcp, jrv, jv);
     build(n, nnzH, hrow, hcol, Hval, true, hcp, hrv, hv);
     std::vector<int> rptr(m + 1, 0), rcol(jrv.size()), rslot(jrv.size());
@@ -622,7 +620,24 @@ extern "C" int sqphip_mf_host_solve(int64_t n, int64_t m, int64_t nnzJ, const in
     int mk = 0;
     for (int64_t i = 0; i < m; ++i)
         if (!condense || kkt_row_is_kept(gL[i], gU[i], rptr[i + 1] - rptr[i])) kpos[i] = mk++;
-    MfPlan P = mf_build_plan((int)n, (int)m, kpos, mk, hcp, hrv, rptr, rcol, rslot, SymOptions());
+    return mf_build_plan((int)n, (int)m, kpos, mk, hcp, hrv, rptr, rcol, rslot, so);
+}
+
+}  // namespace
+
+// C-ABI test hook (host only, no GPU): plan + host reference of the numeric phase for the NLP structure given as in
+// sqphip_create; values in the library's internal layouts (see include/sqphip.h).
+extern "C" int sqphip_mf_host_solve(int64_t n, int64_t m, int64_t nnzJ, const int64_t *jrow, const int64_t *jcol,
+                                    int64_t nnzH, const int64_t *hrow, const int64_t *hcol, const double *gL,
+                                    const double *gU, int32_t condense, const double *Jval, const double *Hval,
+                                    const double *Dd, const double *sigp, const double *hd, const int32_t *rtype,
+                                    double hsc, double dw, const double *rhs, double *sol, double *dinv_by_unknown,
+                                    int32_t *npos)
+{
+    if (n <= 0 || m < 0 || !rhs || !sol) return SQPHIP_EINVAL;
+    using namespace sqphip;
+    std::vector<double> jv, hv;
+    MfPlan P = host_plan(n, m, nnzJ, jrow, jcol, nnzH, hrow, hcol, gL, gU, condense, SymOptions(), Jval, Hval, jv, hv);
     std::vector<int> rt(m > 0 ? m : 1, 1);
     for (int64_t i = 0; i < m; ++i) rt[i] = rtype ? rtype[i] : 1;
     MfValues V{hv.data(), jv.data(), Dd, sigp, hd, rt.data(), hsc, dw};
@@ -635,5 +650,41 @@ extern "C" int sqphip_mf_host_solve(int64_t n, int64_t m, int64_t nnzJ, const in
         if (d > 0.0 && std::isfinite(d)) ++np;
     }
     if (npos) *npos = np;
+    return SQPHIP_OK;
+}
+
+// C-ABI test hook (host only, no GPU): the shape of the plan sqphip_create builds for the structure with the given condense
+// option and batch (the batch sets SymOptions::merge_tiles; the SQPHIP_MF_* overrides apply as there): per front (columns,
+// rows, level), per factor launch (level, tiles of its kernel, fronts, tiles of its smallest front); caps 0 ask for the
+// counts only.  *top2_lds_bytes: LDS the streamed top-of-tree solve needs
+// (0: the plan has none), *spine_fronts: fronts of the spine kernel (0: none).
+extern "C" int sqphip_mf_plan_info(int64_t n, int64_t m, int64_t nnzJ, const int64_t *jrow, const int64_t *jcol, int64_t nnzH,
+                                   const int64_t *hrow, const int64_t *hcol, const double *gL, const double *gU,
+                                   int32_t condense, int32_t batch, int32_t *fronts, int32_t cap_fronts, int32_t *n_fronts,
+                                   int32_t *launches, int32_t cap_launches, int32_t *n_launches, int64_t *top2_lds_bytes,
+                                   int32_t *spine_fronts)
+{
+    if (n <= 0 || m < 0 || batch <= 0 || cap_fronts < 0 || cap_launches < 0 || (cap_fronts > 0 && !fronts) ||
+        (cap_launches > 0 && !launches))
+        return SQPHIP_EINVAL;
+    using namespace sqphip;
+    const SymOptions so = mf_sym_options(batch);
+    std::vector<double> jv, hv;
+    const MfPlan P = host_plan(n, m, nnzJ, jrow, jcol, nnzH, hrow, hcol, gL, gU, condense, so, nullptr, nullptr, jv, hv);
+    const SparseSym &S = P.S;
+    std::vector<int> level(S.ns, 0);
+    for (int l = 0; l < S.nlevels; ++l)
+        for (int q = S.level_ptr[l]; q < S.level_ptr[l + 1]; ++q) level[S.level_sn[q]] = l;
+    for (int f = 0; f < S.ns && f < cap_fronts; ++f) { fronts[3 * f] = S.sn_nc[f]; fronts[3 * f + 1] = S.sn_nr[f]; fronts[3 * f + 2] = level[f]; }
+    for (int k = 0; k < (int)P.fac.size() && k < cap_launches; ++k) {
+        const MfLaunch &L = P.fac[k];
+        int tmin = 1 << 30;
+        for (int q = L.begin; q < L.begin + L.count; ++q) tmin = std::min(tmin, (S.sn_nc[P.sched[q]] + S.sn_nr[P.sched[q]] + 1 + 15) / 16);
+        launches[4 * k] = L.level; launches[4 * k + 1] = L.tiles; launches[4 * k + 2] = L.count; launches[4 * k + 3] = tmin;
+    }
+    if (n_fronts) *n_fronts = S.ns;
+    if (n_launches) *n_launches = (int32_t)P.fac.size();
+    if (top2_lds_bytes) *top2_lds_bytes = P.top2_lds_bytes;
+    if (spine_fronts) *spine_fronts = (int32_t)P.sp_fr.size();
     return SQPHIP_OK;
 }

@@ -75,10 +75,11 @@ __global__ __launch_bounds__(NT) void k_mf_factor(DV d, int sbegin, int want, in
     for (int e = tid; e < ld * fs; e += NT) F[e] = 0.0;
     __syncthreads();
     MF_TR(1)
-    // 2. structural entries of the Newton matrix that live in this front, right-hand side row
+    // 2. structural entries of the Newton matrix that live in this front, right-hand side row (candidate 1: the next shift of
+    //    the schedule, as k_mf_values assembles it)
     {
         const IpmState &st = d.ist[inst];
-        const double hsc = st.hsc, dw = st.dw;
+        const double hsc = st.hsc, dw = cand ? next_shift(st.dw, st.dw_last) : st.dw;
         const double *hv = d.hv + (long)inst * d.nnzhc, *jv = d.jv + (long)inst * d.nnzjc;
         const double *Dd = d.Dd + (long)inst * d.m, *sigp = d.sigp + (long)inst * d.n, *hd = d.hd + (long)inst * d.n;
         const int *rt = d.rtype + (long)inst * d.m;
@@ -1947,6 +1948,33 @@ __global__ __launch_bounds__(256, HASBIG ? 4 : 5) void k_mf_bwd2(DV d, int ibegi
 }
 
 // ---------------------------------------------------------------------------------------------------------------
+// launch census (ctx.hpp MfKernel): the names, and the counter of a front kernel instantiation
+const char *const mf_kernel_names[] = {
+    "k_mf_values", "k_mf_factor<256, true>", "k_mf_factor2<1, 3, true>", "k_mf_factor2<2, 5, true>", "k_mf_factor2<4, 4, true>",
+    "k_mf_factor2<4, 9, false>", "k_mf_factor2<8, 12, false>",
+    "k_mf_front<1, 1, true>", "k_mf_front<2, 1, true>", "k_mf_front<3, 1, true>", "k_mf_front<4, 2, true>", "k_mf_front<4, 4, true>",
+    "k_mf_front<5, 2, true>", "k_mf_front<5, 4, true>",
+    "k_mf_front<6, 4, false>", "k_mf_front<6, 4, true>", "k_mf_front<6, 8, true>",
+    "k_mf_front<7, 4, false>", "k_mf_front<7, 4, true>", "k_mf_front<7, 8, true>",
+    "k_mf_front<8, 4, false>", "k_mf_front<8, 4, true>", "k_mf_front<8, 8, true>",
+    "k_mf_front<9, 8, false>", "k_mf_front<10, 8, false>", "k_mf_front<11, 8, false>", "k_mf_front<12, 8, false>",
+    "k_mf_spine", "k_mf_solve_inst<16>", "k_mf_fwd", "k_mf_fwd2<false>", "k_mf_fwd2<true>", "k_mf_solve_top", "k_mf_solve_top2",
+    "k_mf_bwd", "k_mf_bwd2<false>", "k_mf_bwd2<true>", "k_inertia" };
+static_assert(sizeof(mf_kernel_names) / sizeof(mf_kernel_names[0]) == MFK_COUNT, "a name per MfKernel entry");
+// -1: an instantiation the census has no counter for (the launch macros of mf_factor refuse to compile it)
+static constexpr int mf_front_kid(int T, int NW, bool IMG)
+{
+    return T >= 1 && T <= 3 ? (NW == 1 && IMG ? MFK_FRONT_1 + T - 1 : -1)
+         : T <= 5 ? ((NW == 2 || NW == 4) && IMG ? MFK_FRONT_4_2 + 2 * (T - 4) + (NW == 4) : -1)
+         : T <= 8 ? (NW == 4 ? MFK_FRONT_6_4 + 3 * (T - 6) + (IMG ? 1 : 0) : NW == 8 && IMG ? MFK_FRONT_6_4 + 3 * (T - 6) + 2 : -1)
+         : T <= 12 ? (NW == 8 && !IMG ? MFK_FRONT_9 + T - 9 : -1) : -1;
+}
+static constexpr int mf_factor2_kid(int NW, int MAXT, bool IMG)
+{
+    return NW == 1 && MAXT == 3 && IMG ? MFK_F2_1_3 : NW == 2 && MAXT == 5 && IMG ? MFK_F2_2_5 : NW == 4 && MAXT == 4 && IMG ? MFK_F2_4_4
+         : NW == 4 && MAXT == 9 && !IMG ? MFK_F2_4_9 : NW == 8 && MAXT == 12 && !IMG ? MFK_F2_8_12 : -1;
+}
+
 static int mf_generic_solves()
 {
     static const int g = getenv("SQPHIP_MF_GENERIC") ? atoi(getenv("SQPHIP_MF_GENERIC")) : 0;
@@ -1981,7 +2009,7 @@ void mf_factor(Ctx &C, int want, bool with_rhs, bool values_done)
     const int wr = (int)with_rhs;
     const int nb = d.mf.fronts1 && d.spec_mode != 0 ? 2 * d.B : d.B;         // with the second candidate the factor side runs over 2 B "instances"
     // (values_done: the stage kernel that built the right-hand sides has assembled the values too: mf_values_block)
-    if (!v1 && !values_done) { C.tm.open(s); hipLaunchKernelGGL(k_mf_values, dim3((d.mf.nnzK + 255) / 256, nb), dim3(256), 0, s, d, want); C.tm.close(KC_VALUES, s); }
+    if (!v1 && !values_done) { C.tm.open(s); C.mf_census[MFK_VALUES]++; hipLaunchKernelGGL(k_mf_values, dim3((d.mf.nnzK + 255) / 256, nb), dim3(256), 0, s, d, want); C.tm.close(KC_VALUES, s); }
     // static front kernels (k_mf_front<T, NW, LDSIMG>) unless SQPHIP_MF_STATIC=0 asks for the generic ones (cross-check)
     const bool stat = !(getenv("SQPHIP_MF_STATIC") && atoi(getenv("SQPHIP_MF_STATIC")) == 0);     // (read per call: tests flip it)
     // the levels below the spine as level launches, the spine (mfplan.hip: spine_level) by one workgroup per instance
@@ -1993,10 +2021,10 @@ void mf_factor(Ctx &C, int want, bool with_rhs, bool values_done)
         if (cls != cls_open) { if (cls_open >= 0) C.tm.close(cls_open, s); C.tm.open(s); cls_open = cls; }
         const dim3 grid(L.count, nb);
         const int T = L.tiles, R = 16 * T;
-        if (v1 || T > 13) { hipLaunchKernelGGL((k_mf_factor<256, true>), grid, dim3(256), 0, s, d, L.begin, want, wr); continue; }
+        if (v1 || T > 13) { C.mf_census[MFK_FACTOR_R1]++; hipLaunchKernelGGL((k_mf_factor<256, true>), grid, dim3(256), 0, s, d, L.begin, want, wr); continue; }
         // generic kernels: dynamic LDS = [image (16 T)^2 when it lives in LDS][panel X and L: 2 x 4 x 16 T][4 x 4 block][1 / D: 16 T]
-#define MF_GENERIC(NW, MAXT, IMG) hipLaunchKernelGGL((k_mf_factor2<NW, MAXT, IMG>), grid, dim3(64 * NW), 8 * (size_t)((IMG ? R * R : 0) + 9 * R + 16), s, d, L.begin, want, wr, T)
-#define MF_STATIC(TT, NW, IMG) hipLaunchKernelGGL((k_mf_front<TT, NW, IMG>), grid, dim3(64 * NW), 8 * (size_t)mf_front_lds_doubles(TT, NW, IMG), s, d, L.begin, want, wr)
+#define MF_GENERIC(NW, MAXT, IMG) do { constexpr int kid_ = mf_factor2_kid(NW, MAXT, IMG); static_assert(kid_ >= 0, "census: no counter"); C.mf_census[kid_]++; hipLaunchKernelGGL((k_mf_factor2<NW, MAXT, IMG>), grid, dim3(64 * NW), 8 * (size_t)((IMG ? R * R : 0) + 9 * R + 16), s, d, L.begin, want, wr, T); } while (0)
+#define MF_STATIC(TT, NW, IMG) do { constexpr int kid_ = mf_front_kid(TT, NW, IMG); static_assert(kid_ >= 0, "census: no counter"); C.mf_census[kid_]++; hipLaunchKernelGGL((k_mf_front<TT, NW, IMG>), grid, dim3(64 * NW), 8 * (size_t)mf_front_lds_doubles(TT, NW, IMG), s, d, L.begin, want, wr); } while (0)
         // ... from four tile rows on: below that the generic kernels are as fast per front and lighter (registers, code
         // size) where thousands of small fronts are in flight.  Measured (QP/s, static from T = 1 / from T = 4 / never):
         // 512 x IEEE-118 5565 / 5507 / 5259, 64 x IEEE-118 1372 / - / 1315, 9241 shape 20.6 / 24.3 / 23.4, IEEE-14 50.9 k /
@@ -2044,7 +2072,7 @@ void mf_factor(Ctx &C, int want, bool with_rhs, bool values_done)
 #undef MF_STATIC
     }
     if (cls_open >= 0) C.tm.close(cls_open, s);
-    if (spine) { C.tm.open(s); hipLaunchKernelGGL(k_mf_spine, dim3(1, nb), dim3(MF_SP_NT), (size_t)C.mfp().spine_lds_bytes, s, d, want, wr); C.tm.close(KC_FRONTS_TOP, s); }
+    if (spine) { C.tm.open(s); C.mf_census[MFK_SPINE]++; hipLaunchKernelGGL(k_mf_spine, dim3(1, nb), dim3(MF_SP_NT), (size_t)C.mfp().spine_lds_bytes, s, d, want, wr); C.tm.close(KC_FRONTS_TOP, s); }
     C.mf_factor_launches += spine ? (long)C.mfp().fac_below + 1 : (long)C.mfp().fac.size();
 }
 
@@ -2066,6 +2094,7 @@ void mf_solve(Ctx &C, int want, bool skip_fwd, bool inertia)
     // 512 x IEEE-118, so it is off unless asked for.
     static const int inst_min = getenv("SQPHIP_MF_INST_SOLVE_MIN") ? atoi(getenv("SQPHIP_MF_INST_SOLVE_MIN")) : (1 << 30);
     if (d.B >= inst_min && d.mf.max_front * 8 * 16 <= 64 * 1024) {
+        C.mf_census[MFK_SOLVE_INST]++;
         hipLaunchKernelGGL(k_mf_solve_inst<16>, dim3(d.B), dim3(1024), (size_t)d.mf.max_front * 8 * 16, s, d, want, skip_fwd ? 0 : 1, generic);
         return;
     }
@@ -2075,6 +2104,7 @@ void mf_solve(Ctx &C, int want, bool skip_fwd, bool inertia)
     if (!skip_fwd && !C.mfp().fwd.empty()) C.tm.open(s);
     if (!skip_fwd)
         for (const MfLaunch &L : C.mfp().fwd) {
+            C.mf_census[lvl2 && !generic && L.wimg >= 0 ? (L.hasbig ? MFK_FWD2_BIG : MFK_FWD2) : MFK_FWD]++;
             if (lvl2 && !generic && L.wimg >= 0) {
                 if (L.hasbig) hipLaunchKernelGGL(k_mf_fwd2<true>, dim3(L.count, d.B), dim3(256), L.lds2, s, d, L.begin, want, L.wimg);
                 else hipLaunchKernelGGL(k_mf_fwd2<false>, dim3(L.count, d.B), dim3(256), L.lds2, s, d, L.begin, want, L.wimg);
@@ -2086,13 +2116,17 @@ void mf_solve(Ctx &C, int want, bool skip_fwd, bool inertia)
     if (has_top) C.tm.open(s);
     if (d.mf.top_n > 0 && !generic) {
         const size_t lds = (size_t)C.mfp().top2_lds_bytes;
+        C.mf_census[MFK_SOLVE_TOP2]++;
         hipLaunchKernelGGL(k_mf_solve_top2, dim3(d.B), dim3(256), lds, s, d, want, skip_fwd ? 0 : 1, inertia ? 1 : 0);
-    } else if (const MfLaunch &T = C.mfp().top; T.count > 0)
+    } else if (const MfLaunch &T = C.mfp().top; T.count > 0) {
+        C.mf_census[MFK_SOLVE_TOP]++;
         hipLaunchKernelGGL(k_mf_solve_top, dim3(d.B), dim3(256), T.lds_bytes, s, d, T.begin, T.count, want, skip_fwd ? 0 : 1, generic,
                            T.tiles, T.cls, T.lds_bytes / 8 - T.cls);
+    }
     if (has_top) C.tm.close(KC_SOLVE_TOP, s);
     if (!C.mfp().bwd.empty()) C.tm.open(s);
     for (const MfLaunch &L : C.mfp().bwd) {
+        C.mf_census[lvl2 && !generic && L.wimg >= 0 ? (L.hasbig ? MFK_BWD2_BIG : MFK_BWD2) : MFK_BWD]++;
         if (lvl2 && !generic && L.wimg >= 0) {
             if (L.hasbig) hipLaunchKernelGGL(k_mf_bwd2<true>, dim3(L.count, d.B), dim3(256), L.lds2, s, d, L.begin, want, L.wimg);
             else hipLaunchKernelGGL(k_mf_bwd2<false>, dim3(L.count, d.B), dim3(256), L.lds2, s, d, L.begin, want, L.wimg);

@@ -5,6 +5,7 @@
 // /root/reference/examples/acopf/opf.jl:59-64), done once per sparsity structure.
 #pragma once
 #include <cstdint>
+#include <cstdlib>
 #include <vector>
 
 namespace sqphip {
@@ -52,6 +53,17 @@ struct SymOptions {
     int chain_front = 0;       // > 0: along the spine of the tree the deepest child is merged into its parent while the
                                // merged front stays within this many rows (symbolic.hip, second amalgamation pass)
 };
+// the options sqphip_create builds the plan of a batch of B instances with: small batches run one launch per level of small
+// fronts (merge_tiles); SQPHIP_MF_SMALL_FRONT / _ZERO_FRAC / _ROWS_AFTER override the amalgamation and ordering (experiments)
+inline SymOptions mf_sym_options(int B)
+{
+    SymOptions so;
+    if (const char *e = getenv("SQPHIP_MF_SMALL_FRONT")) so.small_front = atoi(e);
+    if (const char *e = getenv("SQPHIP_MF_ZERO_FRAC")) so.zero_frac = atof(e);
+    if (const char *e = getenv("SQPHIP_MF_ROWS_AFTER")) so.rows_after_vars = atoi(e);
+    so.merge_tiles = B <= 64 ? 4 : 0;
+    return so;
+}
 
 // adj: symmetric adjacency lists over nu unknowns (sorted, unique, no self loops);
 // need[u] (may be empty): for rows_after_vars, the unknowns that must precede u (the variables of row u)

@@ -120,6 +120,23 @@ def mf_host_spine_err() -> float:
     return float(_lib.lib().sqphip_mf_host_spine_err())
 
 
+def mf_plan_info(n, m, jrow, jcol, hrow, hcol, gL, gU, condense=1, batch=1):
+    """Shape of the multifrontal plan `sqphip_create` builds (`sqphip_mf_plan_info`, host only): fronts (columns, rows, level)
+    as an (ns, 3) array, factor launches (level, tiles of the kernel, fronts, tiles of the smallest front) as an (nl, 4)
+    array, LDS bytes of the streamed top-of-tree
+    solve (0: none), fronts of the spine kernel (0: none)."""
+    L = _lib.lib()
+    jr, jc, hr, hc = (np.ascontiguousarray(a, dtype=np.int64) for a in (jrow, jcol, hrow, hcol))
+    nf, nl, top, sp = C.c_int32(), C.c_int32(), C.c_int64(), C.c_int32()
+    args = (n, m, len(jr), _l(jr), _l(jc), len(hr), _l(hr), _l(hc), _d(_f(gL)), _d(_f(gU)), int(condense), int(batch))
+    if L.sqphip_mf_plan_info(*args, None, 0, C.byref(nf), None, 0, C.byref(nl), C.byref(top), C.byref(sp)) != 0:
+        raise SqpHipError("sqphip_mf_plan_info failed")
+    fr = np.zeros((nf.value, 3), dtype=np.int32); la = np.zeros((nl.value, 4), dtype=np.int32)
+    if L.sqphip_mf_plan_info(*args, _i(fr), nf.value, C.byref(nf), _i(la), nl.value, C.byref(nl), C.byref(top), C.byref(sp)) != 0:
+        raise SqpHipError("sqphip_mf_plan_info failed")
+    return fr, la, top.value, sp.value
+
+
 class Context:
     """Owns a sqphip_ctx (one NLP structure, `batch` instances)."""
 
@@ -200,6 +217,30 @@ class Context:
         self._ck(self.L.sqphip_mf_solve_test(self.h, inst, _d(_f(jval)), _d(_f(hval)), _d(_f(Dd)), _d(_f(sigp)),
                                              _d(_f(hd)), _i(rt), float(hsc), float(dw), _d(rhs), _d(a), _d(b), _d(dv)))
         return a, b, dv
+
+    def mf_batch_test(self, active, jval, hval, Dd, sigp, hd, rtype, hsc, dw, dw_last, fac_attempt, rhs):
+        """Batched kernel-level hook of the multifrontal path (`sqphip_mf_batch_test`); per-instance inputs stacked as
+        [B, ...].  Returns a dict: fused, standalone, dinv0, dinv1 ([B, nu]), decision ([B, 5]: outcome 0 idle / 1 another
+        shift / 2 passed / 3 given up, sel, n_factor, fac_attempt, speculates: derived on the host from the inputs), dw ([B])."""
+        rhs = _f(rhs); B = rhs.shape[0]
+        out = {k: np.zeros_like(rhs) for k in ("fused", "standalone", "dinv0", "dinv1")}
+        dec = np.zeros((B, 5), dtype=np.int32); dwo = np.zeros(B)
+        i32 = lambda a: np.ascontiguousarray(a, dtype=np.int32)
+        act, rt, fa = i32(active), i32(rtype), i32(fac_attempt)
+        self._ck(self.L.sqphip_mf_batch_test(self.h, _i(act), _d(_f(jval)), _d(_f(hval)), _d(_f(Dd)), _d(_f(sigp)), _d(_f(hd)),
+                                             _i(rt), _d(_f(hsc)), _d(_f(dw)), _d(_f(dw_last)), _i(fa), _d(rhs),
+                                             _d(out["fused"]), _d(out["standalone"]), _d(out["dinv0"]), _d(out["dinv1"]),
+                                             _i(dec), _d(dwo)))
+        out["decision"] = dec; out["dw"] = dwo
+        return out
+
+    def mf_census(self):
+        """Launch census of the multifrontal path (`sqphip_mf_census`): {kernel instantiation: launches enqueued}."""
+        nk = C.c_int32()
+        self._ck(self.L.sqphip_mf_census(self.h, None, None, 0, C.byref(nk)))
+        cnt = np.zeros(nk.value, dtype=np.int64); names = C.create_string_buffer(64 * nk.value)
+        self._ck(self.L.sqphip_mf_census(self.h, _l(cnt), names, nk.value, C.byref(nk)))
+        return {names.raw[64 * k:64 * (k + 1)].split(b"\0")[0].decode(): int(cnt[k]) for k in range(nk.value)}
 
     # ---- merit path
     def norm_violations(self, E, x, p=1):
