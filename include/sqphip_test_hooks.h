@@ -71,6 +71,33 @@ int sqphip_ldlt_solve_host(int32_t device, int32_t batch, int64_t N, const doubl
  * factorisation of the whole batch and seconds spent in the trailing-update kernel */
 int sqphip_ldlt_bench(int32_t device, int32_t batch, int64_t N, int32_t reps,
                       double *sec_per_factor, double *sec_trailing, int64_t *trailing_launches);
+/* Host-only (no GPU): what sqphip_ldlt_case_test derives from the matrices when Ts > 0.  A[batch][N * N]: lower triangles in
+ * full column-major storage; T = ceil(N / 64), Tr = T - Ts.  tmask[Tr][Ts]: the (remainder tile, leading tile) block has a
+ * non-zero in some instance; pair_ptr[Tr (Tr + 1) / 2 + 1], pair_k[cap_k] (*n_k entries exist): the pair lists the product's
+ * ordering builds from such a mask (order.hip, the same function).  SQPHIP_EINVAL and a message on stderr when some
+ * instance has an entry between two different leading tiles. */
+int sqphip_ldlt_tile_masks(int32_t batch, int64_t N, const double *A, int32_t Ts, uint8_t *tmask, int32_t *pair_ptr,
+                           int32_t *pair_k, int32_t cap_k, int32_t *n_k);
+/* One case of the dense path, everything at padded size Npad = 64 ceil(N / 64) so that the identity padding is visible.
+ * A[batch][N * N]: lower triangles in full column-major storage (the strict upper triangle of the input is ignored); the
+ * strict upper triangle of the device buffers is filled with quiet NaNs (nan_upper != 0) or zeros before the run.
+ * rhs[batch][N] (may be null: factorisation only).  phase[batch] / want: the phase mask of the kernels (null: every instance).
+ * Ts: independent leading tile columns (0: plain dense); the coupling mask and pair lists come from the zero blocks of A as in
+ * sqphip_ldlt_tile_masks (SQPHIP_EINVAL when the leading block is not block diagonal); no_tile_mask != 0: Ts set, masks null
+ * (the product under SQPHIP_NO_TILE_MASK).  The schedule switches (SQPHIP_KC, SQPHIP_OUTER, ...) are read from the environment
+ * per call, as the product reads them.  Before the run dinv and v hold `sentinel` everywhere, b and both x the right-hand side
+ * (zero padded): what an instance outside the mask must come back with.
+ * Outputs (any may be null): factor[batch][Npad * Npad] (the device buffer after the factorisation: L strictly below the
+ * diagonal), dinv[batch][Npad], npos[batch], b / v[batch][Npad] after the fused factorisation (y and D^-1 y), x_fused
+ * (ldlt_factor with the right-hand side + backward steps), x_standalone (stand-alone forward and backward steps on the same
+ * factors from a fresh right-hand side).  counts[cap] / names[cap][64] (may be null): launches per kernel instantiation of
+ * ldlt.hip during the call; info[8] = number of instantiations counted, Npad, T, diagonal tiles factorised per instance,
+ * launches enqueued on the auxiliary stream (counted where they are enqueued), 1 when the tile masks were in use, the longest
+ * run of tiles per workgroup among the k_trailing launches and among the k_colupdate launches (SQPHIP_TPB; 0: no launch). */
+int sqphip_ldlt_case_test(int32_t device, int32_t batch, int64_t N, const double *A, int32_t nan_upper, const double *rhs,
+                          const int32_t *phase, int32_t want, int32_t Ts, int32_t no_tile_mask, double sentinel,
+                          double *factor, double *dinv, int32_t *npos, double *b, double *v, double *x_fused,
+                          double *x_standalone, int64_t *counts, char *names, int32_t cap, int64_t *info);
 
 /* on-box fp64 MFMA issue-rate probe (register-resident v_mfma_f64_16x16x4_f64 loop), TFLOP/s */
 /* test hook: factorise random batches with and without the look-ahead schedule and count repetitions whose

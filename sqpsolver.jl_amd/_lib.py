@@ -145,6 +145,9 @@ def lib():
         L.sqphip_ldlt_solve_host.argtypes = [C.c_int32, C.c_int32, C.c_int64, dp, dp]
         L.sqphip_ldlt_bench.argtypes = [C.c_int32, C.c_int32, C.c_int64, C.c_int32, dp, dp, lp]
         L.sqphip_mfma_f64_peak.argtypes = [C.c_int32, dp]
+        L.sqphip_ldlt_tile_masks.argtypes = [C.c_int32, C.c_int64, dp, C.c_int32, C.POINTER(C.c_uint8), ip, ip, C.c_int32, ip]
+        L.sqphip_ldlt_case_test.argtypes = [C.c_int32, C.c_int32, C.c_int64, dp, C.c_int32, dp, ip, C.c_int32, C.c_int32,
+                                            C.c_int32, C.c_double, dp, dp, ip, dp, dp, dp, dp, lp, C.c_char_p, C.c_int32, lp]
         if hasattr(L, "sqphip_create"):
             L.sqphip_create.argtypes = [C.POINTER(vp), C.c_int64, C.c_int64, C.c_int64,
                                         C.c_int64, lp, lp, C.c_int64, lp, lp, dp, dp, dp, dp,
@@ -235,5 +238,5 @@ EXPORTS = [
     "sqphip_sqp_run", "sqphip_sqp_get", "sqphip_sqp_status", "sqphip_sqp_trace",
     "sqphip_comm_available", "sqphip_comm_unique_id", "sqphip_comm_init", "sqphip_gather_status", "sqphip_comm_destroy",
     "sqphip_get_counters", "sqphip_get_mode_counters", "sqphip_sqp_work", "sqphip_sqp_stream_begin", "sqphip_sqp_stream_set", "sqphip_sqp_stream_run", "sqphip_sqp_stream_get", "sqphip_sqp_stream_assign", "sqphip_sqp_stream_append", "sqphip_sqp_stream_release", "sqphip_sqp_stream_run_some", "sqphip_sqp_last_request", "sqphip_sqp_qp_log", "sqphip_reset_counters", "sqphip_set_timing", "sqphip_get_kernel_times", "sqphip_ldlt_factor_host",
-    "sqphip_ldlt_solve_host", "sqphip_ldlt_bench", "sqphip_ldlt_stress", "sqphip_mfma_f64_peak", "sqphip_armijo_alpha", "sqphip_compute_mu_rule",
+    "sqphip_ldlt_solve_host", "sqphip_ldlt_bench", "sqphip_ldlt_stress", "sqphip_ldlt_tile_masks", "sqphip_ldlt_case_test", "sqphip_mfma_f64_peak", "sqphip_armijo_alpha", "sqphip_compute_mu_rule",
 ]

@@ -2,6 +2,7 @@
 #include "../../include/sqphip.h"
 #include "../../include/sqphip_test_hooks.h"
 #include "sqphip_internal.hpp"
+#include <algorithm>
 #include <cmath>
 #include <cstring>
 #include <random>
@@ -38,12 +39,12 @@ struct Scratch {
     LdltPlan P;
     double *K = nullptr, *dinv = nullptr, *x = nullptr, *v = nullptr;
     int *npos = nullptr;
-    void alloc(int B, long N)
+    void alloc(int B, long N, int Ts = 0)
     {
         P.N = (int)N; P.Npad = (int)((N + 63) / 64 * 64); P.T = P.Npad / 64; P.ld = P.Npad; P.B = B;
         SQPHIP_HIP_OK(hipStreamCreate(&P.stream));
         SQPHIP_HIP_OK(hipMalloc(&K, sizeof(double) * (size_t)B * P.ld * P.Npad));
-        SQPHIP_HIP_OK(hipMalloc(&P.Wbuf, sizeof(double) * (size_t)2 * LdltPlan::MAX_R * B * P.Npad * 64));
+        SQPHIP_HIP_OK(hipMalloc(&P.Wbuf, sizeof(double) * (size_t)std::max(2 * LdltPlan::MAX_R, Ts) * B * P.Npad * 64));
         P.init_lookahead();
         SQPHIP_HIP_OK(hipMalloc(&dinv, sizeof(double) * (size_t)B * P.Npad));
         SQPHIP_HIP_OK(hipMalloc(&x, sizeof(double) * (size_t)B * P.Npad));
@@ -122,6 +123,164 @@ extern "C" int sqphip_ldlt_solve_host(int32_t device, int32_t batch, int64_t N, 
             SQPHIP_HIP_OK(hipMemcpyAsync(rhs + (long)b * N, S.x + (long)b * S.P.Npad, sizeof(double) * N,
                                          hipMemcpyDeviceToHost, S.P.stream));
         SQPHIP_HIP_OK(hipStreamSynchronize(S.P.stream));
+        return SQPHIP_OK;
+    } catch (const std::string &e) {
+        fprintf(stderr, "sqphip: %s\n", e.c_str());
+        return SQPHIP_EHIP;
+    }
+}
+
+namespace {
+// strict upper triangle of every instance's padded buffer <- val (the kernels must never let it reach an output)
+__global__ void k_fill_upper(double *K, long strideK, int ld, int Npad, double val)
+{
+    const int inst = blockIdx.y, j = blockIdx.x;
+    double *col = K + (long)inst * strideK + (long)j * ld;
+    for (int i = threadIdx.x; i < j; i += blockDim.x) col[i] = val;
+}
+
+__global__ void k_fill_value(double *p, size_t n, double val)
+{
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) p[i] = val;
+}
+
+// Coupling mask [Tr][Ts] of the (remainder tile, leading tile) blocks from the zero blocks of the lower triangles
+// A[batch][N * N] (column-major): a block is coupled iff any instance has a non-zero there; then the pair lists by the
+// product's own construction (order.hip).  False (and a message) when some instance has an entry between two different
+// leading tiles: the factorisation treats them as independent.
+bool tile_masks_from_values(int batch, long N, const double *A, int Ts, int T, std::vector<unsigned char> &tmask,
+                            std::vector<int> &pair_ptr, std::vector<int> &pair_k, std::string &msg)
+{
+    const int Tr = T - Ts;
+    const long lead_end = std::min<long>(64L * Ts, N);
+    tmask.assign((size_t)std::max(Tr, 0) * std::max(1, Ts), 0);
+    for (int b = 0; b < batch; ++b) {
+        const double *Ab = A + (long)b * N * N;
+        for (long j = 0; j < lead_end; ++j)
+            for (long i = j + 1; i < N; ++i) {
+                if (Ab[j * N + i] == 0.0) continue;
+                if (i < lead_end) {
+                    if (i / 64 != j / 64) {
+                        char buf[160];
+                        snprintf(buf, sizeof buf, "instance %d: entry (%ld, %ld) couples the leading tiles %ld and %ld", b, i, j, i / 64, j / 64);
+                        msg = buf;
+                        return false;
+                    }
+                } else
+                    tmask[(size_t)(i / 64 - Ts) * Ts + j / 64] = 1;
+            }
+    }
+    kkt_pair_lists(Ts, std::max(Tr, 0), tmask, pair_ptr, pair_k);
+    return true;
+}
+}  // namespace
+
+// Host-only: what sqphip_ldlt_case_test derives from the matrices before it launches anything.
+extern "C" int sqphip_ldlt_tile_masks(int32_t batch, int64_t N, const double *A, int32_t Ts, uint8_t *tmask,
+                                      int32_t *pair_ptr, int32_t *pair_k, int32_t cap_k, int32_t *n_k)
+{
+    if (batch < 1 || N < 1 || !A || Ts < 1 || Ts > (N + 63) / 64) return SQPHIP_EINVAL;
+    const int T = (int)((N + 63) / 64), Tr = T - Ts;
+    std::vector<unsigned char> tm;
+    std::vector<int> pp, pk;
+    std::string msg;
+    if (!tile_masks_from_values(batch, N, A, Ts, T, tm, pp, pk, msg)) {
+        fprintf(stderr, "sqphip_ldlt_tile_masks: %s\n", msg.c_str());
+        return SQPHIP_EINVAL;
+    }
+    if (tmask) for (size_t i = 0; i < (size_t)Tr * Ts; ++i) tmask[i] = tm[i];
+    if (pair_ptr) for (size_t i = 0; i < pp.size(); ++i) pair_ptr[i] = pp[i];
+    if (n_k) *n_k = (int)pk.size();
+    if (pair_k) for (size_t i = 0; i < pk.size() && i < (size_t)std::max(cap_k, 0); ++i) pair_k[i] = pk[i];
+    return SQPHIP_OK;
+}
+
+extern "C" int sqphip_ldlt_case_test(int32_t device, int32_t batch, int64_t N, const double *A, int32_t nan_upper,
+                                     const double *rhs, const int32_t *phase, int32_t want, int32_t Ts,
+                                     int32_t no_tile_mask, double sentinel, double *factor, double *dinv, int32_t *npos,
+                                     double *b, double *v, double *x_fused, double *x_standalone, int64_t *counts,
+                                     char *names, int32_t cap, int64_t *info)
+{
+    if (batch < 1 || N < 1 || !A || Ts < 0 || Ts > (N + 63) / 64 || cap < 0 || (cap > 0 && !counts)) return SQPHIP_EINVAL;
+    try {
+        const int T = (int)((N + 63) / 64), Tr = T - Ts;
+        std::vector<unsigned char> tm;
+        std::vector<int> pp, pk;
+        if (Ts > 0) {
+            std::string msg;
+            if (!tile_masks_from_values(batch, N, A, Ts, T, tm, pp, pk, msg)) {
+                fprintf(stderr, "sqphip_ldlt_case_test: %s\n", msg.c_str());
+                return SQPHIP_EINVAL;
+            }
+        }
+        SQPHIP_HIP_OK(hipSetDevice(device));
+        Scratch S;
+        S.alloc(batch, N, Ts);
+        LdltCensus cs;
+        S.P.census = &cs;
+        S.P.Ts = Ts;
+        const int Npad = S.P.Npad;
+        const long strideK = (long)S.P.ld * Npad;
+        const size_t nv = (size_t)batch * Npad;
+        hipStream_t s = S.P.stream;
+        unsigned char *d_tm = nullptr;
+        int *d_pp = nullptr, *d_pk = nullptr, *d_phase = nullptr;
+        double *x2 = nullptr;
+        struct Free { void **p; ~Free() { if (*p) hipFree(*p); } };
+        Free f1{(void **)&d_tm}, f2{(void **)&d_pp}, f3{(void **)&d_pk}, f4{(void **)&d_phase}, f5{(void **)&x2};
+        if (Ts > 0 && Tr > 0 && !no_tile_mask) {             // as sqphip_create uploads them (SQPHIP_NO_TILE_MASK: none)
+            if (pk.empty()) pk.assign(1, 0);
+            SQPHIP_HIP_OK(hipMalloc(&d_tm, tm.size()));
+            SQPHIP_HIP_OK(hipMalloc(&d_pp, sizeof(int) * pp.size()));
+            SQPHIP_HIP_OK(hipMalloc(&d_pk, sizeof(int) * pk.size()));
+            SQPHIP_HIP_OK(hipMemcpy(d_tm, tm.data(), tm.size(), hipMemcpyHostToDevice));
+            SQPHIP_HIP_OK(hipMemcpy(d_pp, pp.data(), sizeof(int) * pp.size(), hipMemcpyHostToDevice));
+            SQPHIP_HIP_OK(hipMemcpy(d_pk, pk.data(), sizeof(int) * pk.size(), hipMemcpyHostToDevice));
+            S.P.tmask = d_tm; S.P.pair_ptr = d_pp; S.P.pair_k = d_pk;
+        }
+        if (phase) {
+            SQPHIP_HIP_OK(hipMalloc(&d_phase, sizeof(int) * batch));
+            SQPHIP_HIP_OK(hipMemcpy(d_phase, phase, sizeof(int) * batch, hipMemcpyHostToDevice));
+        }
+        SQPHIP_HIP_OK(hipMalloc(&x2, sizeof(double) * nv));
+        S.upload(A);
+        hipLaunchKernelGGL(k_fill_upper, dim3(Npad, batch), dim3(64), 0, s, S.K, strideK, S.P.ld, Npad,
+                           nan_upper ? std::nan("") : 0.0);
+        // what an instance outside the mask must come back with: the sentinel in dinv and v, its right-hand side in b and x
+        hipLaunchKernelGGL(k_fill_value, dim3(64), dim3(256), 0, s, S.dinv, nv, sentinel);
+        hipLaunchKernelGGL(k_fill_value, dim3(64), dim3(256), 0, s, S.v, nv, sentinel);
+        SQPHIP_HIP_OK(hipMemsetAsync(S.x, 0, sizeof(double) * nv, s));
+        if (rhs)
+            for (int i = 0; i < batch; ++i)
+                SQPHIP_HIP_OK(hipMemcpyAsync(S.x + (long)i * Npad, rhs + (long)i * N, sizeof(double) * N, hipMemcpyHostToDevice, s));
+        SQPHIP_HIP_OK(hipMemcpyAsync(x2, S.x, sizeof(double) * nv, hipMemcpyDeviceToDevice, s));
+        // the product path: forward elimination fused into the factorisation, then the backward steps only
+        if (rhs) ldlt_factor(S.P, S.K, S.dinv, d_phase, want, nullptr, S.x, S.v);
+        else ldlt_factor(S.P, S.K, S.dinv, d_phase, want, nullptr);
+        hipLaunchKernelGGL(k_count_pos, dim3(batch), dim3(256), 0, s, S.dinv, Npad, S.P.N, S.npos);
+        if (factor) SQPHIP_HIP_OK(hipMemcpyAsync(factor, S.K, sizeof(double) * (size_t)batch * strideK, hipMemcpyDeviceToHost, s));
+        if (dinv) SQPHIP_HIP_OK(hipMemcpyAsync(dinv, S.dinv, sizeof(double) * nv, hipMemcpyDeviceToHost, s));
+        if (npos) SQPHIP_HIP_OK(hipMemcpyAsync(npos, S.npos, sizeof(int) * batch, hipMemcpyDeviceToHost, s));
+        if (rhs) {
+            if (b) SQPHIP_HIP_OK(hipMemcpyAsync(b, S.x, sizeof(double) * nv, hipMemcpyDeviceToHost, s));
+            if (v) SQPHIP_HIP_OK(hipMemcpyAsync(v, S.v, sizeof(double) * nv, hipMemcpyDeviceToHost, s));
+            ldlt_solve(S.P, S.K, S.dinv, S.x, S.v, d_phase, want, true);
+            if (x_fused) SQPHIP_HIP_OK(hipMemcpyAsync(x_fused, S.x, sizeof(double) * nv, hipMemcpyDeviceToHost, s));
+            // the refinement path: the stand-alone forward and backward steps on the same factors, fresh right-hand side
+            hipLaunchKernelGGL(k_fill_value, dim3(64), dim3(256), 0, s, S.v, nv, sentinel);
+            ldlt_solve(S.P, S.K, S.dinv, x2, S.v, d_phase, want, false);
+            if (x_standalone) SQPHIP_HIP_OK(hipMemcpyAsync(x_standalone, x2, sizeof(double) * nv, hipMemcpyDeviceToHost, s));
+        }
+        SQPHIP_HIP_OK(hipStreamSynchronize(s));
+        SQPHIP_HIP_OK(hipGetLastError());
+        for (int k = 0; k < LK_COUNT && k < cap; ++k) {
+            counts[k] = cs.launches[k];
+            if (names) { std::strncpy(names + 64 * (size_t)k, ldlt_kernel_names[k], 63); names[64 * (size_t)k + 63] = 0; }
+        }
+        if (info) {
+            info[0] = LK_COUNT; info[1] = Npad; info[2] = T; info[3] = cs.diag_tiles; info[4] = cs.aux_launches;
+            info[5] = S.P.tmask != nullptr; info[6] = cs.max_tpb_trailing; info[7] = cs.max_tpb_colupdate;
+        }
         return SQPHIP_OK;
     } catch (const std::string &e) {
         fprintf(stderr, "sqphip: %s\n", e.c_str());

@@ -758,6 +758,18 @@ __global__ __launch_bounds__(256) void k_bwd_step(const double *__restrict__ K, 
 }
 
 // ---------------------------------------------------------------------------------------------
+// launch census (sqphip_internal.hpp LdltKernel): the names, and the increment at a launch site
+const char *const ldlt_kernel_names[] = {
+    "k_diag_factor", "k_panel_trsm<1>", "k_panel_trsm_mfma", "k_colupdate<16>", "k_colupdate<32>", "k_trailing<16>",
+    "k_trailing<32>", "k_trailing_list<16>", "k_fwd_step", "k_fwd_lead", "k_bwd_step" };
+static_assert(sizeof(ldlt_kernel_names) / sizeof(ldlt_kernel_names[0]) == LK_COUNT, "a name per LdltKernel entry");
+static inline void census(const LdltPlan &P, LdltKernel k, hipStream_t s)
+{
+    if (!P.census) return;
+    P.census->launches[k]++;
+    if (P.aux && s == P.aux) P.census->aux_launches++;
+}
+
 // number of tiles (ti >= tj) in tile columns [jlo, jhi)
 static int tiles_in_cols(int T, int jlo, int jhi)
 {
@@ -777,6 +789,10 @@ static void launch_update(const LdltPlan &P, hipStream_t s, double *K, int kp, i
     if (tpb > P.tpb_max) tpb = P.tpb_max;
     if (tpb < 1) tpb = 1;
     const int nrun = (ntl + tpb - 1) / tpb;
+    if (P.census && !(use_list && P.pair_ptr)) {
+        int &m = count ? P.census->max_tpb_trailing : P.census->max_tpb_colupdate;
+        if (tpb > m) m = tpb;
+    }
     const long strideK = (long)P.ld * P.Npad, strideW = (long)P.B * P.Npad * 64;
     std::pair<hipEvent_t, hipEvent_t> ev;
     const bool timed = tm && tm->enabled && count;
@@ -784,21 +800,27 @@ static void launch_update(const LdltPlan &P, hipStream_t s, double *K, int kp, i
     if (use_list && P.pair_ptr) {
         // one tile per workgroup (the pair list belongs to the tile), plain column-major tile order (S = 1): the
         // pair index in the kernel is computed from (ti, tj) directly
+        census(P, LK_TRAILING_LIST_16, s);
         hipLaunchKernelGGL(k_trailing_list<16>, dim3(ntl * P.B), dim3(256), P.trail_pad, s, K, strideK, P.ld, P.Wbuf, strideW,
                            P.Npad, P.T, kp, nsub, wslot, jlo, jhi, P.supertile, ntl, 1, ntl, P.B, phase, want, P.pair_ptr,
                            P.pair_k);
-    } else if (count && P.kc == 16)
+    } else if (count && P.kc == 16) {
+        census(P, LK_TRAILING_16, s);
         hipLaunchKernelGGL(k_trailing<16>, dim3(nrun * P.B), dim3(256), P.trail_pad, s, K, strideK, P.ld, P.Wbuf, strideW, P.Npad,
                            P.T, kp, nsub, wslot, jlo, jhi, P.supertile, ntl, tpb, nrun, P.B, phase, want);
-    else if (count)
+    } else if (count) {
+        census(P, LK_TRAILING_32, s);
         hipLaunchKernelGGL(k_trailing<32>, dim3(nrun * P.B), dim3(256), 0, s, K, strideK, P.ld, P.Wbuf, strideW, P.Npad,
                            P.T, kp, nsub, wslot, jlo, jhi, P.supertile, ntl, tpb, nrun, P.B, phase, want);
-    else if (P.kc == 16)
+    } else if (P.kc == 16) {
+        census(P, LK_COLUPDATE_16, s);
         hipLaunchKernelGGL(k_colupdate<16>, dim3(nrun * P.B), dim3(256), 0, s, K, strideK, P.ld, P.Wbuf, strideW, P.Npad,
                            P.T, kp, nsub, wslot, jlo, jhi, P.supertile, ntl, tpb, nrun, P.B, phase, want);
-    else
+    } else {
+        census(P, LK_COLUPDATE_32, s);
         hipLaunchKernelGGL(k_colupdate<32>, dim3(nrun * P.B), dim3(256), 0, s, K, strideK, P.ld, P.Wbuf, strideW, P.Npad,
                            P.T, kp, nsub, wslot, jlo, jhi, P.supertile, ntl, tpb, nrun, P.B, phase, want);
+    }
     if (timed) { hipEventRecord(ev.second, s); tm->pending_trailing.push_back(ev); }
     if (tm && count) tm->trailing_launches++;
 }
@@ -807,19 +829,24 @@ static void launch_panel(const LdltPlan &P, hipStream_t s, double *K, double *di
                          const int *phase, int want, double *b, double *v)
 {
     const long strideK = (long)P.ld * P.Npad, strideW = (long)P.B * P.Npad * 64;
+    census(P, LK_DIAG_FACTOR, s);
+    if (P.census) P.census->diag_tiles++;
     hipLaunchKernelGGL(k_diag_factor, dim3(P.B), dim3(256), 0, s, K, strideK, P.ld, dinv, P.Npad, c, phase, want, b, v);
     const int rem = P.T - c - 1;
     if (rem <= 0) return;
     // one row tile per workgroup.  The TB = 2 instantiation (two row tiles share every L_kk read and every
     // barrier) is correct and spill-free but measured slower: 15.4 instead of 12.0 ms per factorisation, the
     // longer steps of half as many workgroups hide less latency.
-    if (P.trsm_mfma)
+    if (P.trsm_mfma) {
+        census(P, LK_PANEL_TRSM_MFMA, s);
         hipLaunchKernelGGL(k_panel_trsm_mfma, dim3((rem + 1) / 2, P.B), dim3(256), 0, s, K, strideK, P.ld, dinv,
                            P.Wbuf + (long)wslot * strideW, P.Npad, c, P.T, phase, want, b, c + 1, strideW,
                            (const unsigned char *)nullptr, 0);
-    else
-        hipLaunchKernelGGL(k_panel_trsm<1>, dim3(rem, P.B), dim3(256), 0, s, K, strideK, P.ld, dinv,
-                           P.Wbuf + (long)wslot * strideW, P.Npad, c, P.T, phase, want, b);
+        return;
+    }
+    census(P, LK_PANEL_TRSM_1, s);
+    hipLaunchKernelGGL(k_panel_trsm<1>, dim3(rem, P.B), dim3(256), 0, s, K, strideK, P.ld, dinv,
+                       P.Wbuf + (long)wslot * strideW, P.Npad, c, P.T, phase, want, b);
 }
 
 // Two-level right-looking LDL^T: outer panels of R 64-wide sub-panels, so every pass over the
@@ -838,13 +865,18 @@ void ldlt_factor(const LdltPlan &P, double *K, double *dinv, const int *phase, i
         // ---- the Ts leading tile columns are mutually independent (order.hip): the tiles between them are zero and
         //      stay zero, so all diagonal tiles factor in one launch, all their panel solves (rows >= Ts only) in a
         //      second, and one rank-64 Ts update brings the dense remainder up to date
+        census(P, LK_DIAG_FACTOR, sA);
+        if (P.census) P.census->diag_tiles += Ts;
         hipLaunchKernelGGL(k_diag_factor, dim3(P.B, Ts), dim3(256), 0, sA, K, strideK, P.ld, dinv, P.Npad, 0, phase, want, b, v);
         if (T > Ts) {
+            census(P, LK_PANEL_TRSM_MFMA, sA);
             hipLaunchKernelGGL(k_panel_trsm_mfma, dim3((T - Ts + 1) / 2, P.B, Ts), dim3(256), 0, sA, K, strideK, P.ld,
                                dinv, P.Wbuf, P.Npad, 0, T, phase, want, (double *)nullptr, Ts, strideW, P.tmask, Ts);
-            if (b)
+            if (b) {
+                census(P, LK_FWD_LEAD, sA);
                 hipLaunchKernelGGL(k_fwd_lead, dim3(T - Ts, P.B), dim3(256), 0, sA, K, strideK, P.ld, b, P.Npad, Ts, phase, want,
                                    P.tmask);
+            }
             launch_update(P, sA, K, 0, Ts, 0, Ts, T, phase, want, tm, true, /*use_list=*/true);
         }
     }
@@ -899,22 +931,31 @@ void ldlt_solve(const LdltPlan &P, const double *K, const double *dinv, double *
     const int Ts = P.Ts;
     if (!skip_fwd) {
         if (Ts > 0) {
+            census(P, LK_FWD_STEP, s);
             hipLaunchKernelGGL(k_fwd_step, dim3(1, P.B, Ts), dim3(64), 0, s, K, strideK, P.ld, dinv, x, v, P.Npad, 0,
                                phase, want, 1);
-            if (P.T > Ts)
+            if (P.T > Ts) {
+                census(P, LK_FWD_LEAD, s);
                 hipLaunchKernelGGL(k_fwd_lead, dim3(P.T - Ts, P.B), dim3(256), 0, s, K, strideK, P.ld, x, P.Npad, Ts,
                                    phase, want, P.tmask);
+            }
         }
-        for (int k = Ts; k < P.T; ++k)
+        for (int k = Ts; k < P.T; ++k) {
+            census(P, LK_FWD_STEP, s);
             hipLaunchKernelGGL(k_fwd_step, dim3(P.T - k, P.B), dim3(64), 0, s, K, strideK, P.ld, dinv, x, v,
                                P.Npad, k, phase, want, 0);
+        }
     }
-    for (int k = P.T - 1; k >= Ts; --k)
+    for (int k = P.T - 1; k >= Ts; --k) {
+        census(P, LK_BWD_STEP, s);
         hipLaunchKernelGGL(k_bwd_step, dim3(k + 1, P.B), dim3(256), 0, s, K, strideK, P.ld, x, v, P.Npad, k,
                            phase, want, 0, P.tmask, Ts);
-    if (Ts > 0)
+    }
+    if (Ts > 0) {
+        census(P, LK_BWD_STEP, s);
         hipLaunchKernelGGL(k_bwd_step, dim3(1, P.B, Ts), dim3(256), 0, s, K, strideK, P.ld, x, v, P.Npad, 0,
                            phase, want, 1, (const unsigned char *)nullptr, 0);
+    }
 }
 
 }  // namespace sqphip

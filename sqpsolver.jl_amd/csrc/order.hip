@@ -23,6 +23,20 @@
 
 namespace sqphip {
 
+// per remainder tile pair (ti >= tj, index ti (ti + 1) / 2 + tj): the leading tiles both couple to, from the coupling mask
+// tmask [Tr][Ts]
+void kkt_pair_lists(int Ts, int Tr, const std::vector<unsigned char> &tmask, std::vector<int> &pair_ptr, std::vector<int> &pair_k)
+{
+    pair_ptr.assign(1, 0);
+    pair_k.clear();
+    for (int ti = 0; ti < Tr; ++ti)
+        for (int tj = 0; tj <= ti; ++tj) {
+            for (int k = 0; k < Ts; ++k)
+                if (tmask[(size_t)ti * Ts + k] && tmask[(size_t)tj * Ts + k]) pair_k.push_back(k);
+            pair_ptr.push_back((int)pair_k.size());
+        }
+}
+
 // unknown u: variable j (u = j < n) or kept row (u = n + kpos).  adj: symmetric adjacency lists (sorted, unique)
 // long_rows: variable lists of the eliminated rows whose cliques were only chained in adj (see kkt_order)
 KktOrder kkt_order_from_graph(int n, int nc, const std::vector<std::vector<int>> &adj, bool rows_last,
@@ -166,13 +180,7 @@ KktOrder kkt_order_from_graph(int n, int nc, const std::vector<std::vector<int>>
     o.tmask.assign((size_t)o.Tr * std::max(1, o.Ts), 0);
     for (size_t k = 0; k < rem.size(); ++k)
         for (int t : touch[rem[k]]) o.tmask[(k / 64) * o.Ts + t] = 1;
-    o.pair_ptr.assign(1, 0);
-    for (int ti = 0; ti < o.Tr; ++ti)
-        for (int tj = 0; tj <= ti; ++tj) {
-            for (int k = 0; k < o.Ts; ++k)
-                if (o.tmask[(size_t)ti * o.Ts + k] && o.tmask[(size_t)tj * o.Ts + k]) o.pair_k.push_back(k);
-            o.pair_ptr.push_back((int)o.pair_k.size());
-        }
+    kkt_pair_lists(o.Ts, o.Tr, o.tmask, o.pair_ptr, o.pair_k);
     return o;
 }
 

@@ -62,6 +62,19 @@ struct Timers {
     }
 };
 
+// Launch census of the dense LDL^T: one host counter per kernel instantiation that ldlt_factor / ldlt_solve can enqueue
+// (LdltPlan::census, null in the product; the test hook sqphip_ldlt_case_test reads it and names the counters through
+// ldlt_kernel_names, ldlt.hip).  k_panel_trsm<2> has no launch site (it is never instantiated), hence no counter.
+enum LdltKernel { LK_DIAG_FACTOR, LK_PANEL_TRSM_1, LK_PANEL_TRSM_MFMA, LK_COLUPDATE_16, LK_COLUPDATE_32, LK_TRAILING_16,
+                  LK_TRAILING_32, LK_TRAILING_LIST_16, LK_FWD_STEP, LK_FWD_LEAD, LK_BWD_STEP, LK_COUNT };
+extern const char *const ldlt_kernel_names[];      // [LK_COUNT] (checked where it is defined)
+struct LdltCensus {
+    long launches[LK_COUNT] = {};
+    long diag_tiles = 0;        // diagonal tiles factorised per instance (grid.y summed over the k_diag_factor launches)
+    long aux_launches = 0;      // launches enqueued on the auxiliary stream (counted where they are enqueued)
+    int max_tpb_trailing = 0, max_tpb_colupdate = 0;   // longest run of tiles per workgroup among the k_trailing / k_colupdate launches
+};
+
 struct LdltPlan {
     int N = 0, Npad = 0, T = 0, ld = 0, B = 0;
     int R = 4;                  // 64-wide sub-panels per outer panel: the trailing update has rank 64 R
@@ -84,6 +97,7 @@ struct LdltPlan {
     int tpb_max = 1;            // longest run of tiles one Schur-update workgroup takes (SQPHIP_TPB): runs of 8
                                 // speed the bulk kernel up by 10 % but starve the look-ahead panel chain of CU
                                 // slots; 1 gives the shortest whole factorisation (measured, N = 2813, B = 64)
+    LdltCensus *census = nullptr;   // test hooks only: launches counted at enqueue (null in the product)
     void init_lookahead()
     {
         // the panel chain is latency-critical and shares the chip with the bulk update: give its stream the
@@ -140,6 +154,8 @@ struct KktOrder {
     std::vector<int> pair_ptr, pair_k;  // per remainder tile pair (ti >= tj, index ti (ti + 1) / 2 + tj): the leading
                                         // tiles both couple to = the sub-panels of the rank-64 Ts update that matter
 };
+// tmask [Tr][Ts] -> the pair lists of the rank-64 Ts update (the one construction kkt_order_from_graph and the test hooks use)
+void kkt_pair_lists(int Ts, int Tr, const std::vector<unsigned char> &tmask, std::vector<int> &pair_ptr, std::vector<int> &pair_k);
 KktOrder kkt_order(int n, int m, const std::vector<int> &kpos, int mk, const std::vector<int> &hcolptr,
                    const std::vector<int> &hrowval, const std::vector<int> &jrowptr, const std::vector<int> &jrcol,
                    bool rows_last);
