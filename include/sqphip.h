@@ -297,8 +297,10 @@ int sqphip_dense_set_instance(sqphip_ctx *ctx, int32_t inst, const double *c, co
  * Returns SQPHIP_EINVAL, sqphip_last_error naming the first offending term, on an index out of range, an entry the COO
  * structures lack or a quadratic term in a linear row; SQPHIP_ESTATE on a context attached before (any *_attach).
  * On a QCQP context sqphip_acopf_set_instance, _set_shunts, _set_dclines and sqphip_sqp_stream_begin / _set return
- * SQPHIP_EINVAL: the scenario queue does not carry QCQP values.  sqphip_acopf_eval probes the attached device
- * callbacks, the QCQP evaluator included. */
+ * SQPHIP_EINVAL: their tables are those of the ACOPF evaluators.  The scenario queue of a QCQP context is begun and
+ * filled with sqphip_qcqp_stream_begin / _set (below) and then run, shared and read with the sqphip_sqp_stream_* calls.
+ * An instance's values are one block of doubles (f0 | c | Q0 | g0 | A | Q, padded to an even count).
+ * sqphip_acopf_eval probes the attached device callbacks, the QCQP evaluator included. */
 int sqphip_qcqp_attach(sqphip_ctx *ctx, int64_t nnzQ0, const int64_t *q0r, const int64_t *q0c, const double *q0v,
                        int64_t nnzA, const int64_t *ar, const int64_t *ac, const double *av,
                        int64_t nnzQ, const int64_t *qi, const int64_t *qr, const int64_t *qc, const double *qv,
@@ -339,6 +341,25 @@ int sqphip_sqp_stream_append(sqphip_ctx *ctx, int32_t n, const int32_t *ids);
 int sqphip_sqp_stream_release(sqphip_ctx *ctx, int32_t n, int32_t *ids_out, int32_t *n_out);
 int sqphip_sqp_stream_run_some(sqphip_ctx *ctx, int32_t max_outer, int32_t *n_unstarted, int32_t *n_active);
 int sqphip_sqp_stream_get(sqphip_ctx *ctx, int32_t scenario, double *x, double *obj_val, int32_t *status, int32_t *iter);
+/* The queue of a QCQP context (sqphip_qcqp_attach): one structure, many coefficient sets, more scenarios than slots.
+ * _run, _run_some, _assign, _append, _release and _get above work on it unchanged; a slot loads a scenario by one
+ * streaming copy of its block of values into the slot's own (the layout of sqphip_qcqp_set_instance).
+ * tables for n_scenarios on a QCQP context; keep_multipliers = 1 also allocates result tables for g, mult_g,
+ * mult_x_L, mult_x_U.  SQPHIP_EINVAL on a context without sqphip_qcqp_attach. */
+int sqphip_qcqp_stream_begin(sqphip_ctx *ctx, int32_t n_scenarios, int32_t keep_multipliers);
+/* one scenario: bounds as sqphip_set_bounds, values in the term order of the attach as sqphip_qcqp_set_instance,
+ * start x0.  A NULL value part means "the values given to sqphip_qcqp_attach" (not what an instance holds now); NULL
+ * bounds mean the bounds given to sqphip_create; NULL x0 is refused.  SQPHIP_EINVAL, sqphip_last_error naming the row
+ * (0-based), for a row unbounded on both sides and, with options.kkt_condense = 1, for an equality row that was not
+ * one at sqphip_create. */
+int sqphip_qcqp_stream_set(sqphip_ctx *ctx, int32_t scenario, const double *xL, const double *xU, const double *gL,
+                           const double *gU, const double *f0, const double *c, const double *q0v, const double *g0,
+                           const double *av, const double *qv, const double *x0);
+/* everything sqphip_sqp_get returns, for a scenario of a queue begun with keep_multipliers = 1 (same signs as
+ * sqphip_sqp_get: mult_g = -lambda, mult_x_U negated; any pointer may be NULL): the slot files them with the final
+ * point before it draws its next scenario.  SQPHIP_ESTATE when the tables were not asked for. */
+int sqphip_sqp_stream_get_full(sqphip_ctx *ctx, int32_t scenario, double *x, double *g, double *mult_g,
+                               double *mult_x_L, double *mult_x_U, double *obj_val, int32_t *status, int32_t *iter);
 int sqphip_sqp_get(sqphip_ctx *ctx, int32_t inst, double *x, double *g, double *mult_g,
                    double *mult_x_L, double *mult_x_U, double *obj_val, int32_t *status,
                    int32_t *iter);

@@ -239,6 +239,8 @@ extern "C" int sqphip_create(sqphip_ctx **out, int64_t n, int64_t m, int64_t num
         C.n = n; C.m = m;
         C.h_jrow.assign(jrow, jrow + nnzJ); C.h_jcol.assign(jcol, jcol + nnzJ);
         C.h_hrow.assign(hrow, hrow + nnzH); C.h_hcol.assign(hcol, hcol + nnzH);
+        C.h_xL.assign(xL, xL + n); C.h_xU.assign(xU, xU + n);
+        if (m > 0) { C.h_gL.assign(gL, gL + m); C.h_gU.assign(gU, gU + m); }
         const int B = batch;
         d.n = (int)n; d.m = (int)m; d.nlin = (int)num_linear; d.N = (int)(n + m);
         d.Npad = (d.N + 63) / 64 * 64; d.B = B;
@@ -1002,7 +1004,8 @@ extern "C" int sqphip_acopf_attach_acwr(sqphip_ctx *h, int32_t nb, int32_t ng, i
 
 static int qcqp_refuse(sqphip_ctx *h, const char *fn)
 {
-    h->c.err = std::string(fn) + ": not available on a QCQP context (sqphip_qcqp_attach; use sqphip_qcqp_set_instance)";
+    h->c.err = std::string(fn) + ": not available on a QCQP context (sqphip_qcqp_attach; use sqphip_qcqp_set_instance, "
+               "sqphip_qcqp_stream_begin / _set)";
     return SQPHIP_EINVAL;
 }
 
@@ -1158,7 +1161,8 @@ extern "C" int sqphip_qcqp_attach(sqphip_ctx *h, int64_t nnzQ0, const int64_t *q
     // values of an instance: f0 | c | Q0 | g0 | A | Q
     const int off_c = 1, off_q0 = off_c + (int)n, off_g0 = off_q0 + (int)nnzQ0, off_a = off_g0 + (int)m,
               off_q = off_a + (int)nnzA;
-    const long nv = (long)off_q + nnzQ;
+    const long nvals = (long)off_q + nnzQ;
+    const long nv = (nvals + 1) & ~1L;     // stride of an instance's block, padded to even: every block is 16-byte aligned (b_sqp_stream)
     PlanCsr G, F, J, H;
     for (int64_t t = 0; t < nnzQ0; ++t) {
         const int64_t r = q0r[t] - 1, cc = q0c[t] - 1;
@@ -1241,8 +1245,9 @@ extern "C" int sqphip_qcqp_attach(sqphip_ctx *h, int64_t nnzQ0, const int64_t *q
         d.qcv = C.upload(all);
         d.qc = pd;
         C.qc_nv = nv;
-        const long off[7] = {0, off_c, off_q0, off_g0, off_a, off_q, nv};
+        const long off[7] = {0, off_c, off_q0, off_g0, off_a, off_q, nvals};
         std::copy(off, off + 7, C.qc_off);
+        C.h_qc_base = val0;                // (the instances' blocks are overwritten by sqphip_qcqp_set_instance)
         SQPHIP_HIP_OK(hipStreamSynchronize(C.stream));
         C.acopf_attached = true;           // (the batched run! has its device callbacks)
         make_lanes(C);
@@ -1701,6 +1706,119 @@ extern "C" int sqphip_sqp_stream_get(sqphip_ctx *h, int32_t scen, double *x, dou
         SQPHIP_HIP_OK(hipMemcpyAsync(&st, Q.rstat + scen, sizeof(int), hipMemcpyDeviceToHost, C.stream));
         SQPHIP_HIP_OK(hipMemcpyAsync(&it, Q.riter + scen, sizeof(int), hipMemcpyDeviceToHost, C.stream));
         SQPHIP_HIP_OK(hipStreamSynchronize(C.stream));
+        if (status) *status = st;
+        if (iter) *iter = it;
+        return SQPHIP_OK;
+    });
+}
+
+// ---- the queue on a QCQP context: a scenario is one block of values in the layout of DV::qcv, so that the loader of the
+// stage kernel (sqp.hip, b_sqp_stream) is one streaming copy; _run / _run_some / _assign / _append / _release / _get are shared
+extern "C" int sqphip_qcqp_stream_begin(sqphip_ctx *h, int32_t n_scenarios, int32_t keep_multipliers)
+{
+    if (!h) return SQPHIP_EINVAL;
+    if (!h->c.d.qc) { h->c.err = "sqphip_qcqp_stream_begin: the context has no QCQP attached (sqphip_qcqp_attach)"; return SQPHIP_EINVAL; }
+    if (n_scenarios <= 0) { h->c.err = "sqphip_qcqp_stream_begin: n_scenarios must be positive"; return SQPHIP_EINVAL; }
+    return guarded(h, [&](Ctx &C) {
+        DV &d = C.d;
+        StreamDev Q = {};
+        const size_t M = (size_t)n_scenarios;
+        Q.M = n_scenarios;
+        Q.next = C.dalloc<int>(1); Q.slot_scen = C.dalloc<int>((size_t)d.B);
+        Q.qend = C.dalloc<int>(1);
+        {   // hand-out order: identity, all M scenarios (sqphip_sqp_stream_assign changes it)
+            std::vector<int> ids(M);
+            for (size_t k = 0; k < M; ++k) ids[k] = (int)k;
+            Q.qids = C.upload(ids);
+            SQPHIP_HIP_OK(hipMemcpyAsync(Q.qend, &Q.M, sizeof(int), hipMemcpyHostToDevice, C.stream));
+        }
+        C.stream_started = false;
+        Q.xL = C.dalloc<double>(M * d.n); Q.xU = C.dalloc<double>(M * d.n); Q.x0 = C.dalloc<double>(M * d.n);
+        Q.gL = C.dalloc<double>(M * d.m); Q.gU = C.dalloc<double>(M * d.m);
+        Q.qcv = C.dalloc<double>(M * (size_t)C.qc_nv);
+        Q.rx = C.dalloc<double>(M * d.n); Q.robj = C.dalloc<double>(M);
+        Q.rstat = C.dalloc<int>(M); Q.riter = C.dalloc<int>(M);
+        if (keep_multipliers) {
+            Q.rE = C.dalloc<double>(M * d.m); Q.rlam = C.dalloc<double>(M * d.m);
+            Q.rmxL = C.dalloc<double>(M * d.n); Q.rmxU = C.dalloc<double>(M * d.n);
+        }
+        // slots "queue exhausted" (-1) until a _stream_run arms them; riter = -1: nothing filed (as sqphip_sqp_stream_begin)
+        SQPHIP_HIP_OK(hipMemsetAsync(Q.slot_scen, 0xff, sizeof(int) * (size_t)d.B, C.stream));
+        SQPHIP_HIP_OK(hipMemsetAsync(Q.riter, 0xff, sizeof(int) * M, C.stream));
+        SQPHIP_HIP_OK(hipStreamSynchronize(C.stream));
+        d.stream = Q;
+        make_lanes(C);
+        return SQPHIP_OK;
+    });
+}
+
+extern "C" int sqphip_qcqp_stream_set(sqphip_ctx *h, int32_t scen, const double *xL, const double *xU, const double *gL,
+                                      const double *gU, const double *f0, const double *c, const double *q0v,
+                                      const double *g0, const double *av, const double *qv, const double *x0)
+{
+    if (!h) return SQPHIP_EINVAL;
+    if (!h->c.d.qc || !h->c.d.stream.qcv) { h->c.err = "sqphip_qcqp_stream_set: no QCQP queue (sqphip_qcqp_stream_begin)"; return SQPHIP_EINVAL; }
+    if (scen < 0 || scen >= h->c.d.stream.M) {
+        h->c.err = "sqphip_qcqp_stream_set: scenario " + std::to_string(scen) + " is outside the " + std::to_string(h->c.d.stream.M) + " of the queue";
+        return SQPHIP_EINVAL;
+    }
+    if (!x0) { h->c.err = "sqphip_qcqp_stream_set: x0 is NULL (a scenario needs its start)"; return SQPHIP_EINVAL; }
+    // NULL bounds: those of sqphip_create
+    if (!xL) xL = h->c.h_xL.data();
+    if (!xU) xU = h->c.h_xU.data();
+    if (!gL) gL = h->c.h_gL.data();
+    if (!gU) gU = h->c.h_gU.data();
+    for (int i = 0; i < h->c.d.m; ++i) {
+        if (gL[i] == -INFINITY && gU[i] == INFINITY) {
+            h->c.err = "sqphip_qcqp_stream_set: row " + std::to_string(i) + " is unbounded on both sides";
+            return SQPHIP_EINVAL;
+        }
+        if (h->c.d.condense && gL[i] == gU[i] && h->c.h_kpos[i] < 0) {
+            h->c.err = "sqphip_qcqp_stream_set: row " + std::to_string(i) + " is an equality for this scenario but was not one when "
+                       "the context was created (options.kkt_condense = 1 fixes the kept rows)";
+            return SQPHIP_EINVAL;
+        }
+    }
+    return guarded(h, [&](Ctx &C) {
+        DV &d = C.d;
+        const StreamDev &Q = d.stream;
+        const size_t s = (size_t)scen;
+        h2d(C, const_cast<double *>(Q.xL) + s * d.n, xL, d.n); h2d(C, const_cast<double *>(Q.xU) + s * d.n, xU, d.n);
+        h2d(C, const_cast<double *>(Q.x0) + s * d.n, x0, d.n);
+        h2d(C, const_cast<double *>(Q.gL) + s * d.m, gL, d.m); h2d(C, const_cast<double *>(Q.gU) + s * d.m, gU, d.m);
+        // the scenario's block: the values of the attach, overlaid with the parts given (f0 | c | Q0 | g0 | A | Q)
+        std::vector<double> v(C.h_qc_base);
+        const long *o = C.qc_off;
+        const double *src[6] = {f0, c, q0v, g0, av, qv};
+        for (int k = 0; k < 6; ++k) if (src[k]) std::copy(src[k], src[k] + (o[k + 1] - o[k]), v.begin() + o[k]);
+        h2d(C, const_cast<double *>(Q.qcv) + s * (size_t)C.qc_nv, v.data(), v.size());
+        SQPHIP_HIP_OK(hipStreamSynchronize(C.stream));
+        return SQPHIP_OK;
+    });
+}
+
+extern "C" int sqphip_sqp_stream_get_full(sqphip_ctx *h, int32_t scen, double *x, double *g, double *mult_g, double *mult_x_L,
+                                          double *mult_x_U, double *obj_val, int32_t *status, int32_t *iter)
+{
+    if (!h || scen < 0 || scen >= h->c.d.stream.M) return SQPHIP_EINVAL;
+    if (!h->c.d.stream.rE) {
+        h->c.err = "sqphip_sqp_stream_get_full: the queue keeps no multipliers (sqphip_qcqp_stream_begin with keep_multipliers = 1)";
+        return SQPHIP_ESTATE;
+    }
+    return guarded(h, [&](Ctx &C) {
+        const DV &d = C.d;
+        const StreamDev &Q = d.stream;
+        const size_t s = (size_t)scen;
+        d2h(C, x, Q.rx + s * d.n, d.n); d2h(C, g, Q.rE + s * d.m, d.m); d2h(C, mult_g, Q.rlam + s * d.m, d.m);
+        d2h(C, mult_x_L, Q.rmxL + s * d.n, d.n); d2h(C, mult_x_U, Q.rmxU + s * d.n, d.n);
+        d2h(C, obj_val, Q.robj + s, 1);
+        int st = 0, it = 0;
+        SQPHIP_HIP_OK(hipMemcpyAsync(&st, Q.rstat + s, sizeof(int), hipMemcpyDeviceToHost, C.stream));
+        SQPHIP_HIP_OK(hipMemcpyAsync(&it, Q.riter + s, sizeof(int), hipMemcpyDeviceToHost, C.stream));
+        SQPHIP_HIP_OK(hipStreamSynchronize(C.stream));
+        // as sqphip_sqp_get (sqp_trust_region.jl:219-220): mult_g = -lambda, mult_x_U = -mult_x_U
+        if (mult_g) for (int i = 0; i < d.m; ++i) mult_g[i] = -mult_g[i];
+        if (mult_x_U) for (int j = 0; j < d.n; ++j) mult_x_U[j] = -mult_x_U[j];
         if (status) *status = st;
         if (iter) *iter = it;
         return SQPHIP_OK;

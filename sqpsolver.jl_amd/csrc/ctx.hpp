@@ -117,6 +117,10 @@ struct StreamDev {
     const double *xL, *xU, *gL, *gU, *ohm, *c2, *c1, *x0;   // [M][.] scenario tables
     double *rx, *robj;                                // results: final point [M][n], objective
     int *rstat, *riter;                               // ... run! status (src/status.jl), iterations
+    // queue of a QCQP context (sqphip_qcqp_stream_*; the ohm / c2 / c1 tables are null there)
+    const double *qcv;                                // [M][qc->nv] values of the scenarios, the layout of DV::qcv
+    double *rE, *rlam, *rmxL, *rmxU;                  // keep_multipliers: g [M][m], lambda [M][m], mult_x_L / _U [M][n] as the
+                                                      // device holds them (signs: sqphip_sqp_stream_get_full); null: not kept
 };
 
 struct QcqpDev;                           // qcqp_dev.hpp
@@ -196,7 +200,7 @@ struct DV {
     int max_iter, use_soc, literal_quirks;
     // ---- general sparse QCQP evaluator data
     const QcqpDev *qc;                    // non-null: a general sparse QCQP (qcqp_dev.hpp qcqp_eval; sqphip_qcqp_attach), its plans in HBM
-    double *qcv;                          // ... its values [B][qc->nv]
+    double *qcv;                          // ... its values [B][qc->nv] (nv even)
 };
 
 // phase codes by the side a kernel runs on (see the enum)
@@ -241,8 +245,10 @@ struct Ctx {
     int *h_counters = nullptr;  // pinned
     std::vector<int> h_kpos;    // host copy of DV::kpos (row -> kept position or -1)
     std::vector<int64_t> h_jrow, h_jcol, h_hrow, h_hcol;   // host copies of the COO structures of sqphip_create (1-based)
-    long qc_nv = 0;             // values per instance of an attached QCQP (DV::qcv) ...
+    long qc_nv = 0;             // doubles per instance of an attached QCQP (DV::qcv; even: the blocks are 16-byte aligned) ...
     long qc_off[7] = {};        // ... and where its parts start: f0, c, Q0, g0, A, Q, end
+    std::vector<double> h_qc_base;              // ... the values given to sqphip_qcqp_attach (NULL parts of a queue scenario)
+    std::vector<double> h_xL, h_xU, h_gL, h_gU; // the bounds given to sqphip_create (NULL bounds of a queue scenario)
     bool acopf_attached = false;
     bool mf_big_lds = false;        // the multifrontal kernels were granted 160 KB of dynamic LDS on this context's device (mf_device_setup)
     bool stream_started = false;    // scenario queue: the slots have been armed (sqphip_sqp_stream_run / _run_some)

@@ -651,7 +651,8 @@ static void sqp_run_lane(Ctx &C, int max_outer)
 
 // Scenario queue (ctx.hpp StreamDev): a slot whose run has terminated files its result under its scenario id, takes the
 // next id, loads that scenario and runs the prologue of run! -- all inside the stage kernel of the sweep in which the
-// run ended, so the slot never idles while scenarios are left.
+// run ended, so the slot never idles while scenarios are left.  On a QCQP context (sqphip_qcqp_stream_*) the scenario's
+// data is its block of values; with keep_multipliers the row values and the multipliers are filed next to the point.
 static __device__ __forceinline__ void b_sqp_stream(const DV &d)
 {
     const int inst = blockIdx.x;
@@ -664,6 +665,12 @@ static __device__ __forceinline__ void b_sqp_stream(const DV &d)
     if (cur >= 0) {
         double *rx = Q.rx + (long)cur * d.n;
         for (int j = threadIdx.x; j < d.n; j += TPB) rx[j] = x[j];
+        if (Q.rE) {                  // sqphip_qcqp_stream_begin, keep_multipliers: what sqphip_sqp_get reads from the slot
+            double *rE = Q.rE + (long)cur * d.m, *rl = Q.rlam + (long)cur * d.m;
+            double *rmL = Q.rmxL + (long)cur * d.n, *rmU = Q.rmxU + (long)cur * d.n;
+            for (int i = threadIdx.x; i < d.m; i += TPB) { const double a = E[i], b = lam[i]; rE[i] = a; rl[i] = b; }
+            for (int j = threadIdx.x; j < d.n; j += TPB) { const double a = mxL[j], b = mxU[j]; rmL[j] = a; rmU[j] = b; }
+        }
         if (threadIdx.x == 0) { Q.robj[cur] = S.obj_val; Q.rstat[cur] = S.ret; Q.riter[cur] = S.iter; }
     }
     __shared__ int nxt;
@@ -677,7 +684,25 @@ static __device__ __forceinline__ void b_sqp_stream(const DV &d)
         if (threadIdx.x == 0) Q.slot_scen[inst] = -1;
         return;
     }
-    {
+    if (d.qc) {
+        // A QCQP scenario is one block of qc->nv values in the layout of the slot's block of DV::qcv, next to its bounds and
+        // start.  nv is even and both arrays come from the allocator, so every block is 16-byte aligned: two values per
+        // access, two accesses in flight per thread, every load of an iteration before its stores.
+        double *xLw = d.xL + on, *xUw = d.xU + on, *gLw = d.gL + om, *gUw = d.gU + om, *x0w = d.x0 + on;
+        const double *sxL = Q.xL + (long)sc * d.n, *sxU = Q.xU + (long)sc * d.n, *sx0 = Q.x0 + (long)sc * d.n;
+        const double *sgL = Q.gL + (long)sc * d.m, *sgU = Q.gU + (long)sc * d.m;
+        const int nv2 = d.qc->nv >> 1;
+        const double2 *sv = reinterpret_cast<const double2 *>(Q.qcv + (long)sc * (2 * nv2));
+        double2 *vw = reinterpret_cast<double2 *>(d.qcv + (long)inst * (2 * nv2));
+        for (int k = threadIdx.x; k < nv2; k += 2 * TPB) {
+            const bool two = k + TPB < nv2;
+            const double2 a = sv[k], b = two ? sv[k + TPB] : a;
+            vw[k] = a;
+            if (two) vw[k + TPB] = b;
+        }
+        for (int j = threadIdx.x; j < d.n; j += TPB) { const double a = sxL[j], b = sxU[j], c = sx0[j]; xLw[j] = a; xUw[j] = b; x0w[j] = c; }
+        for (int i = threadIdx.x; i < d.m; i += TPB) { const double a = sgL[i], b = sgU[i]; gLw[i] = a; gUw[i] = b; }
+    } else {
         double *xLw = d.xL + on, *xUw = d.xU + on, *gLw = d.gL + om, *gUw = d.gU + om, *x0w = d.x0 + on;
         double *ohm = d.br_ohm + (long)inst * d.nl * 12, *c2 = d.c2 + (long)inst * d.ng, *c1 = d.c1 + (long)inst * d.ng;
         const double *sxL = Q.xL + (long)sc * d.n, *sxU = Q.xU + (long)sc * d.n, *sx0 = Q.x0 + (long)sc * d.n;

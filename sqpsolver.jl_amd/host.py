@@ -500,6 +500,35 @@ class Context:
         self._ck(self.L.sqphip_sqp_stream_get(self.h, int(scen), _d(x), C.byref(obj), C.byref(st), C.byref(it)))
         return dict(x=x, obj_val=obj.value, status=st.value, iter=it.value)
 
+    # ... on a QCQP context (qcqp_attach): stream_run / _assign / _append / _release / _run_some / stream_get are shared
+    def qcqp_stream_begin(self, n_scenarios, keep_multipliers=False):
+        """Tables for n_scenarios (sqphip_qcqp_stream_begin); keep_multipliers: stream_get_full returns g and the multipliers."""
+        self._ck(self.L.sqphip_qcqp_stream_begin(self.h, int(n_scenarios), int(bool(keep_multipliers))))
+
+    def qcqp_stream_set(self, scen, q=None, x0=None, **values):
+        """One scenario (sqphip_qcqp_stream_set), with the conventions of qcqp_set_instance.  With a Qcqp q: its bounds, every
+        value and its start; keywords f0, c, q0v, g0, av, qv override single parts and xL, xU, gL, gU single bounds.  A value
+        given neither way is the one of qcqp_attach, a bound given neither way the one the context was created with."""
+        names, bnames = ("f0", "c", "q0v", "g0", "av", "qv"), ("xL", "xU", "gL", "gU")
+        if q is not None:
+            values = {**{k: getattr(q, k) for k in names + bnames}, **values}
+            x0 = q.x0 if x0 is None else x0
+        bad = set(values) - set(names + bnames)
+        if bad:
+            raise TypeError(f"qcqp_stream_set: unknown values {sorted(bad)}")
+        arr = [None if values.get(k) is None else _f(np.atleast_1d(values[k])) for k in bnames + names]
+        self._ck(self.L.sqphip_qcqp_stream_set(self.h, int(scen), *[_d(a) for a in arr], _d(_f(x0))))
+
+    def stream_get_full(self, scen):
+        """The dict of sqp_get for a scenario of a queue begun with keep_multipliers (sqphip_sqp_stream_get_full)."""
+        x = np.zeros(self.n); g = np.zeros(self.m); mg = np.zeros(self.m)
+        ml = np.zeros(self.n); mu = np.zeros(self.n)
+        obj = C.c_double(); st = C.c_int32(); it = C.c_int32()
+        self._ck(self.L.sqphip_sqp_stream_get_full(self.h, int(scen), _d(x), _d(g), _d(mg), _d(ml), _d(mu), C.byref(obj),
+                                                   C.byref(st), C.byref(it)))
+        return dict(x=x, g=g, mult_g=mg, mult_x_L=ml, mult_x_U=mu, obj_val=obj.value, status=st.value,
+                    iter=it.value)
+
     def reset_counters(self):
         self._ck(self.L.sqphip_reset_counters(self.h))
 

@@ -74,7 +74,8 @@ def run_shared_queue(queue, rank, world, slots, chunk=5, exchange=None, max_roun
     append(ids).  Per round: every rank runs `chunk` outer iterations per slot, the ranks exchange two integers each,
     and unstarted ids move from the fullest queue to ranks whose queue ran dry (rebalance_plan); the ids themselves
     travel in a second small exchange.  `exchange(list_of_ints) -> list over ranks of lists` is the host channel
-    (default: torch.distributed all_gather_object).  Returns the number of rounds."""
+    (default: torch.distributed all_gather_object).  Returns the number of rounds.  The queue of a QCQP context
+    (qcqp_stream_begin / qcqp_stream_set) is driven the same way: only stream_run_some / _release / _append are used."""
     if exchange is None:
         import torch.distributed as dist
 
