@@ -139,7 +139,7 @@ void make_lanes(Ctx &C)
         L->is_lane = true;
         L->opt = C.opt; L->n = C.n; L->m = C.m; L->acopf_attached = C.acopf_attached;
         L->mfp_ = C.mfp_;
-        L->trans_period = C.trans_period; L->mf_big_lds = C.mf_big_lds; L->post_split = C.post_split; L->side_mode = C.side_mode; L->spec_tail = C.spec_tail; L->spec_mode0 = C.spec_mode0;
+        L->trans_period = C.trans_period; L->refine_slot = C.refine_slot; L->refine_period = C.refine_period; L->mf_big_lds = C.mf_big_lds; L->post_split = C.post_split; L->side_mode = C.side_mode; L->spec_tail = C.spec_tail; L->spec_mode0 = C.spec_mode0;
         L->d = group_view(C.d, lo, hi - lo, g);
         if (L->d.qcv) L->d.qcv += (long)lo * C.qc_nv;
         // the first group runs on the owner's stream (idle during sqphip_sqp_run): HIP maps streams onto four hardware
@@ -442,6 +442,8 @@ extern "C" int sqphip_create(sqphip_ctx **out, int64_t n, int64_t m, int64_t num
         }
         SQPHIP_HIP_OK(hipStreamSynchronize(C.stream));
         if (const char *e = getenv("SQPHIP_TRANS_PERIOD")) C.trans_period = atoi(e);      // experiment switch, read once per context
+        C.refine_slot = getenv("SQPHIP_REFINE_SLOT") && atoi(getenv("SQPHIP_REFINE_SLOT")) == 1;      // the second solve chain of a sweep (ipm_sweep)
+        if (const char *e = getenv("SQPHIP_REFINE_PERIOD")) C.refine_period = atoi(e);      // experiment switch
         if (d.sparse) mf_device_setup(C);
         C.post_split = getenv("SQPHIP_POST_SPLIT") && atoi(getenv("SQPHIP_POST_SPLIT")) == 1;
         C.side_mode = getenv("SQPHIP_SIDE_TRANS") && atoi(getenv("SQPHIP_SIDE_TRANS")) == 1;      // transitions on a side stream (ctx.hpp)

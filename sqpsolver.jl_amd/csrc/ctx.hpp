@@ -72,6 +72,9 @@ struct SqpState {
     int budget;          // outer iterations this instance may still start in the current sqp_run call
 };
 
+// where an instance stands in run! (sqp_trust_region.jl:124-214); kernels act only on their stage
+enum { ST_TOP = 0, ST_QP = 1, ST_SOC = 2, ST_LP = 3, ST_DONE = 4 };
+
 #define SQPHIP_TRACE_COLS 12
 #define SQPHIP_TRACE_CAP 4096
 
@@ -165,7 +168,7 @@ struct DV {
     double *op, *olam, *omxU, *omxL, *oslack;
     IpmState *ist;
     int *phase;
-    int *counters;      // [0] instances iterating, [1] start flags, [2] SQP not done, [3] start flags
+    int *counters;      // [0] instances iterating, [1] start flags, [2] SQP not done, [3] start flags, [4..6] accumulators and [7] ticket of b_sweep_count
     double ipm_tol;
     int ipm_max_iter, ipm_phase1, ipm_corrector, ipm_warm;
     int side;                             // 0: transitions in line; 1: this launch is a transition kernel on the side stream; 2: a main kernel beside it
@@ -228,7 +231,7 @@ struct Ctx {
     // armed by the scenario queue draw their scenario there, whatever the lifetime counter n_sweeps says.
     long run_sweep = 0;
     bool post_split = false;        // experiment (SQPHIP_POST_SPLIT): the right-hand side of the next iteration by its own launch behind k_ipm_post
-    bool want_resolve = true;       // monotone rule: this sweep carries the second solve slot (an instance asked for a refinement solve)
+    bool want_resolve = true;       // monotone rule: an instance asked for a refinement solve -- this sweep's solve chain serves it (or its second solve slot, refine_slot)
     // transitions on a side stream (see the PH_ enum): side_mode = allowed on this context (SQPHIP_SIDE_TRANS), side_on = in
     // use by the current run; evS[k & 3]: side job of sweep k done, evC[k & 3]: hand-over kernel of sweep k done
     bool side_mode = false, side_on = false;
@@ -237,6 +240,12 @@ struct Ctx {
     // second shift per sweep in the TAIL of a run only (large batches, where it costs throughput while every instance is busy):
     // on while at most spec_tail instances of the group have work left (sqp_run_lane); 0: off.  spec_mode0: the mode at creation
     int spec_tail = 0, spec_mode0 = 0;
+    // refinement solves (monotone rule, sparse path, streamed top): refine_slot = the second solve chain of a sweep as before
+    // (SQPHIP_REFINE_SLOT=1, read at creation: A/B runs and the equality test), otherwise they ride in the sweep's own solve chain
+    // every refine_period-th sweep of a run (SQPHIP_REFINE_PERIOD; 0: the default of ipm_sweep)
+    bool refine_slot = false;
+    int refine_period = 0;
+    long resolve_served = -1;       // ... and the last sweep of the current run whose solve chain served them (-1: none yet)
     int trans_period = 0;           // 0: by group size (3 from 64 instances, 2 from 32, else 1); SQPHIP_TRANS_PERIOD, read at creation
     Timers tm;
     std::vector<void *> allocs;
@@ -283,7 +292,8 @@ struct Ctx {
 
 // ipm.hip
 void ipm_run_all(Ctx &C);            // runs every instance whose IpmState.start is set, to completion
-void ipm_sweep(Ctx &C, bool sqp_level);
+// host_slot: pinned words the sweep's counters go to; returns whether its last kernel wrote them (else the caller launches k_sqp_count)
+bool ipm_sweep(Ctx &C, bool sqp_level, int *host_slot = nullptr);
 void sqp_stage_kernels(Ctx &C, hipStream_t s, const DV &d);      // sqp.hip: SQP-level kernels of a sweep (on the stream and with the device view given)
 void sqp_stream_arm(Ctx &C);          // scenario queue: every slot draws its first scenario in the first sweep
 void sqp_stream_rearm(Ctx &C);        // ... slots that found the queue empty look again (ids were appended)
@@ -293,7 +303,7 @@ void comm_release(Ctx &C);
 // mfront.hip
 void mf_device_setup(Ctx &C);
 void mf_factor(Ctx &C, int want, bool with_rhs, bool values_done = false);
-void mf_solve(Ctx &C, int want, bool skip_fwd, bool inertia = false);   // inertia: the streamed top kernel tests the inertia of PH_FACTOR instances first
+void mf_solve(Ctx &C, int want, bool skip_fwd, bool inertia = false, int also = -1);   // inertia: the streamed top kernel tests the inertia of PH_FACTOR instances first; also: a second phase in the same chain
 bool mf_solve_tests_inertia(const Ctx &C);     // ... which it can when the plan has a streamed top (k_mf_solve_top2)
 void launch_inertia(Ctx &C);                   // ipm.hip: k_inertia over the batch (pivot signs -> PH_SOLVE, or the next shift)
 // acopf.hip

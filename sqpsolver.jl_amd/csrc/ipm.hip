@@ -1087,22 +1087,58 @@ __global__ __launch_bounds__(TPB, SQPHIP_VEC_WAVES_PER_EU) void k_ipm_tail(DV d,
     b_ipm_prepare(d);
 }
 
+// The sweep's counters from its last kernel (k_ipm_post, where nothing runs behind it in the sweep): what k_sqp_count forms by
+// walking every instance from one workgroup -- instances with work left, pending starts, instances waiting for a refinement
+// solve -- each workgroup adds for its own instance, gated-out instances too, behind its last state write; the workgroup that
+// draws the last ticket publishes the sums and zeroes accumulators and ticket for the next launch.  Integer sums: the same in
+// any order (cf. the inertia counts, mf_dev.hpp), so the results stay deterministic.
+static __device__ __forceinline__ void b_sweep_count(const DV &d, int *host_slot)
+{
+    __syncthreads();                 // the state words of this instance are final
+    if (threadIdx.x != 0) return;
+    const int inst = blockIdx.x;
+    const SqpState &S = d.sst[inst];
+    int *acc = d.counters + 4;
+    if (!S.done && (S.budget > 0 || S.stage != ST_TOP)) atomicAdd(acc + 0, 1);
+    if (d.ist[inst].start) atomicAdd(acc + 1, 1);
+    if (d.phase[inst] == PH_RESOLVE) atomicAdd(acc + 2, 1);
+    __threadfence();
+    if (atomicAdd(acc + 3, 1) != (int)gridDim.x - 1) return;
+    __threadfence();
+    const int s0 = atomicExch(acc + 0, 0), s1 = atomicExch(acc + 1, 0), s2 = atomicExch(acc + 2, 0);
+    atomicExch(acc + 3, 0);
+    d.counters[2] = s0; d.counters[3] = s1;
+    host_slot[0] = s0; host_slot[1] = s2; __threadfence_system();
+}
+
 // Monotone barrier rule (options.ipm_corrector = 0, the default since round 4: what Ipopt, the reference's sub-solver, does
 // by default -- mu_strategy = monotone): one solve per factorisation, so everything behind that solve -- residual check,
 // step, convergence test of the new iterate, the next Newton right-hand side -- is ONE kernel, and the second solve slot
 // of a sweep exists only for the rare refinement step (0.4 % of the iterations on 512 x IEEE-118): `want` = PH_SOLVE behind
 // the solve of the sweep, PH_RESOLVE behind a refinement solve.  25 launches per sweep instead of 36.
+// also (-1: none): a second phase served by the same launch -- PH_RESOLVE, the refinement solves that rode in the sweep's solve
+// chain (ipm_sweep).  Which of the two an instance is served as is decided from its phase at kernel entry, read by every thread
+// before any thread writes state: an instance that asks for a refinement inside this launch is not mistaken for one being served.
+// host_slot (null: none): the sweep's counters go there from this kernel (b_sweep_count).
 template <int WANT, bool RHS>
-__global__ __launch_bounds__(TPB, SQPHIP_VEC_WAVES_PER_EU) void k_ipm_post(DV d, int last)
+__global__ __launch_bounds__(TPB, SQPHIP_VEC_WAVES_PER_EU) void k_ipm_post(DV d, int last, int also, int *host_slot)
 {
-    b_refine(d, last, WANT);
+    int want = WANT;
+    if (also >= 0) {
+        const int ph = __builtin_amdgcn_readfirstlane(d.phase[blockIdx.x]);
+        __syncthreads();
+        if (ph == also) want = also;
+    }
+    b_refine(d, last, want);
     __syncthreads();
     b_ipm_step(d);
     __syncthreads();
     b_ipm_prepare(d);
-    if (!RHS) return;          // (the right-hand side by k_ipm_rhs behind this kernel: experiment switch SQPHIP_POST_SPLIT)
-    __syncthreads();
-    b_build_rhs(d);
+    if (RHS) {                 // (!RHS: the right-hand side by k_ipm_rhs behind this kernel: experiment switch SQPHIP_POST_SPLIT)
+        __syncthreads();
+        b_build_rhs(d);
+    }
+    if (host_slot) b_sweep_count(d, host_slot);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1209,7 +1245,7 @@ static void read_counters(Ctx &C)
 //   backward solve, residual check                  -> SOLVE -> STEP
 //   k_ipm_step    phase STEP      -> update -> PREP
 //   k_ipm_prepare again           -> so that a converged instance is recognised in this sweep
-void ipm_sweep(Ctx &C, bool sqp_level)
+bool ipm_sweep(Ctx &C, bool sqp_level, int *host_slot)
 {
     DV &d = C.d;
     hipStream_t s = C.stream;
@@ -1275,8 +1311,19 @@ void ipm_sweep(Ctx &C, bool sqp_level)
     else ldlt_factor(C.plan, d.K, d.dinv, d.phase, PH_FACTOR, &C.tm, d.xv, d.vv);
     if (C.tm.enabled) { hipEventRecord(ev.second, s); C.tm.pending_factor.push_back(ev); }
     const bool top_inertia = d.sparse && mf_solve_tests_inertia(C);      // the streamed solve kernel tests the inertia itself
+    // Refinement solves in the sweep's own solve chain (monotone rule, sparse path, streamed top, one-workgroup vector stages):
+    // an instance in PH_RESOLVE is gated out of the values and of every front launch, so its factors stay valid in its arena
+    // until a later sweep's solve chain serves it -- forward level launches gated to it ahead of the top launch, then the top,
+    // the backward levels and k_ipm_post serve both kinds of instance.  The second chain this replaces (eight gated launches,
+    // each as long as its slowest instance, for the one or two instances of a group that wait) stays behind SQPHIP_REFINE_SLOT=1.
+    // Which sweep serves an instance changes nothing it computes.  Served every refine_period-th sweep of a run once the host
+    // has seen a request.
+    const bool ride = mono && d.sparse && !d.flat && top_inertia && !C.refine_slot && !C.post_split;
+    const int rperiod = C.refine_period > 0 ? C.refine_period : 1;
+    const int also = ride && C.want_resolve && (!sqp_level || rperiod <= 1 || (C.run_sweep % rperiod) == 0) ? (int)PH_RESOLVE : -1;
+    if (also >= 0) C.resolve_served = C.run_sweep - 1;      // (this sweep's position in the run: sqp_run_lane reads it with the counter)
     auto lin_solve = [&](int want, bool skip_fwd) {
-        if (d.sparse) mf_solve(C, want, skip_fwd, top_inertia && want == PH_SOLVE);
+        if (d.sparse) mf_solve(C, want, skip_fwd, top_inertia && want == PH_SOLVE, want == PH_SOLVE ? also : -1);
         else ldlt_solve(C.plan, d.K, d.dinv, d.xv, d.vv, d.phase, want, skip_fwd);
     };
     if (!top_inertia) launch_inertia(C);
@@ -1307,16 +1354,18 @@ void ipm_sweep(Ctx &C, bool sqp_level)
         hipLaunchKernelGGL(k_sp_clear, dim3(1), dim3(256), 0, s, d);
     };
     if (mono) {
-        // behind the solve: residual check, step, convergence test, next right-hand side; then -- only when the host has
-        // seen an instance ask for it (C.want_resolve: the counter of the sweep before last) -- the refinement solve
+        // behind the solve: residual check, step, convergence test, next right-hand side (and, where the refinement solves
+        // ride in the solve chain, the sweep's counters); otherwise then -- only when the host has seen an instance ask for it
+        // (C.want_resolve: the counter of the sweep before last) -- the refinement solve in a chain of its own
+        int *const no_slot = nullptr;
         auto post = [&](int want) {
             if (!d.flat) {
                 if (C.post_split) {
-                    if (want == PH_SOLVE) hipLaunchKernelGGL((k_ipm_post<PH_SOLVE, false>), gB, bT, vlds, s, d, last);
-                    else hipLaunchKernelGGL((k_ipm_post<PH_RESOLVE, false>), gB, bT, vlds, s, d, last);
+                    if (want == PH_SOLVE) hipLaunchKernelGGL((k_ipm_post<PH_SOLVE, false>), gB, bT, vlds, s, d, last, -1, no_slot);
+                    else hipLaunchKernelGGL((k_ipm_post<PH_RESOLVE, false>), gB, bT, vlds, s, d, last, -1, no_slot);
                     hipLaunchKernelGGL(k_ipm_rhs, gB, bT, vlds, s, d);
-                } else if (want == PH_SOLVE) hipLaunchKernelGGL((k_ipm_post<PH_SOLVE, true>), gB, bT, vlds, s, d, last);
-                else hipLaunchKernelGGL((k_ipm_post<PH_RESOLVE, true>), gB, bT, vlds, s, d, last);
+                } else if (want == PH_SOLVE) hipLaunchKernelGGL((k_ipm_post<PH_SOLVE, true>), gB, bT, vlds, s, d, last, also, ride && !C.side_on ? host_slot : no_slot);
+                else hipLaunchKernelGGL((k_ipm_post<PH_RESOLVE, true>), gB, bT, vlds, s, d, last, -1, no_slot);
                 return;
             }
             refine_front(want);
@@ -1332,13 +1381,14 @@ void ipm_sweep(Ctx &C, bool sqp_level)
         // (the refinement slot at most every fourth sweep of a run: with 128 instances in a group one of them asks for it in a
         //  third of all sweeps, and the slot costs every instance of the group a forward and a backward pass of gated kernels;
         //  the few that wait are 0.4 % of the iterations)
+        if (ride) return host_slot != nullptr && !C.side_on;
         if (C.want_resolve && (!sqp_level || d.B < 8 || (C.run_sweep & 3) == 0)) {
             if (C.tm.enabled) { ev = C.tm.get(); hipEventRecord(ev.first, s); }
             lin_solve(PH_RESOLVE, false);
             if (C.tm.enabled) { hipEventRecord(ev.second, s); C.tm.pending_solve.push_back(ev); }
             post(PH_RESOLVE);
         }
-        return;
+        return false;
     }
     if (!d.flat) hipLaunchKernelGGL(k_ipm_mid, gB, bT, vlds, s, d, last);
     else { refine_front(PH_SOLVE); hipLaunchKernelGGL(k_ipm_mid_b, gB, bT, vlds, s, d, last); reload(); }
@@ -1353,6 +1403,7 @@ void ipm_sweep(Ctx &C, bool sqp_level)
         hipLaunchKernelGGL(k_sp_products, gP, b256, 0, s, d, (int)SP_PREP, (int)PH_PREP);
         hipLaunchKernelGGL(k_ipm_prepare, gB, bT, vlds, s, d);
     }
+    return false;
 }
 
 // Runs every instance whose IpmState.start flag is set until each has a final MOI status

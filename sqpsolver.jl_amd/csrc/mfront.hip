@@ -1332,10 +1332,12 @@ __global__ __launch_bounds__(256) void k_mf_fwd(DV d, int ibegin, int want, int 
     if (s >= 0) mf_front_fwd(d, inst, s, mf_lds + wstride * wave, threadIdx.x & 63, generic);
 }
 
-__global__ __launch_bounds__(256) void k_mf_bwd(DV d, int ibegin, int want, int generic, int wstride, int vecsz, int lcap)
+// (also: a second phase served by the same launch -- the refinement solves riding in the sweep's solve chain, mf_solve; -1: none)
+__global__ __launch_bounds__(256) void k_mf_bwd(DV d, int ibegin, int want, int generic, int wstride, int vecsz, int lcap, int also)
 {
     const int inst = blockIdx.y;
-    if (d.phase[inst] != want) return;
+    const int ph = d.phase[inst];
+    if (ph != want && ph != also) return;
     extern __shared__ double mf_lds[];
     const int4 it = reinterpret_cast<const int4 *>(d.mf.sol_items)[ibegin + blockIdx.x];
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -1712,7 +1714,11 @@ __device__ __forceinline__ void mf_top_bwd(const MfTopFront &F, const double *Bf
     if constexpr (TWO) if (i1 < nc) { xtop[F.xloc + i1] = t1; xg[F.first + i1] = t1; }
 }
 
-__global__ __launch_bounds__(256) void k_mf_solve_top2(DV d, int want, int do_fwd, int inertia)
+// want: the phase served with the direction do_fwd gives; also (-1: none): a second phase served by the same launch, forward
+// and backward -- the refinement solves (PH_RESOLVE) riding in the sweep's solve chain (ipm_sweep).  The direction is a
+// per-instance decision taken from the phase as it stands behind the inertia block; one workgroup serves one instance, so it
+// stays uniform and lives in a scalar register.
+__global__ __launch_bounds__(256) void k_mf_solve_top2(DV d, int want, int do_fwd_want, int inertia, int also)
 {
     const int inst = blockIdx.x;
     if (inertia && d.phase[inst] == PH_FACTOR) {
@@ -1736,7 +1742,9 @@ __global__ __launch_bounds__(256) void k_mf_solve_top2(DV d, int want, int do_fw
                            (ish[2][0] + ish[2][1]) + (ish[2][2] + ish[2][3]), (ish[3][0] + ish[3][1]) + (ish[3][2] + ish[3][3]));
         __syncthreads();
     }
-    if (d.phase[inst] != want) return;
+    const int ph = __builtin_amdgcn_readfirstlane(d.phase[inst]);
+    if (ph != want && ph != also) return;
+    const int do_fwd = ph == want ? do_fwd_want : 1;
     const MfDev &M = d.mf;
     extern __shared__ double mf_lds[];
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -1910,10 +1918,11 @@ __global__ __launch_bounds__(256, HASBIG ? 4 : 6) void k_mf_fwd2(DV d, int ibegi
 }
 
 template <bool HASBIG>
-__global__ __launch_bounds__(256, HASBIG ? 4 : 5) void k_mf_bwd2(DV d, int ibegin, int want, int wimg)
+__global__ __launch_bounds__(256, HASBIG ? 4 : 5) void k_mf_bwd2(DV d, int ibegin, int want, int wimg, int also)
 {
     const int inst = blockIdx.y;
-    if (d.phase[inst] != want) return;
+    const int ph = d.phase[inst];
+    if (ph != want && ph != also) return;         // (also: a second phase served by the same launch, mf_solve; -1: none)
     extern __shared__ double mf_lds[];
     const MfDev &M = d.mf;
     const int4 it = reinterpret_cast<const int4 *>(M.sol_items)[ibegin + blockIdx.x];
@@ -2083,7 +2092,9 @@ bool mf_solve_tests_inertia(const Ctx &C)
 }
 
 // x (d.xv) <- K^-1 x through the factors; skip_fwd: d.vv already holds D^-1 L^-1 b (fused into mf_factor)
-void mf_solve(Ctx &C, int want, bool skip_fwd, bool inertia)
+// also (-1: none; needs the streamed top): a second phase served by the same top and backward launches, with forward level
+// launches of its own ahead of the top -- one launch group per timing class and census entry, whichever phases it serves
+void mf_solve(Ctx &C, int want, bool skip_fwd, bool inertia, int also)
 {
     const DV &d = C.d;
     hipStream_t s = C.stream;
@@ -2101,23 +2112,26 @@ void mf_solve(Ctx &C, int want, bool skip_fwd, bool inertia)
     // level launches: the LDS-staged kernels where every front of the level fits them (mfplan.hip: L.wimg >= 0)
     const bool lvl2 = !(getenv("SQPHIP_MF_LEVEL2") && atoi(getenv("SQPHIP_MF_LEVEL2")) == 0);      // (read per call: tests flip it)
     if (!C.mf_big_lds) throw std::string("sqphip: the solve kernels could not be granted 160 KB of dynamic LDS on this device (mf_device_setup)");
-    if (!skip_fwd && !C.mfp().fwd.empty()) C.tm.open(s);
-    if (!skip_fwd)
+    if (also >= 0 && !(skip_fwd && d.mf.top_n > 0 && !generic && d.B < inst_min)) throw std::string("sqphip: mf_solve: a second phase needs the streamed top behind a fused forward pass");
+    const int fwant = also >= 0 ? also : want;        // (the forward level launches serve one phase: `want` has its forward half behind it when `also` is given)
+    const bool run_fwd = !skip_fwd || also >= 0;
+    if (run_fwd && !C.mfp().fwd.empty()) C.tm.open(s);
+    if (run_fwd)
         for (const MfLaunch &L : C.mfp().fwd) {
             C.mf_census[lvl2 && !generic && L.wimg >= 0 ? (L.hasbig ? MFK_FWD2_BIG : MFK_FWD2) : MFK_FWD]++;
             if (lvl2 && !generic && L.wimg >= 0) {
-                if (L.hasbig) hipLaunchKernelGGL(k_mf_fwd2<true>, dim3(L.count, d.B), dim3(256), L.lds2, s, d, L.begin, want, L.wimg);
-                else hipLaunchKernelGGL(k_mf_fwd2<false>, dim3(L.count, d.B), dim3(256), L.lds2, s, d, L.begin, want, L.wimg);
+                if (L.hasbig) hipLaunchKernelGGL(k_mf_fwd2<true>, dim3(L.count, d.B), dim3(256), L.lds2, s, d, L.begin, fwant, L.wimg);
+                else hipLaunchKernelGGL(k_mf_fwd2<false>, dim3(L.count, d.B), dim3(256), L.lds2, s, d, L.begin, fwant, L.wimg);
             }
-            else hipLaunchKernelGGL(k_mf_fwd, dim3(L.count, d.B), dim3(256), L.lds_bytes, s, d, L.begin, want, generic, L.tiles, L.cls, L.lds_bytes / 8 - L.cls);
+            else hipLaunchKernelGGL(k_mf_fwd, dim3(L.count, d.B), dim3(256), L.lds_bytes, s, d, L.begin, fwant, generic, L.tiles, L.cls, L.lds_bytes / 8 - L.cls);
         }
-    if (!skip_fwd && !C.mfp().fwd.empty()) C.tm.close(KC_SOLVE_LEVELS, s);
+    if (run_fwd && !C.mfp().fwd.empty()) C.tm.close(KC_SOLVE_LEVELS, s);
     const bool has_top = (d.mf.top_n > 0 && !generic) || C.mfp().top.count > 0;
     if (has_top) C.tm.open(s);
     if (d.mf.top_n > 0 && !generic) {
         const size_t lds = (size_t)C.mfp().top2_lds_bytes;
         C.mf_census[MFK_SOLVE_TOP2]++;
-        hipLaunchKernelGGL(k_mf_solve_top2, dim3(d.B), dim3(256), lds, s, d, want, skip_fwd ? 0 : 1, inertia ? 1 : 0);
+        hipLaunchKernelGGL(k_mf_solve_top2, dim3(d.B), dim3(256), lds, s, d, want, skip_fwd ? 0 : 1, inertia ? 1 : 0, also);
     } else if (const MfLaunch &T = C.mfp().top; T.count > 0) {
         C.mf_census[MFK_SOLVE_TOP]++;
         hipLaunchKernelGGL(k_mf_solve_top, dim3(d.B), dim3(256), T.lds_bytes, s, d, T.begin, T.count, want, skip_fwd ? 0 : 1, generic,
@@ -2128,10 +2142,10 @@ void mf_solve(Ctx &C, int want, bool skip_fwd, bool inertia)
     for (const MfLaunch &L : C.mfp().bwd) {
         C.mf_census[lvl2 && !generic && L.wimg >= 0 ? (L.hasbig ? MFK_BWD2_BIG : MFK_BWD2) : MFK_BWD]++;
         if (lvl2 && !generic && L.wimg >= 0) {
-            if (L.hasbig) hipLaunchKernelGGL(k_mf_bwd2<true>, dim3(L.count, d.B), dim3(256), L.lds2, s, d, L.begin, want, L.wimg);
-            else hipLaunchKernelGGL(k_mf_bwd2<false>, dim3(L.count, d.B), dim3(256), L.lds2, s, d, L.begin, want, L.wimg);
+            if (L.hasbig) hipLaunchKernelGGL(k_mf_bwd2<true>, dim3(L.count, d.B), dim3(256), L.lds2, s, d, L.begin, want, L.wimg, also);
+            else hipLaunchKernelGGL(k_mf_bwd2<false>, dim3(L.count, d.B), dim3(256), L.lds2, s, d, L.begin, want, L.wimg, also);
         }
-        else hipLaunchKernelGGL(k_mf_bwd, dim3(L.count, d.B), dim3(256), L.lds_bytes, s, d, L.begin, want, generic, L.tiles, L.cls, L.lds_bytes / 8 - L.cls);
+        else hipLaunchKernelGGL(k_mf_bwd, dim3(L.count, d.B), dim3(256), L.lds_bytes, s, d, L.begin, want, generic, L.tiles, L.cls, L.lds_bytes / 8 - L.cls, also);
     }
     if (!C.mfp().bwd.empty()) C.tm.close(KC_SOLVE_LEVELS, s);
 }

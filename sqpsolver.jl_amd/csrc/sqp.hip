@@ -19,9 +19,6 @@
 
 namespace sqphip {
 
-// where an instance stands in run! (sqp_trust_region.jl:124-214); kernels act only on their stage
-enum { ST_TOP = 0, ST_QP = 1, ST_SOC = 2, ST_LP = 3, ST_DONE = 4 };
-
 // the sub-problem requested by this instance has reached a final MOI status
 static __device__ __forceinline__ bool qp_final(const DV &d, int inst)
 {
@@ -477,6 +474,8 @@ __global__ void k_sqp_count(DV d, int *host_slot)
     // two words in pinned host memory (written from here: one launch per sweep less than a device-to-host copy behind it)
     // host_slot[1] (round 4): instances waiting for a refinement solve (PH_RESOLVE) -- with the monotone rule the second solve
     // slot of a sweep is launched only when the host has seen one (ipm_sweep, Ctx::want_resolve)
+    // (Where k_ipm_post is the last kernel of the sweep it forms the same three counts itself -- b_sweep_count, ipm.hip -- and this
+    //  kernel is not launched; it remains for the other paths and for the side-stream mode, whose hand-over lives here.)
     int nb = 0, ns = 0, nr = 0;
     for (int i = threadIdx.x; i < d.B; i += blockDim.x) {
         // transitions on a side stream: the hand-over between the two sides (ctx.hpp, the PH_ enum); both streams are
@@ -577,6 +576,7 @@ static void sqp_run_lane(Ctx &C, int max_outer)
     const dim3 gB(d.B), bT(TPB);
     C.run_sweep = 0;                     // (the first sweep of a run always carries the transitions: ipm_sweep)
     C.want_resolve = true;               // (... and the refinement slot, until the first counter has come back)
+    C.resolve_served = -1;
     // transitions on a side stream (ctx.hpp, the PH_ enum; ipm_sweep): monotone rule, sparse path, one-workgroup vector stages
     C.side_on = C.side_mode && d.sparse && !d.flat && d.ipm_corrector == 0 && d.B >= 8;
     if (C.side_on && !C.side) {
@@ -588,6 +588,7 @@ static void sqp_run_lane(Ctx &C, int max_outer)
     struct SideOff { Ctx &C; ~SideOff() { C.d.side = 0; C.side_on = false; C.d.spec_mode = C.spec_mode0; } } side_off{C};     // (other entry points run in line)
     hipLaunchKernelGGL(k_sqp_budget, dim3(1), dim3(64), 0, s, d, max_outer > 0 ? max_outer : 0x3fffffff);
     hipLaunchKernelGGL(k_sqp_begin, gB, bT, 0, s, d);
+    SQPHIP_HIP_OK(hipMemsetAsync(d.counters + 4, 0, 4 * sizeof(int), s));      // accumulators and ticket of b_sweep_count (a run that failed may have left them)
     // The "anyone left?" counter of sweep k is read while sweep k + 1 is already queued: the stream never runs dry
     // behind a host round trip.  The price is one sweep of gated-off kernels after the last instance has finished.
     static const bool sweep_log = getenv("SQPHIP_SWEEP_LOG") != nullptr;    // instances with work left, per sweep
@@ -607,7 +608,10 @@ static void sqp_run_lane(Ctx &C, int max_outer)
         }
         SQPHIP_HIP_OK(hipGetLastError());   // a failed launch anywhere in the sweep surfaces here
         const int left = C.h_counters[2 + 2 * (k & 1)];
-        C.want_resolve = C.h_counters[3 + 2 * (k & 1)] > 0;      // (refinement solves pending after sweep k: the next sweep queued carries the slot)
+        // refinement solves pending after sweep k: the next sweep queued serves them -- unless a sweep behind k has been queued
+        // with them already (the counter is one sweep late: sweep k + 1 is in the queue): its solve chain serves every instance
+        // that waited when sweep k ended, and what asks inside it shows in its own counter
+        C.want_resolve = C.h_counters[3 + 2 * (k & 1)] > 0 && C.resolve_served <= k;
         if (C.spec_tail > 0) d.spec_mode = left <= C.spec_tail ? 1 : 0;     // second shift per sweep in the tail of the run (api.hip)
         if (sweep_log) fprintf(stderr, "%d%c", left, (k % 32) == 31 ? '\n' : ' ');
         return left;
@@ -615,11 +619,12 @@ static void sqp_run_lane(Ctx &C, int max_outer)
     try {
         for (long sweep = 0; sweep < 100000000L; ++sweep) {
             const auto q0 = std::chrono::steady_clock::now();
-            ipm_sweep(C, /*sqp_level=*/true);
             int *slot = nullptr;                 // device view of the pinned words this sweep reports into
             SQPHIP_HIP_OK(hipHostGetDevicePointer((void **)&slot, C.h_counters + 2 + 2 * (sweep & 1), 0));
+            // (the last kernel of the sweep forms the counts itself where it can -- b_sweep_count, ipm.hip --, k_sqp_count otherwise)
+            const bool counted = ipm_sweep(C, /*sqp_level=*/true, C.side_on ? nullptr : slot);
             if (C.side_on && sweep > 0) SQPHIP_HIP_OK(hipStreamWaitEvent(s, C.evS[sweep & 3], 0));     // the side job of this sweep
-            hipLaunchKernelGGL(k_sqp_count, dim3(1), dim3(64), 0, s, d, slot);
+            if (!counted) hipLaunchKernelGGL(k_sqp_count, dim3(1), dim3(64), 0, s, d, slot);
             if (C.side_on) SQPHIP_HIP_OK(hipEventRecord(C.evC[sweep & 3], s));
             SQPHIP_HIP_OK(hipEventRecord(ev[sweep & 1], s));
             if (host_stats) { hs_queue += std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - q0).count(); ++hs_sweeps; }
