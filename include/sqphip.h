@@ -153,6 +153,29 @@ int sqphip_qp_stats(const sqphip_ctx *ctx, int32_t *ipm_iters, int32_t *n_factor
  * accurate to 1e4 x ipm_tol only. */
 int sqphip_qp_termination(const sqphip_ctx *ctx, int32_t *rule, double *scaled_error);
 
+/* ---- the seat for many host models at once ---------------------------------------------------------
+ * `count` sub-problems in one call, request k on instance inst[k] of the context -- the bounds sqphip_set_bounds gave that
+ * instance -- with its own mode[k], delta[k], mu[k].  Arrays are stored back to back per request: x_k, df [count][n],
+ * E [count][m], Jval [count][nnzJ], Hval [count][nnzH] or NULL; outputs p, mult_x_U, mult_x_L [count][n], lambda [count][m],
+ * slack [count][2m] or NULL, moi_status [count].  count in 1 .. batch, inst[k] in range and pairwise distinct, modes in range,
+ * else SQPHIP_EINVAL with sqphip_last_error naming the offending index; NULL rules as for sqphip_qp_solve (df and E may be
+ * NULL only when every mode is LP).  Request k returns bit for bit what sqphip_qp_solve returns for it on a context whose
+ * instance 0 carries the bounds of inst[k]: no instance's arithmetic depends on which others are active.  Instances not
+ * listed keep their outputs, warm-start state and interior-point state (the start flags are cleared for all, as
+ * sqphip_qp_solve does).  The call lasts as long as its slowest request.  Its HIP traffic does not grow with count: the
+ * operands are packed into a pinned staging buffer (allocated at the first batch call, sized for the batch), moved by one
+ * copy and spread over the instances by one kernel; results and the instances' states come back the same way.  The
+ * counters of sqphip_get_counters advance by the sums over the batch; afterwards sqphip_qp_stats / _termination describe
+ * request count - 1. */
+int sqphip_qp_solve_batch(sqphip_ctx *ctx, int32_t count, const int32_t *inst, const int32_t *mode, const double *x_k,
+                          const double *delta, const double *mu, const double *df, const double *E, const double *Jval,
+                          const double *Hval, double *p, double *lambda, double *mult_x_U, double *mult_x_L, double *slack,
+                          int32_t *moi_status);
+/* sqphip_qp_stats and sqphip_qp_termination for the last sub-problem of each listed instance, read from the device
+ * ([count] each, any may be NULL) */
+int sqphip_qp_stats_batch(const sqphip_ctx *ctx, int32_t count, const int32_t *inst, int32_t *ipm_iters, int32_t *n_factor,
+                          int32_t *rule, double *scaled_error);
+
 /* ---- merit / acceptance path (device reductions over host-supplied vectors) -------------------- */
 /* common.jl:54-77; pnorm 1, 2 or 0 (=Inf) */
 int sqphip_norm_violations(sqphip_ctx *ctx, const double *E, const double *x, int32_t pnorm,
@@ -182,6 +205,26 @@ int sqphip_compute_derivative(sqphip_ctx *ctx, const double *df, const double *p
 int sqphip_compute_derivative_full(sqphip_ctx *ctx, const double *df, const double *p, const double *E, double mu,
                                    const double *mu_vec, int32_t feasibility_restoration, const double *slack,
                                    double *D);
+/* Batch forms of the merit calls run! makes: `count, inst` in front as for sqphip_qp_solve_batch, every vector operand
+ * [count][.] stored back to back, every scalar operand [count], flags (pnorm, feasibility_restoration, with_step) one value
+ * per call, out [count].  Operands of request k are staged into the vectors of instance inst[k] and reduced with its bounds
+ * by the arithmetic of the scalar call, in the same order: out[k] is bit for bit the scalar result. */
+int sqphip_norm_violations_batch(sqphip_ctx *ctx, int32_t count, const int32_t *inst, const double *E, const double *x,
+                                 int32_t pnorm, double *out);
+int sqphip_kt_residuals_batch(sqphip_ctx *ctx, int32_t count, const int32_t *inst, const double *df, const double *lambda,
+                              const double *mult_x_U, const double *mult_x_L, const double *Jval, double *out);
+int sqphip_norm_complementarity_batch(sqphip_ctx *ctx, int32_t count, const int32_t *inst, const double *E,
+                                      const double *lambda, int32_t pnorm, double *out);
+int sqphip_compute_phi_batch(sqphip_ctx *ctx, int32_t count, const int32_t *inst, const double *f_trial,
+                             const double *E_trial, const double *x_trial, const double *mu,
+                             int32_t feasibility_restoration, double *phi);
+int sqphip_compute_qmodel_batch(sqphip_ctx *ctx, int32_t count, const int32_t *inst, const double *x, const double *p,
+                                const double *df, const double *E, const double *Jval, const double *Hval, const double *mu,
+                                int32_t with_step, double *q);
+/* mu_vec [count][m] or NULL for the whole call; slack [count][2m] under feasibility restoration */
+int sqphip_compute_derivative_full_batch(sqphip_ctx *ctx, int32_t count, const int32_t *inst, const double *df,
+                                         const double *p, const double *E, const double *mu, const double *mu_vec,
+                                         int32_t feasibility_restoration, const double *slack, double *D);
 /* sqp_trust_region.jl:529-538,:574-577: ratio test and radius update.
  * accept_out = 1 if ared > 0 and ared/pred > 0; delta_out the updated radius. */
 int sqphip_tr_update(double ared, double pred, double delta, double pnorm_inf,

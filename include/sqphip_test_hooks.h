@@ -105,6 +105,12 @@ int sqphip_ldlt_case_test(int32_t device, int32_t batch, int64_t N, const double
 int sqphip_ldlt_stress(int32_t device, int32_t batch, int64_t N, int32_t reps, int32_t *mismatches);
 int sqphip_mfma_f64_peak(int32_t device, double *tflops);
 
+/* test hook of the batched seat: what instance `inst` holds on the device in the output slots of the sub-problem seat (the
+ * results sqphip_qp_solve / _batch returned for it last) and the MOI status of its interior-point state -- an instance a batch
+ * call does not list must come back unchanged.  Any output may be NULL. */
+int sqphip_seat_peek(sqphip_ctx *ctx, int32_t inst, double *p, double *lambda, double *mult_x_U, double *mult_x_L,
+                     double *slack, int32_t *moi_status);
+
 #ifdef __cplusplus
 }
 #endif

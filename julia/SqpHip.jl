@@ -94,6 +94,30 @@ function sub_optimize_lp(qp::QpHip, x_k)                                        
     return x, λ, mU, mL, st
 end
 
+# ---- many models on one context: request k runs on instance inst[k] (0-based, bounds through sqphip_set_bounds) -----
+# Operands are matrices with one COLUMN per request (column-major: back to back per request, as the C side reads them);
+# hval may be `nothing`.  Returns (p, λ, mult_x_U, mult_x_L, slack, statuses), the vectors again one column per request.
+function qp_solve_batch!(ctx::Ptr{Cvoid}, inst::Vector{Int32}, mode::Vector{Int32}, x_k::Matrix{Float64},
+                         Δ::Vector{Float64}, μ::Vector{Float64}, df::Matrix{Float64}, E::Matrix{Float64},
+                         dE::Matrix{Float64}, hval::Union{Nothing,Matrix{Float64}})
+    count = length(inst); n, m = size(x_k, 1), size(E, 1)
+    p, λ, mU, mL = zeros(n, count), zeros(m, count), zeros(n, count), zeros(n, count)
+    slack = zeros(2m, count); st = zeros(Int32, count)
+    rc = ccall((:sqphip_qp_solve_batch, LIBSQPHIP), Cint,
+               (Ptr{Cvoid}, Int32, Ptr{Int32}, Ptr{Int32}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble},
+                Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Int32}),
+               ctx, count, inst, mode, x_k, Δ, μ, df, E, dE, isnothing(hval) ? C_NULL : pointer(hval), p, λ, mU, mL, slack, st)
+    _check(ctx, rc)
+    return p, λ, mU, mL, slack, MOI.TerminationStatusCode.(st)
+end
+function hip_norm_violations_batch(ctx::Ptr{Cvoid}, inst::Vector{Int32}, E::Matrix{Float64}, x::Matrix{Float64}, p = 1)
+    out = zeros(length(inst)); code = p == Inf ? 0 : Int(p)
+    _check(ctx, ccall((:sqphip_norm_violations_batch, LIBSQPHIP), Cint,
+                      (Ptr{Cvoid}, Int32, Ptr{Int32}, Ptr{Cdouble}, Ptr{Cdouble}, Int32, Ptr{Cdouble}),
+                      ctx, length(inst), inst, E, x, code, out))
+    return out
+end
+
 # ---- merit path: one ccall each, host vectors in, scalar out --------------------------------------------------------
 function hip_norm_violations(qp::QpHip, E, x, p = 1)                               # common.jl:54-77
     out = Ref{Cdouble}(0); code = p == Inf ? 0 : Int(p)

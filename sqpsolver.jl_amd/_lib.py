@@ -159,6 +159,16 @@ def lib():
             L.sqphip_qp_solve.argtypes = [vp, C.c_int32, dp, C.c_double, C.c_double, dp, dp, dp, dp,
                                           dp, dp, dp, dp, dp, ip]
             L.sqphip_qp_stats.argtypes = [vp, ip, ip]
+            if hasattr(L, "sqphip_qp_solve_batch"):       # (an older build given through SQPHIP_SO lacks the batched seat)
+                L.sqphip_qp_solve_batch.argtypes = [vp, C.c_int32, ip, ip] + [dp] * 7 + [dp] * 5 + [ip]
+                L.sqphip_qp_stats_batch.argtypes = [vp, C.c_int32, ip, ip, ip, ip, dp]
+                L.sqphip_seat_peek.argtypes = [vp, C.c_int32, dp, dp, dp, dp, dp, ip]
+                L.sqphip_norm_violations_batch.argtypes = [vp, C.c_int32, ip, dp, dp, C.c_int32, dp]
+                L.sqphip_kt_residuals_batch.argtypes = [vp, C.c_int32, ip, dp, dp, dp, dp, dp, dp]
+                L.sqphip_norm_complementarity_batch.argtypes = [vp, C.c_int32, ip, dp, dp, C.c_int32, dp]
+                L.sqphip_compute_phi_batch.argtypes = [vp, C.c_int32, ip, dp, dp, dp, dp, C.c_int32, dp]
+                L.sqphip_compute_qmodel_batch.argtypes = [vp, C.c_int32, ip, dp, dp, dp, dp, dp, dp, dp, C.c_int32, dp]
+                L.sqphip_compute_derivative_full_batch.argtypes = [vp, C.c_int32, ip, dp, dp, dp, dp, dp, C.c_int32, dp, dp]
             L.sqphip_qp_termination.argtypes = [vp, ip, dp]
             L.sqphip_sqp_qp_log_term.argtypes = [vp, C.c_int32, dp, ip, C.c_int32, ip]
             L.sqphip_get_termination_counters.argtypes = [vp, C.POINTER(C.c_int64)]
@@ -233,7 +243,10 @@ def lib():
 
 EXPORTS = [
     "sqphip_default_options", "sqphip_create", "sqphip_destroy", "sqphip_last_error",
-    "sqphip_set_bounds", "sqphip_qp_solve", "sqphip_qp_stats", "sqphip_qp_termination", "sqphip_sqp_qp_log_term", "sqphip_get_termination_counters", "sqphip_norm_violations",
+    "sqphip_set_bounds", "sqphip_qp_solve", "sqphip_qp_stats",
+    "sqphip_qp_solve_batch", "sqphip_qp_stats_batch", "sqphip_seat_peek", "sqphip_norm_violations_batch", "sqphip_kt_residuals_batch",
+    "sqphip_norm_complementarity_batch", "sqphip_compute_phi_batch", "sqphip_compute_qmodel_batch",
+    "sqphip_compute_derivative_full_batch", "sqphip_qp_termination", "sqphip_sqp_qp_log_term", "sqphip_get_termination_counters", "sqphip_norm_violations",
     "sqphip_kt_residuals", "sqphip_norm_complementarity", "sqphip_compute_phi",
     "sqphip_compute_qmodel", "sqphip_compute_derivative", "sqphip_compute_derivative_full", "sqphip_compute_mu_rule_dev",
     "sqphip_acopf_armijo", "sqphip_tr_update",

@@ -22,6 +22,7 @@ Ctx::~Ctx()
     plan.destroy_lookahead();
     for (void *p : allocs) hipFree(p);
     if (h_counters) hipHostFree(h_counters);
+    if (stg_h) hipHostFree(stg_h);
     if (side) { hipStreamDestroy(side); for (auto &e : evS) if (e) hipEventDestroy(e); for (auto &e : evC) if (e) hipEventDestroy(e); }
     if (stream && owns_stream) hipStreamDestroy(stream);
 }
@@ -177,6 +178,70 @@ __global__ void k_qp_request(DV d, int inst, int mode, double delta, double mu_p
         I.stage = 0; I.rho_big = 1e4; I.start = 1; I.ipm_iters = 0; I.n_factor = 0; I.n_solve = 0; I.status = 0;
     }
 }
+
+// the same for the requests of sqphip_qp_solve_batch: instances inst[0 .. count) (pairwise distinct, checked on the host) with
+// their own mode, radius and penalty; every other instance loses its start flag and keeps everything else.  One workgroup,
+// strided over the batch and over the requests (either may exceed the workgroup).
+__global__ __launch_bounds__(256) void k_qp_request_batch(DV d, int count, const int *inst, const int *mode, const double *delta,
+                                                          const double *mu_pen)
+{
+    for (int i = threadIdx.x; i < d.B; i += blockDim.x) d.ist[i].start = 0;
+    __syncthreads();
+    for (int k = threadIdx.x; k < count; k += blockDim.x) {
+        IpmState &I = d.ist[inst[k]];
+        I.mode = mode[k]; I.delta = delta[k]; I.mu_pen = mu_pen[k];
+        I.stage = 0; I.rho_big = 1e4; I.start = 1; I.ipm_iters = 0; I.n_factor = 0; I.n_solve = 0; I.status = 0;
+    }
+}
+
+// Staging of the batched seat.  A call packs its operands on the host into one pinned buffer, request
+// after request: row k holds the fields of request k back to back, every field padded to an even number of doubles, so that
+// rows and fields start on 16-byte boundaries.  One copy moves the buffer, then k_seat_stage<true> spreads row k over the
+// slots of instance inst[k] (field f -> base[f] + inst[k] * stride[f]); k_seat_stage<false> collects results the other way,
+// and the IpmState of every listed instance behind the rows.  Streaming copies: 16-byte loads from / stores to staging, and
+// to / from a slot where the slot is aligned (n, m or the nnz odd: every other instance is not), two 8-byte ones otherwise.
+#define SQPHIP_SEAT_FIELDS 8
+struct StageMap {
+    int nf, row;                                  // fields in use; doubles per row (even)
+    int len[SQPHIP_SEAT_FIELDS], off[SQPHIP_SEAT_FIELDS], stride[SQPHIP_SEAT_FIELDS];   // off < 0 (to the slots only): zeros
+    double *base[SQPHIP_SEAT_FIELDS];
+    const IpmState *ist;                          // from the slots only, may be null: the states go to stg + ist_off,
+    long ist_off;                                 // sizeof(IpmState) / 8 doubles each
+};
+
+template <bool TO_SLOTS>
+__global__ __launch_bounds__(256) void k_seat_stage(StageMap M, double *stg, const int *inst)
+{
+    const int k = blockIdx.y, b = inst[k];
+    double *row = stg + (long)k * M.row;
+#pragma unroll
+    for (int f = 0; f < SQPHIP_SEAT_FIELDS; ++f) {
+        if (f >= M.nf) break;
+        const int len = M.len[f];
+        double *slot = M.base[f] + (long)b * M.stride[f];
+        const bool al = ((unsigned long)slot & 15ul) == 0;
+        for (int q = blockIdx.x * 256 + threadIdx.x; 2 * q < len; q += gridDim.x * 256) {
+            const bool two = 2 * q + 1 < len;
+            if (TO_SLOTS) {
+                const double2 v = M.off[f] < 0 ? make_double2(0.0, 0.0) : *(const double2 *)(row + M.off[f] + 2 * q);
+                if (two && al) *(double2 *)(slot + 2 * q) = v;
+                else { slot[2 * q] = v.x; if (two) slot[2 * q + 1] = v.y; }
+            } else {
+                double2 v;
+                if (two && al) v = *(const double2 *)(slot + 2 * q);
+                else { v.x = slot[2 * q]; v.y = two ? slot[2 * q + 1] : 0.0; }
+                *(double2 *)(row + M.off[f] + 2 * q) = v;
+            }
+        }
+    }
+    if (!TO_SLOTS && M.ist && blockIdx.x == 0) {
+        constexpr int W = (int)(sizeof(IpmState) / 8);
+        const unsigned long long *src = (const unsigned long long *)(M.ist + b);    // (bit copies)
+        unsigned long long *dst = (unsigned long long *)(stg + M.ist_off) + (long)k * W;
+        for (int w = threadIdx.x; w < W; w += 256) dst[w] = src[w];
+    }
+}
+static_assert(sizeof(IpmState) % 8 == 0, "k_seat_stage copies IpmState in 8-byte words");
 
 // test hook (sqphip_mf_solve_test): instance `inst` alone enters phase `ph` with the given Hessian scale / delta_w
 __global__ void k_mf_test_setup(DV d, int inst, double hsc, double dw, int ph)
@@ -686,6 +751,190 @@ extern "C" int sqphip_qp_termination(const sqphip_ctx *h, int32_t *rule, double 
     return SQPHIP_OK;
 }
 
+// ---- the batched seat ---------------------------------------------------------------------------
+namespace {
+
+inline long ev(long k) { return (k + 1) & ~1L; }       // doubles of a staged field: padded to 16 bytes
+
+// count in 1 .. batch, inst[k] in range and pairwise distinct; the message names the offending index
+int seat_check(sqphip_ctx *h, const char *fn, int32_t count, const int32_t *inst)
+{
+    Ctx &C = h->c;
+    if (count < 1 || count > C.d.B) { C.err = std::string(fn) + ": count " + std::to_string(count) + " is outside 1 .. batch = " + std::to_string(C.d.B); return SQPHIP_EINVAL; }
+    if (!inst) { C.err = std::string(fn) + ": inst is NULL"; return SQPHIP_EINVAL; }
+    std::vector<int> seen((size_t)C.d.B, -1);
+    for (int k = 0; k < count; ++k) {
+        if (inst[k] < 0 || inst[k] >= C.d.B) { C.err = std::string(fn) + ": inst[" + std::to_string(k) + "] = " + std::to_string(inst[k]) + " is outside 0 .. batch - 1 = " + std::to_string(C.d.B - 1); return SQPHIP_EINVAL; }
+        if (seen[inst[k]] >= 0) { C.err = std::string(fn) + ": inst[" + std::to_string(k) + "] = " + std::to_string(inst[k]) + " repeats inst[" + std::to_string(seen[inst[k]]) + "]"; return SQPHIP_EINVAL; }
+        seen[inst[k]] = k;
+    }
+    return SQPHIP_OK;
+}
+
+// One call of the batched seat in staging: header (per request: two scalars, the instance, the mode), then the rows.
+//   doubles [0, cp) a0, [cp, 2 cp) a1, then cp int32 inst and cp int32 mode (cp = count padded to even), rows from 3 cp
+struct SeatCall {
+    Ctx &C;
+    int count; long cp, rows0;
+    StageMap in{}, out{};
+    const double *src[SQPHIP_SEAT_FIELDS] = {};
+    SeatCall(Ctx &C_, int count_) : C(C_), count(count_), cp(ev(count_)), rows0(3 * ev(count_))
+    {
+        // pinned and device staging, once per context, sized for its batch: the header, then per request the longest row of
+        // any entry point (operands of compute_qmodel / results of the sub-problem) and its IpmState
+        if (!C.stg_h) {
+            const DV &d = C.d;
+            const long row = 3 * ev(d.n) + 4 * ev(d.m) + ev(d.nnzj_coo) + ev(d.nnzh_coo) + (long)(sizeof(IpmState) / 8) + 2;
+            C.stg_doubles = 3 * ev(d.B) + (long)d.B * row;
+            SQPHIP_HIP_OK(hipHostMalloc((void **)&C.stg_h, sizeof(double) * (size_t)C.stg_doubles));
+            C.stg_d = C.dalloc<double>((size_t)C.stg_doubles);
+        }
+    }
+    double *a0() { return C.stg_h; }
+    double *a1() { return C.stg_h + cp; }
+    int *inst() { return (int *)(C.stg_h + 2 * cp); }
+    int *mode() { return (int *)(C.stg_h + 2 * cp) + cp; }
+    const double *a0_dev() const { return C.stg_d; }
+    const double *a1_dev() const { return C.stg_d + cp; }
+    const int *inst_dev() const { return (const int *)(C.stg_d + 2 * cp); }
+    const int *mode_dev() const { return (const int *)(C.stg_d + 2 * cp) + cp; }
+    // an operand: [count][len] on the host (null with zero: the slots are cleared; null without: the field is left out)
+    void operand(const double *host, double *base, int len, bool zero = false)
+    {
+        if ((!host && !zero) || len == 0) return;
+        const int f = in.nf++;
+        in.len[f] = len; in.stride[f] = len; in.base[f] = base; src[f] = host;
+        in.off[f] = host ? in.row : -1;
+        if (host) in.row += (int)ev(len);
+    }
+    void result(double *base, int len)
+    {
+        if (len == 0) return;
+        const int f = out.nf++;
+        out.len[f] = len; out.stride[f] = len; out.base[f] = base; out.off[f] = out.row;
+        out.row += (int)ev(len);
+    }
+    static dim3 grid(const StageMap &M, int count) { return dim3((unsigned)std::min(32L, std::max(1L, (M.row / 2 + 255L) / 256)), (unsigned)count); }
+    // header and rows: packed on the host, one copy, one scatter kernel
+    void send(const int32_t *inst_host, const int32_t *mode_host, const double *a0_host, const double *a1_host)
+    {
+        for (int k = 0; k < count; ++k) {
+            a0()[k] = a0_host ? a0_host[k] : 0.0; a1()[k] = a1_host ? a1_host[k] : 0.0;
+            inst()[k] = inst_host[k]; mode()[k] = mode_host ? mode_host[k] : 0;
+        }
+        for (int k = 0; k < count; ++k)
+            for (int f = 0; f < in.nf; ++f)
+                if (src[f]) std::memcpy(C.stg_h + rows0 + (long)k * in.row + in.off[f], src[f] + (size_t)k * in.len[f], sizeof(double) * (size_t)in.len[f]);
+        SQPHIP_HIP_OK(hipMemcpyAsync(C.stg_d, C.stg_h, sizeof(double) * (size_t)(rows0 + (long)count * in.row), hipMemcpyHostToDevice, C.stream));
+        if (in.nf) hipLaunchKernelGGL(k_seat_stage<true>, grid(in, count), dim3(256), 0, C.stream, in, C.stg_d + rows0, inst_dev());
+    }
+    // results (and, with_states, the IpmState of the listed instances): one gather kernel, one copy back, then the host waits
+    long fetch(bool with_states, long extra = 0)
+    {
+        const long body = (long)count * out.row;
+        out.ist = with_states ? C.d.ist : nullptr; out.ist_off = body;
+        if (out.nf || with_states) hipLaunchKernelGGL(k_seat_stage<false>, grid(out, count), dim3(256), 0, C.stream, out, C.stg_d + rows0, inst_dev());
+        const long total = body + (with_states ? (long)count * (long)(sizeof(IpmState) / 8) : 0) + extra;
+        SQPHIP_HIP_OK(hipMemcpyAsync(C.stg_h + rows0, C.stg_d + rows0, sizeof(double) * (size_t)total, hipMemcpyDeviceToHost, C.stream));
+        SQPHIP_HIP_OK(hipStreamSynchronize(C.stream));
+        SQPHIP_HIP_OK(hipGetLastError());
+        return body;
+    }
+    void unpack(int f, double *host) const
+    {
+        if (!host) return;
+        for (int k = 0; k < count; ++k)
+            std::memcpy(host + (size_t)k * out.len[f], C.stg_h + rows0 + (long)k * out.row + out.off[f], sizeof(double) * (size_t)out.len[f]);
+    }
+    IpmState state(int k, long body) const
+    {
+        IpmState st;
+        std::memcpy(&st, (const char *)(C.stg_h + rows0 + body) + sizeof(IpmState) * (size_t)k, sizeof(IpmState));
+        return st;
+    }
+};
+
+}  // namespace
+
+extern "C" int sqphip_qp_solve_batch(sqphip_ctx *h, int32_t count, const int32_t *inst, const int32_t *mode, const double *x_k,
+                                     const double *delta, const double *mu, const double *df, const double *E,
+                                     const double *Jval, const double *Hval, double *p, double *lambda, double *mult_x_U,
+                                     double *mult_x_L, double *slack, int32_t *moi_status)
+{
+    if (!h || !mode || !x_k || !delta || !mu || !Jval || !p || !lambda || !mult_x_U || !mult_x_L || !moi_status) return SQPHIP_EINVAL;
+    if (int rc = seat_check(h, "sqphip_qp_solve_batch", count, inst)) return rc;
+    for (int k = 0; k < count; ++k) {
+        if (mode[k] < 0 || mode[k] > SQPHIP_MODE_INFEAS) { h->c.err = "sqphip_qp_solve_batch: mode[" + std::to_string(k) + "] = " + std::to_string(mode[k]) + " is no sub-problem mode"; return SQPHIP_EINVAL; }
+        if (mode[k] != SQPHIP_MODE_LP && (!df || !E)) { h->c.err = "sqphip_qp_solve_batch: mode[" + std::to_string(k) + "] needs df and E"; return SQPHIP_EINVAL; }
+    }
+    return guarded(h, [&](Ctx &C) {
+        DV &d = C.d;
+        auto t0 = std::chrono::steady_clock::now();
+        SeatCall S(C, count);
+        S.operand(x_k, d.xk, d.n); S.operand(df, d.cin, d.n); S.operand(E, d.bE, d.m);
+        S.operand(Jval, d.jcoo, d.nnzj_coo); S.operand(Hval, d.hcoo, d.nnzh_coo, true);
+        S.send(inst, mode, delta, mu);
+        hipLaunchKernelGGL(k_qp_request_batch, dim3(1), dim3(256), 0, C.stream, d, (int)count, S.inst_dev(), S.mode_dev(), S.a0_dev(), S.a1_dev());
+        launch_qp_gather(C);
+        ipm_run_all(C);
+        S.result(d.op, d.n); S.result(d.olam, d.m); S.result(d.omxU, d.n); S.result(d.omxL, d.n); S.result(d.oslack, 2 * d.m);
+        const long body = S.fetch(true);
+        int f = 0;
+        S.unpack(f++, p);
+        if (d.m) S.unpack(f++, lambda);
+        S.unpack(f++, mult_x_U); S.unpack(f++, mult_x_L);
+        if (d.m) S.unpack(f++, slack);
+        for (int k = 0; k < count; ++k) {
+            const IpmState st = S.state(k, body);
+            moi_status[k] = st.status;
+            C.last_ipm_iters = st.ipm_iters; C.last_n_factor = st.n_factor;
+            C.last_rule = st.rc == 0 ? st.acc_rule : -1; C.last_e0 = st.e0;
+            C.n_qp += 1; C.n_ipm_iter += st.ipm_iters; C.n_factor += st.n_factor; C.n_solve += st.n_solve;
+        }
+        C.total_seconds += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+        return SQPHIP_OK;
+    });
+}
+
+extern "C" int sqphip_qp_stats_batch(const sqphip_ctx *hc, int32_t count, const int32_t *inst, int32_t *ipm_iters,
+                                     int32_t *n_factor, int32_t *rule, double *scaled_error)
+{
+    sqphip_ctx *h = const_cast<sqphip_ctx *>(hc);       // (reads the states from the device: the stream and the staging are used)
+    if (!h) return SQPHIP_EINVAL;
+    if (int rc = seat_check(h, "sqphip_qp_stats_batch", count, inst)) return rc;
+    return guarded(h, [&](Ctx &C) {
+        SeatCall S(C, count);
+        S.send(inst, nullptr, nullptr, nullptr);
+        const long body = S.fetch(true);
+        for (int k = 0; k < count; ++k) {
+            const IpmState st = S.state(k, body);
+            if (ipm_iters) ipm_iters[k] = st.ipm_iters;
+            if (n_factor) n_factor[k] = st.n_factor;
+            if (rule) rule[k] = st.rc == 0 ? st.acc_rule : -1;
+            if (scaled_error) scaled_error[k] = st.e0;
+        }
+        return SQPHIP_OK;
+    });
+}
+
+// test hook: the sub-problem outputs instance `inst` holds on the device (what the seat returned for it last)
+extern "C" int sqphip_seat_peek(sqphip_ctx *h, int32_t inst, double *p, double *lambda, double *mult_x_U, double *mult_x_L,
+                                double *slack, int32_t *moi_status)
+{
+    if (!h || inst < 0 || inst >= h->c.d.B) return SQPHIP_EINVAL;
+    return guarded(h, [&](Ctx &C) {
+        DV &d = C.d;
+        d2h(C, p, d.op + (size_t)inst * d.n, d.n); d2h(C, lambda, d.olam + (size_t)inst * d.m, d.m);
+        d2h(C, mult_x_U, d.omxU + (size_t)inst * d.n, d.n); d2h(C, mult_x_L, d.omxL + (size_t)inst * d.n, d.n);
+        d2h(C, slack, d.oslack + 2 * (size_t)inst * d.m, 2 * (size_t)d.m);
+        IpmState st;
+        SQPHIP_HIP_OK(hipMemcpyAsync(&st, d.ist + inst, sizeof(IpmState), hipMemcpyDeviceToHost, C.stream));
+        SQPHIP_HIP_OK(hipStreamSynchronize(C.stream));
+        if (moi_status) *moi_status = st.status;
+        return SQPHIP_OK;
+    });
+}
+
 // ---- merit path -------------------------------------------------------------------------------
 extern "C" int sqphip_norm_violations(sqphip_ctx *h, const double *E, const double *x, int32_t pnorm, double *out)
 {
@@ -776,6 +1025,93 @@ extern "C" int sqphip_compute_derivative_full(sqphip_ctx *h, const double *df, c
         if (mu_vec) h2d(C, d.plam, mu_vec, d.m);
         merit_eval(C, 6, 0.0, mu, (feasibility_restoration ? 1 : 0) | (mu_vec ? 2 : 0), D);
         return SQPHIP_OK;
+    });
+}
+
+// ---- merit path of the batched seat: operands of request k staged into the vectors of instance inst[k], one workgroup
+// of k_merit_batch per request with the arithmetic of k_merit (sqp.hip, merit_body), out[count]
+namespace {
+template <class Stage>
+int merit_batch(sqphip_ctx *h, const char *fn, int32_t count, const int32_t *inst, int op, const double *a0, const double *a1,
+                int flag, double *out, Stage &&stage)
+{
+    if (int rc = seat_check(h, fn, count, inst)) return rc;
+    return guarded(h, [&](Ctx &C) {
+        SeatCall S(C, count);
+        stage(S, C.d);
+        S.send(inst, nullptr, a0, a1);
+        double *o = C.stg_d + S.rows0;                    // (the rows have been spread by then: same stream)
+        merit_eval_batch(C, count, S.inst_dev(), op, S.a0_dev(), S.a1_dev(), flag, o);
+        S.fetch(false, count);
+        std::memcpy(out, C.stg_h + S.rows0, sizeof(double) * (size_t)count);
+        return SQPHIP_OK;
+    });
+}
+}  // namespace
+
+extern "C" int sqphip_norm_violations_batch(sqphip_ctx *h, int32_t count, const int32_t *inst, const double *E, const double *x,
+                                            int32_t pnorm, double *out)
+{
+    if (!h || !E || !x || !out || pnorm < 0 || pnorm > 2) return SQPHIP_EINVAL;
+    return merit_batch(h, "sqphip_norm_violations_batch", count, inst, 0, nullptr, nullptr, pnorm, out,
+                       [&](SeatCall &S, DV &d) { S.operand(E, d.E, d.m); S.operand(x, d.x, d.n); });
+}
+
+extern "C" int sqphip_kt_residuals_batch(sqphip_ctx *h, int32_t count, const int32_t *inst, const double *df,
+                                         const double *lambda, const double *mult_x_U, const double *mult_x_L,
+                                         const double *Jval, double *out)
+{
+    if (!h || !df || !lambda || !mult_x_U || !mult_x_L || !Jval || !out) return SQPHIP_EINVAL;
+    return merit_batch(h, "sqphip_kt_residuals_batch", count, inst, 1, nullptr, nullptr, 0, out, [&](SeatCall &S, DV &d) {
+        S.operand(df, d.df, d.n); S.operand(lambda, d.lambda, d.m); S.operand(mult_x_U, d.mxU, d.n);
+        S.operand(mult_x_L, d.mxL, d.n); S.operand(Jval, d.jcoo, d.nnzj_coo);
+    });
+}
+
+extern "C" int sqphip_norm_complementarity_batch(sqphip_ctx *h, int32_t count, const int32_t *inst, const double *E,
+                                                 const double *lambda, int32_t pnorm, double *out)
+{
+    if (!h || !E || !lambda || !out || pnorm < 0 || pnorm > 2) return SQPHIP_EINVAL;
+    return merit_batch(h, "sqphip_norm_complementarity_batch", count, inst, 2, nullptr, nullptr, pnorm, out,
+                       [&](SeatCall &S, DV &d) { S.operand(E, d.E, d.m); S.operand(lambda, d.lambda, d.m); });
+}
+
+extern "C" int sqphip_compute_phi_batch(sqphip_ctx *h, int32_t count, const int32_t *inst, const double *f_trial,
+                                        const double *E_trial, const double *x_trial, const double *mu,
+                                        int32_t feasibility_restoration, double *phi)
+{
+    if (!h || !f_trial || !E_trial || !x_trial || !mu || !phi) return SQPHIP_EINVAL;
+    return merit_batch(h, "sqphip_compute_phi_batch", count, inst, 3, f_trial, mu, feasibility_restoration, phi,
+                       [&](SeatCall &S, DV &d) { S.operand(E_trial, d.E, d.m); S.operand(x_trial, d.x, d.n); });
+}
+
+extern "C" int sqphip_compute_qmodel_batch(sqphip_ctx *h, int32_t count, const int32_t *inst, const double *x, const double *p,
+                                           const double *df, const double *E, const double *Jval, const double *Hval,
+                                           const double *mu, int32_t with_step, double *q)
+{
+    if (!h || !x || !E || !mu || !q) return SQPHIP_EINVAL;
+    if (with_step && (!p || !df || !Jval)) return SQPHIP_EINVAL;
+    return merit_batch(h, "sqphip_compute_qmodel_batch", count, inst, 4, nullptr, mu, with_step, q, [&](SeatCall &S, DV &d) {
+        S.operand(x, d.x, d.n); S.operand(E, d.E, d.m);
+        if (with_step) {
+            S.operand(p, d.pstep, d.n); S.operand(df, d.df, d.n); S.operand(Jval, d.jcoo, d.nnzj_coo);
+            S.operand(Hval, d.hcoo, d.nnzh_coo, true);
+        }
+    });
+}
+
+extern "C" int sqphip_compute_derivative_full_batch(sqphip_ctx *h, int32_t count, const int32_t *inst, const double *df,
+                                                    const double *p, const double *E, const double *mu, const double *mu_vec,
+                                                    int32_t feasibility_restoration, const double *slack, double *D)
+{
+    if (!h || !E || !mu || !D) return SQPHIP_EINVAL;
+    if (feasibility_restoration ? !slack : (!df || !p)) return SQPHIP_EINVAL;
+    return merit_batch(h, "sqphip_compute_derivative_full_batch", count, inst, 6, nullptr, mu,
+                       (feasibility_restoration ? 1 : 0) | (mu_vec ? 2 : 0), D, [&](SeatCall &S, DV &d) {
+        S.operand(E, d.E, d.m);
+        if (feasibility_restoration) S.operand(slack, d.oslack, 2 * d.m);
+        else { S.operand(df, d.df, d.n); S.operand(p, d.pstep, d.n); }
+        S.operand(mu_vec, d.plam, d.m);
     });
 }
 

@@ -252,6 +252,10 @@ struct Ctx {
     std::string err;
     hipStream_t stream = nullptr;
     int *h_counters = nullptr;  // pinned
+    // staging of the batched seat (sqphip_*_batch, api.hip SeatCall): pinned host and device buffer of stg_doubles, allocated at the
+    // first batch call and sized for the batch
+    double *stg_h = nullptr, *stg_d = nullptr;
+    long stg_doubles = 0;
     std::vector<int> h_kpos;    // host copy of DV::kpos (row -> kept position or -1)
     std::vector<int64_t> h_jrow, h_jcol, h_hrow, h_hcol;   // host copies of the COO structures of sqphip_create (1-based)
     long qc_nv = 0;             // doubles per instance of an attached QCQP (DV::qcv; even: the blocks are 16-byte aligned) ...
@@ -314,6 +318,9 @@ void launch_acopf_eval_point(Ctx &C, int inst, const double *x_dev, double sigma
 void sqp_reset(Ctx &C);
 void sqp_run(Ctx &C, int max_outer);
 void merit_eval(Ctx &C, int op, double a0, double a1, int flag, double *out_host);
+// ... for request k = 0 .. count - 1 on instance inst_dev[k] with a0_dev[k], a1_dev[k]; out_dev[count]; device pointers, no copy, no wait
+void merit_eval_batch(Ctx &C, int count, const int *inst_dev, int op, const double *a0_dev, const double *a1_dev, int flag,
+                      double *out_dev);
 void armijo_eval(Ctx &C, int inst, double mu, double phi0, double D, double eta, double tau, double min_alpha, int fr,
                  double *out3_host);
 

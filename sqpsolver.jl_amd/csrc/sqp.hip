@@ -749,9 +749,10 @@ void sqp_stage_kernels(Ctx &C, hipStream_t s, const DV &d)          // called fr
 //   op 0 norm_violations (common.jl:54-77)      op 1 KT_residuals (common.jl:14-23)
 //   op 2 norm_complementarity (common.jl:30-47) op 3 compute_phi (sqp.jl:170-183)
 //   op 4 compute_qmodel (sqp_trust_region.jl:487-508)  op 5 compute_derivative (merit.jl:15, sqp.jl:203-212)
-__global__ __launch_bounds__(TPB) void k_merit(DV d, int op, double a0, double a1, int flag, double *out)
+// The operands are those of instance `inst` (0 for the scalar entry points, inst[k] for request k of the batch forms): one
+// body for both kernels, so that a batched result is the scalar one bit for bit.
+static __device__ __forceinline__ double merit_body(const DV &d, const int inst, int op, double a0, double a1, int flag)
 {
-    const int inst = 0;
     SQP_PTRS
     double r = 0.0;
     if (op == 0 || op == 2) {
@@ -806,7 +807,7 @@ __global__ __launch_bounds__(TPB) void k_merit(DV d, int op, double a0, double a
         // compute_derivative(sqp), sqp.jl:190-213 over merit.jl:13-17.  flag bit 0: feasibility restoration (dfp =
         // sum of the slacks staged in oslack), bit 1: vector penalty staged in plam
         const bool fr = flag & 1, vec = flag & 2;
-        const double *slack = d.oslack;
+        const double *slack = d.oslack + 2 * om;
         double dfp = 0.0, cv = 0.0;
         if (fr) { for (int k = threadIdx.x; k < 2 * d.m; k += TPB) dfp += slack[k]; }
         else for (int j = threadIdx.x; j < d.n; j += TPB) dfp += df[j] * ps[j];
@@ -841,7 +842,22 @@ __global__ __launch_bounds__(TPB) void k_merit(DV d, int op, double a0, double a
         }
         r = t;
     }
+    return r;
+}
+
+__global__ __launch_bounds__(TPB) void k_merit(DV d, int op, double a0, double a1, int flag, double *out)
+{
+    const double r = merit_body(d, 0, op, a0, a1, flag);
     if (threadIdx.x == 0) *out = r;
+}
+
+// one workgroup per request of a batch call (sqphip_*_batch): instance table, per-request scalars (null: 0), out[count]
+__global__ __launch_bounds__(TPB) void k_merit_batch(DV d, const int *inst, int op, const double *a0, const double *a1, int flag,
+                                                     double *out)
+{
+    const int k = blockIdx.x;
+    const double r = merit_body(d, inst[k], op, a0 ? a0[k] : 0.0, a1 ? a1[k] : 0.0, flag);
+    if (threadIdx.x == 0) out[k] = r;
 }
 
 // compute_alpha (sqp_line_search.jl:303-334) on the device: x and p of instance `inst` are staged in d.x / d.pstep;
@@ -918,6 +934,12 @@ void merit_eval(Ctx &C, int op, double a0, double a1, int flag, double *out_host
     hipLaunchKernelGGL(k_merit, dim3(1), dim3(TPB), 0, C.stream, C.d, op, a0, a1, flag, o);
     SQPHIP_HIP_OK(hipMemcpyAsync(out_host, o, sizeof(double), hipMemcpyDeviceToHost, C.stream));
     SQPHIP_HIP_OK(hipStreamSynchronize(C.stream));
+}
+
+void merit_eval_batch(Ctx &C, int count, const int *inst_dev, int op, const double *a0_dev, const double *a1_dev, int flag,
+                      double *out_dev)
+{
+    hipLaunchKernelGGL(k_merit_batch, dim3(count), dim3(TPB), 0, C.stream, C.d, inst_dev, op, a0_dev, a1_dev, flag, out_dev);
 }
 
 }  // namespace sqphip

@@ -5,7 +5,8 @@ library through the `ccall` shim of julia/SqpHip.jl.  No Julia 
 the same thin layer is written here in Python over ctypes with the reference's names, argument meaning and error
 behaviour:
 
-    Context         one sqphip_ctx: every entry point of include/sqphip.h
+    Context         one sqphip_ctx: every entry point of include/sqphip.h (the *_batch methods: many host models on the
+                    instances of one context, one call per round)
     QpData          /root/reference/src/algorithms/subproblem.jl:12-23
     QpHip           the `AbstractSubOptimizer` seat (subproblem.jl:1), API of QpJuMP:
                     sub_optimize / sub_optimize_FR / sub_optimize_lp / sub_optimize_L1QP /
@@ -186,6 +187,117 @@ class Context:
         self.L.sqphip_qp_termination(self.h, C.byref(rule), C.byref(err))
         return dict(p=p, lam=lam, mult_x_U=mu_u, mult_x_L=mu_l, slack=slack, status=st.value,
                     ipm_iters=it.value, n_factor=nf.value, term_rule=rule.value, scaled_error=err.value)
+
+    # ---- the seat for many host models at once (sqphip_*_batch): request k runs on instance inst[k]
+    def _insts(self, inst):
+        a = np.ascontiguousarray(inst, dtype=np.int32)
+        if a.ndim != 1 or len(a) == 0:
+            raise ValueError("inst must be a non-empty list of instance numbers")
+        return a
+
+    @staticmethod
+    def _rows(name, rows, count, width):
+        """[count][width] float64, contiguous, from a sequence of `count` vectors; None stays None.  Ragged or mis-sized
+        input is refused here, before the library sees a pointer."""
+        if rows is None:
+            return None
+        rows = list(rows) if not isinstance(rows, np.ndarray) else rows
+        if len(rows) != count:
+            raise ValueError(f"{name}: {len(rows)} rows for {count} requests")
+        for k, r in enumerate(rows):
+            if r is None or np.ndim(r) != 1 or len(r) != width:
+                raise ValueError(f"{name}[{k}]: expected a vector of length {width}")
+        return np.ascontiguousarray(np.asarray(rows, dtype=np.float64).reshape(count, width))
+
+    @staticmethod
+    def _scalars(name, v, count):
+        a = np.ascontiguousarray(np.broadcast_to(np.asarray(v, dtype=np.float64), (count,)) if np.ndim(v) == 0 else v,
+                                 dtype=np.float64)
+        if a.shape != (count,):
+            raise ValueError(f"{name}: expected {count} values")
+        return a
+
+    def qp_solve_batch(self, inst, mode, x_k, delta, mu, df, E, jval, hval):
+        """`sqphip_qp_solve_batch`: one call for len(inst) sub-problems; returns the dicts of qp_solve in request order."""
+        ins = self._insts(inst); cnt = len(ins)
+        md = np.ascontiguousarray(mode, dtype=np.int32)
+        if md.shape != (cnt,):
+            raise ValueError(f"mode: expected {cnt} values")
+        dl, pen = self._scalars("delta", delta, cnt), self._scalars("mu", mu, cnt)
+        xk = self._rows("x_k", x_k, cnt, self.n); c = self._rows("df", df, cnt, self.n); b = self._rows("E", E, cnt, self.m)
+        jv = self._rows("jval", jval, cnt, self.nnzj)
+        hv = self._rows("hval", hval, cnt, self.nnzh) if hval is not None and self.nnzh and all(h is not None for h in hval) else None
+        if hval is not None and self.nnzh and hv is None and any(h is not None for h in hval):
+            raise ValueError("hval: given for some requests only")
+        p = np.zeros((cnt, self.n)); lam = np.zeros((cnt, self.m)); mu_u = np.zeros((cnt, self.n)); mu_l = np.zeros((cnt, self.n))
+        slack = np.zeros((cnt, 2 * self.m)); st = np.zeros(cnt, dtype=np.int32)
+        self._ck(self.L.sqphip_qp_solve_batch(self.h, cnt, _i(ins), _i(md), _d(xk), _d(dl), _d(pen), _d(c), _d(b), _d(jv), _d(hv),
+                                              _d(p), _d(lam), _d(mu_u), _d(mu_l), _d(slack), _i(st)))
+        stats = self.qp_stats_batch(ins)
+        return [dict(p=p[k].copy(), lam=lam[k].copy(), mult_x_U=mu_u[k].copy(), mult_x_L=mu_l[k].copy(), slack=slack[k].copy(),
+                     status=int(st[k]), **stats[k]) for k in range(cnt)]
+
+    def qp_stats_batch(self, inst):
+        """`sqphip_qp_stats_batch`: per listed instance the ipm_iters, n_factor, term_rule, scaled_error of its last sub-problem."""
+        ins = self._insts(inst); cnt = len(ins)
+        it = np.zeros(cnt, dtype=np.int32); nf = np.zeros(cnt, dtype=np.int32); rule = np.zeros(cnt, dtype=np.int32); err = np.zeros(cnt)
+        self._ck(self.L.sqphip_qp_stats_batch(self.h, cnt, _i(ins), _i(it), _i(nf), _i(rule), _d(err)))
+        return [dict(ipm_iters=int(it[k]), n_factor=int(nf[k]), term_rule=int(rule[k]), scaled_error=float(err[k])) for k in range(cnt)]
+
+    def seat_peek(self, inst):
+        """Test hook `sqphip_seat_peek`: the seat's output slots of one instance as the device holds them."""
+        p = np.zeros(self.n); lam = np.zeros(self.m); mu_u = np.zeros(self.n); mu_l = np.zeros(self.n); slack = np.zeros(2 * self.m)
+        st = C.c_int32()
+        self._ck(self.L.sqphip_seat_peek(self.h, int(inst), _d(p), _d(lam), _d(mu_u), _d(mu_l), _d(slack), C.byref(st)))
+        return dict(p=p, lam=lam, mult_x_U=mu_u, mult_x_L=mu_l, slack=slack, status=st.value)
+
+    _PN = {1: 1, 2: 2, math.inf: 0, "inf": 0}
+
+    def norm_violations_batch(self, inst, E, x, p=1):
+        ins = self._insts(inst); cnt = len(ins); out = np.zeros(cnt)
+        self._ck(self.L.sqphip_norm_violations_batch(self.h, cnt, _i(ins), _d(self._rows("E", E, cnt, self.m)),
+                                                     _d(self._rows("x", x, cnt, self.n)), self._PN[p], _d(out)))
+        return out
+
+    def kt_residuals_batch(self, inst, df, lam, mult_x_U, mult_x_L, jval):
+        ins = self._insts(inst); cnt = len(ins); out = np.zeros(cnt)
+        self._ck(self.L.sqphip_kt_residuals_batch(self.h, cnt, _i(ins), _d(self._rows("df", df, cnt, self.n)),
+                                                  _d(self._rows("lam", lam, cnt, self.m)),
+                                                  _d(self._rows("mult_x_U", mult_x_U, cnt, self.n)),
+                                                  _d(self._rows("mult_x_L", mult_x_L, cnt, self.n)),
+                                                  _d(self._rows("jval", jval, cnt, self.nnzj)), _d(out)))
+        return out
+
+    def norm_complementarity_batch(self, inst, E, lam, p=math.inf):
+        ins = self._insts(inst); cnt = len(ins); out = np.zeros(cnt)
+        self._ck(self.L.sqphip_norm_complementarity_batch(self.h, cnt, _i(ins), _d(self._rows("E", E, cnt, self.m)),
+                                                          _d(self._rows("lam", lam, cnt, self.m)), self._PN[p], _d(out)))
+        return out
+
+    def compute_phi_batch(self, inst, f_trial, E_trial, x_trial, mu, fr):
+        ins = self._insts(inst); cnt = len(ins); out = np.zeros(cnt)
+        self._ck(self.L.sqphip_compute_phi_batch(self.h, cnt, _i(ins), _d(self._scalars("f_trial", f_trial, cnt)),
+                                                 _d(self._rows("E_trial", E_trial, cnt, self.m)),
+                                                 _d(self._rows("x_trial", x_trial, cnt, self.n)),
+                                                 _d(self._scalars("mu", mu, cnt)), int(fr), _d(out)))
+        return out
+
+    def compute_qmodel_batch(self, inst, x, p, df, E, jval, hval, mu, with_step):
+        ins = self._insts(inst); cnt = len(ins); out = np.zeros(cnt)
+        hv = self._rows("hval", hval, cnt, self.nnzh) if hval is not None and self.nnzh and all(h is not None for h in hval) else None
+        self._ck(self.L.sqphip_compute_qmodel_batch(self.h, cnt, _i(ins), _d(self._rows("x", x, cnt, self.n)),
+                                                    _d(self._rows("p", p, cnt, self.n)), _d(self._rows("df", df, cnt, self.n)),
+                                                    _d(self._rows("E", E, cnt, self.m)), _d(self._rows("jval", jval, cnt, self.nnzj)),
+                                                    _d(hv), _d(self._scalars("mu", mu, cnt)), int(with_step), _d(out)))
+        return out
+
+    def compute_derivative_full_batch(self, inst, df, p, E, mu, mu_vec=None, feasibility_restoration=False, slack=None):
+        ins = self._insts(inst); cnt = len(ins); out = np.zeros(cnt)
+        self._ck(self.L.sqphip_compute_derivative_full_batch(
+            self.h, cnt, _i(ins), _d(self._rows("df", df, cnt, self.n)), _d(self._rows("p", p, cnt, self.n)),
+            _d(self._rows("E", E, cnt, self.m)), _d(self._scalars("mu", mu, cnt)), _d(self._rows("mu_vec", mu_vec, cnt, self.m)),
+            int(feasibility_restoration), _d(self._rows("slack", slack, cnt, 2 * self.m)), _d(out)))
+        return out
 
     def compute_derivative_full(self, df, p, E, mu, mu_vec=None, feasibility_restoration=False, slack=None):
         """compute_derivative(sqp) of sqp.jl:190-213 over merit.jl:13-17 (vector penalty, restoration branch)."""
@@ -591,3 +703,21 @@ class QpHip:
     def sub_optimize_lp(self, x_k):
         p, lam, mu_u, mu_l, _, st = self._solve(MODE_LP, x_k, math.inf)
         return p, lam, mu_u, mu_l, st
+
+    # ---- many models at once: lists of QpData (one per request) on the instances `inst` of the context
+    def _solve_batch(self, inst, mode, datas, x_k, delta, mu=1.0):
+        cnt = len(datas)
+        hv = None if any(d.Q is None for d in datas) else [d.Q for d in datas]
+        rs = self.ctx.qp_solve_batch(inst, [mode] * cnt, x_k, delta, mu, [d.c for d in datas], [d.b for d in datas],
+                                     [d.A for d in datas], hv)
+        return [(r["p"], r["lam"], r["mult_x_U"], r["mult_x_L"], r["slack"], r["status"]) for r in rs]
+
+    def sub_optimize_batch(self, inst, datas, x_k, delta):
+        return self._solve_batch(inst, MODE_QP, datas, x_k, delta)
+
+    def sub_optimize_FR_batch(self, inst, datas, x_k, delta):
+        return self._solve_batch(inst, MODE_FR, datas, x_k, delta)
+
+    def sub_optimize_lp_batch(self, inst, datas, x_k):
+        return [(p, lam, mu_u, mu_l, st) for p, lam, mu_u, mu_l, _, st in
+                self._solve_batch(inst, MODE_LP, datas, x_k, math.inf)]
