@@ -880,6 +880,8 @@ static int ipm_run(ora_qp *q, const double *p_start, const double *y_start)
     double *soc = mpc ? (double *)calloc((size_t)(2 * n + 4 * m + 1), sizeof(double)) : NULL;
     int verbose = getenv("ORA_IPM_VERBOSE") != NULL;
     const int eq_steps = getenv("ORA_EQ_STEPS") ? atoi(getenv("ORA_EQ_STEPS")) : 0;
+    double e_best = INFINITY;       /* stall guard of the predictor-corrector mode: best scaled error so far, ... */
+    int n_stall = 0;                /* ... iterations in a row that did not improve on it by 10 % */
     int short_lim = 0, n_short = 0;
     double short_a = 0.1;
     double short_dw = 0.0;
@@ -909,6 +911,17 @@ static int ipm_run(ora_qp *q, const double *p_start, const double *y_start)
          * sub-problems: same iteration and factorisation counts with and without it); same rule in ipm.hip (b_ipm_prepare) */
         n_acc3 = e0 <= 1e4 * tol ? n_acc3 + 1 : 0;
         if (n_acc >= 8 || n_acc2 >= 15 || n_acc3 >= 25) { rc = 0; q->last_rule = n_acc >= 8 ? 1 : (n_acc2 >= 15 ? 2 : 3); break; }
+        /* predictor-corrector mode, stall guard: Mehrotra's rule with separate primal and dual step lengths has no
+         * convergence proof on a QP and can cycle (a one-variable programme whose start sits 0.01 from its upper bound
+         * with a multiplier of 100 there repeats four iterates for ever: tests/test_planted_qps_cpu.py).  Eight iterations
+         * in a row that do not bring the scaled error 10 % below its best value so far end the mode, like an inertia
+         * correction does: the monotone rule from the current average complementarity.  Converged runs of every test
+         * problem have at most four such iterations in a row, so their iterates are unchanged.  Same rule in ipm.hip
+         * (b_ipm_prepare). */
+        if (mpc) {
+            if (e0 < 0.9 * e_best) { e_best = e0; n_stall = 0; }
+            else if (++n_stall >= 8) { mpc = 0; mu = fmax(mu_min, fmin(1.0, ms.cavg)); }
+        }
         /* barrier update */
         for (int k = 0; k < 20 && !mpc; ++k) {
             double emu = fmax(fmax(ms.rd / sd, ms.rp), ipm_compl_err(q, mu) / sd);

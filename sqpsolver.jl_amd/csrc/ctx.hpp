@@ -46,6 +46,8 @@ struct IpmState {
     int iter, rc, fac_attempt, dir_attempt, refine_it, n_acc, n_acc2, n_acc3;
     int mpc, use_soc;              // predictor-corrector mode of this solve; second-order terms valid for the step
     double cavg;                   // average complementarity at the top of the iteration
+    double e_best;                 // predictor-corrector mode, stall guard (b_ipm_prepare): best scaled error of this run so far, ...
+    int n_stall;                   // ... iterations in a row that did not improve on it by 10 %
     // outcome
     int prev_mode;                 // 1 + mode of this instance's last solved sub-problem (options.ipm_warm_start), 0 none
     int status, ipm_iters, n_factor, n_solve;   // n_solve: forward + backward solves with the factors (incl. refinement)

@@ -292,6 +292,7 @@ static __device__ void b_ipm_start(const DV &d)
         st.dw_last = 0.0;
         st.cn = 0.0;
         st.mpc = d.ipm_corrector != 0; st.use_soc = 0; st.cavg = 0.0;
+        st.e_best = INFINITY; st.n_stall = 0;
         st.start = 0;
         d.phase[inst] = ph_prep(d);
     }
@@ -312,6 +313,8 @@ static __device__ void b_ipm_prepare(const DV &d)
     }
     const double hsc = st.hsc;
     const int n_acc_prev = st.n_acc, n_acc2_prev = st.n_acc2, n_acc3_prev = st.n_acc3;   // read here: thread 0 updates them below, after the reductions' barriers
+    const int mpc_prev = st.mpc, n_stall_prev = st.n_stall;                               // (the same)
+    const double e_best_prev = st.e_best;
     VTR(16)
     const double *pv = p, *yv = y;
     if (d.vstage) {                                  // p and y are gathered from below: LDS copies
@@ -407,10 +410,20 @@ static __device__ void b_ipm_prepare(const DV &d)
     // barrier update: mu <- max(mu_min, min(0.2 mu, mu^1.5)) while the barrier problem is solved
     double mu = st.mu;
     const double mu_min = d.ipm_tol / 10.0;
-    const int mpc = st.mpc;           // predictor-corrector mode picks mu after the predictor (k_mpc)
+    int mpc = mpc_prev;               // predictor-corrector mode picks mu after the predictor (k_mpc)
+    // ... unless it stalls: eight iterations in a row that do not bring the scaled error 10 % below its best value so far end
+    // the mode as an inertia correction does (b_mpc) -- the monotone rule from the current average complementarity.  Mehrotra's
+    // rule with separate primal and dual step lengths can cycle on a QP (oracle/qp_ipm.c, ipm_run, has the programme)
+    int n_stall = n_stall_prev;
+    double e_best = e_best_prev;
+    bool stalled = false;
+    if (mpc) {
+        if (e0 < 0.9 * e_best) { e_best = e0; n_stall = 0; }
+        else if (++n_stall >= 8) { mpc = 0; stalled = true; mu = fmax(mu_min, fmin(1.0, cavg)); }
+    }
     for (int kk = 0; kk < 20 && !mpc; ++kk) {
         double ce = ce0;                 // first pass: taken with the residual loops above (mu is still the value they used)
-        if (kk > 0) {
+        if (kk > 0 || stalled) {
             ce = 0.0;
             for (int j = threadIdx.x; j < d.n; j += TPB) {
                 if (fin(lb[j])) ce = fmax(ce, compl_err(zl[j], p[j] - lb[j], mu));
@@ -433,6 +446,7 @@ static __device__ void b_ipm_prepare(const DV &d)
     }
     if (threadIdx.x == 0) {
         st.mu = mu; st.tau = fmax(0.99, 1.0 - mu); st.e0 = e0; st.cavg = cavg; st.use_soc = 0;
+        st.mpc = mpc; st.e_best = e_best; st.n_stall = n_stall;
         st.ipm_iters++;
         // st.dw still holds the correction the previous iteration of this solve ended with: if it needed one,
         // skip the zero trial and start from a third of it
