@@ -50,6 +50,10 @@ int sqphip_mf_batch_test(sqphip_ctx *ctx, const int32_t *active, const double *J
 /* Launch census of the multifrontal path: launches enqueued per kernel instantiation (factor, solve, inertia test) since the
  * context was created.  counts[cap]; names (may be null): cap x 64 characters; *n_kernels = number of instantiations. */
 int sqphip_mf_census(const sqphip_ctx *ctx, int64_t *counts, char *names, int32_t cap, int32_t *n_kernels);
+/* Transition launch groups in line: how many sweeps, summed over the instance groups of the context, have launched the three
+ * transition kernels (k_qp_finish, k_sqp_stage, k_ipm_head) themselves since the context was created.  With the transitions
+ * riding in the post launch (SQPHIP_TRANS_RIDE) that is the first sweep of every run of every group and no other. */
+int sqphip_trans_inline_groups(const sqphip_ctx *ctx, int64_t *count);
 /* Host-only (no GPU): the shape of the multifrontal plan sqphip_create builds for the structure, condense option and batch
  * (and the SQPHIP_MF_SMALL_FRONT / _ZERO_FRAC / _ROWS_AFTER overrides it reads): fronts[cap_fronts][3] = (columns, rows,
  * level), launches[cap_launches][4] = factor launches (level, tiles of the kernel, fronts, tiles of the smallest front);

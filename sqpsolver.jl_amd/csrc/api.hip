@@ -121,6 +121,7 @@ void make_lanes(Ctx &C)
 {
     for (const auto &L : C.lanes)           // (the launch census of the groups being replaced stays with the context)
         for (int k = 0; k < MFK_COUNT; ++k) C.mf_census[k] += L->mf_census[k];
+    for (const auto &L : C.lanes) C.n_trans_inline += L->n_trans_inline;
     C.lanes.clear();
     int G = 1;
     // (round 3, with the shorter solve kernels: four groups from 64 instances on -- 64 resident scenarios 1 955 -> 2 015 QP/s;
@@ -140,7 +141,7 @@ void make_lanes(Ctx &C)
         L->is_lane = true;
         L->opt = C.opt; L->n = C.n; L->m = C.m; L->acopf_attached = C.acopf_attached;
         L->mfp_ = C.mfp_;
-        L->trans_period = C.trans_period; L->refine_slot = C.refine_slot; L->refine_period = C.refine_period; L->mf_big_lds = C.mf_big_lds; L->post_split = C.post_split; L->side_mode = C.side_mode; L->spec_tail = C.spec_tail; L->spec_mode0 = C.spec_mode0;
+        L->trans_period = C.trans_period; L->trans_ride = C.trans_ride; L->refine_slot = C.refine_slot; L->refine_period = C.refine_period; L->mf_big_lds = C.mf_big_lds; L->post_split = C.post_split; L->side_mode = C.side_mode; L->spec_tail = C.spec_tail; L->spec_mode0 = C.spec_mode0;
         L->d = group_view(C.d, lo, hi - lo, g);
         if (L->d.qcv) L->d.qcv += (long)lo * C.qc_nv;
         // the first group runs on the owner's stream (idle during sqphip_sqp_run): HIP maps streams onto four hardware
@@ -507,6 +508,7 @@ extern "C" int sqphip_create(sqphip_ctx **out, int64_t n, int64_t m, int64_t num
         }
         SQPHIP_HIP_OK(hipStreamSynchronize(C.stream));
         if (const char *e = getenv("SQPHIP_TRANS_PERIOD")) C.trans_period = atoi(e);      // experiment switch, read once per context
+        if (const char *e = getenv("SQPHIP_TRANS_RIDE")) C.trans_ride = atoi(e);      // transitions inside the post launch (ctx.hpp): 0 off, 1 one ride, 2 two
         C.refine_slot = getenv("SQPHIP_REFINE_SLOT") && atoi(getenv("SQPHIP_REFINE_SLOT")) == 1;      // the second solve chain of a sweep (ipm_sweep)
         if (const char *e = getenv("SQPHIP_REFINE_PERIOD")) C.refine_period = atoi(e);      // experiment switch
         if (d.sparse) mf_device_setup(C);
@@ -732,6 +734,16 @@ extern "C" int sqphip_mf_census(const sqphip_ctx *h, int64_t *counts, char *name
         counts[k] = c;
         if (names) { std::strncpy(names + 64 * (size_t)k, mf_kernel_names[k], 63); names[64 * (size_t)k + 63] = 0; }
     }
+    return SQPHIP_OK;
+}
+
+// Sweeps that launched the three transition kernels in line since the context was created, summed over its instance groups.
+extern "C" int sqphip_trans_inline_groups(const sqphip_ctx *h, int64_t *count)
+{
+    if (!h || !count) return SQPHIP_EINVAL;
+    long c = h->c.n_trans_inline;
+    for (const auto &L : h->c.lanes) c += L->n_trans_inline;
+    *count = c;
     return SQPHIP_OK;
 }
 

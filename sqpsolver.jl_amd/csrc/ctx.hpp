@@ -249,6 +249,13 @@ struct Ctx {
     int refine_period = 0;
     long resolve_served = -1;       // ... and the last sweep of the current run whose solve chain served them (-1: none yet)
     int trans_period = 0;           // 0: by group size (3 from 64 instances, 2 from 32, else 1); SQPHIP_TRANS_PERIOD, read at creation
+    // transitions inside the post launch (ipm_sweep, k_ipm_post_ride): 0 the inline launches every trans_period-th sweep, 1 one
+    // ride (finish, stage and start in one post launch), 2 two rides (the start in the launch after), -1 the default of ipm_sweep
+    // (by group size: 2 from 32 instances on, else 1);
+    // SQPHIP_TRANS_RIDE, read at creation.  n_trans_inline: sweeps of this context or lane that launched the three transition
+    // kernels in line (test hook sqphip_trans_inline_groups)
+    int trans_ride = -1;
+    long n_trans_inline = 0;
     Timers tm;
     std::vector<void *> allocs;
     std::string err;

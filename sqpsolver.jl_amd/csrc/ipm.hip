@@ -18,6 +18,7 @@
 #include "ctx.hpp"
 #include "dev_util.hpp"
 #include "mf_dev.hpp"
+#include "sqp_dev.hpp"
 #include <cmath>
 
 #ifndef SQPHIP_VEC_FUSE
@@ -79,13 +80,13 @@ __device__ __forceinline__ double jac_row(const DV &d, const double *jv, const d
     return acc;
 }
 // out_j = hsc * (H v)_j + hd_j v_j   (H full symmetric CSC, gather by column)
-__device__ void hess_mul(const DV &d, int inst, double hsc, const double *v, double *out)
+__device__ __forceinline__ void hess_mul(const DV &d, int inst, double hsc, const double *v, double *out)
 {
     const double *hv = d.hv + (long)inst * d.nnzhc, *hd = d.hd + (long)inst * d.n;
     for (int j = threadIdx.x; j < d.n; j += TPB) out[j] = hess_row(d, hv, hd, hsc, v, j);
 }
 // out_i = J_i v over active rows (CSR view)
-__device__ void jac_mul(const DV &d, int inst, const double *v, double *out)
+__device__ __forceinline__ void jac_mul(const DV &d, int inst, const double *v, double *out)
 {
     const double *jv = d.jv + (long)inst * d.nnzjc;
     const int *rt = d.rtype + (long)inst * d.m;
@@ -116,7 +117,7 @@ __device__ __forceinline__ double jact_col(const DV &d, const double *jv, const 
 
 // ---------------------------------------------------------------------------------------------
 // K2: COO -> CSC with duplicate summation by precomputed gather lists (sqp.jl:94-102, :113-116)
-static __device__ void b_qp_gather(const DV &d)
+static __device__ __forceinline__ void b_qp_gather(const DV &d)
 {
     const int inst = blockIdx.x;
     const IpmState &st = d.ist[inst];
@@ -188,7 +189,7 @@ __device__ __forceinline__ double nudge_inside(double v, double lo, double hi)
 
 // ---------------------------------------------------------------------------------------------
 // Mode set-up (stage 0 only computes the request-dependent data), weights, interior start.
-static __device__ void b_ipm_start(const DV &d)
+static __device__ __forceinline__ void b_ipm_start(const DV &d)
 {
     const int inst = blockIdx.x;
     IpmState &st = d.ist[inst];
@@ -300,7 +301,7 @@ static __device__ void b_ipm_start(const DV &d)
 
 // ---------------------------------------------------------------------------------------------
 // top of an interior-point iteration: residuals, convergence test, barrier update, diagonals
-static __device__ void b_ipm_prepare(const DV &d)
+static __device__ __forceinline__ void b_ipm_prepare(const DV &d)
 {
     const int inst = blockIdx.x;
     if (d.phase[inst] != ph_prep(d)) return;
@@ -609,7 +610,7 @@ __device__ __forceinline__ double solve_vector_at(const DV &d, const double *jv,
         return v;
     }
 }
-__device__ void load_solve_vector(const DV &d, int inst, const double *src, double *xv)
+__device__ __forceinline__ void load_solve_vector(const DV &d, int inst, const double *src, double *xv)
 {
     const double *jv = d.jv + (long)inst * d.nnzjc, *Dd = d.Dd + (long)inst * d.m;
     const int *rt = d.rtype + (long)inst * d.m;
@@ -618,7 +619,7 @@ __device__ void load_solve_vector(const DV &d, int inst, const double *src, doub
 
 // Newton right-hand side for centring target tgt (minus the second-order terms when soc), its working copy xv
 // for the triangular solves, sol = 0.  Returns max |rhs| (block-wide).
-__device__ double build_rhs(const DV &d, int inst, double tgt, bool soc)
+__device__ __forceinline__ double build_rhs(const DV &d, int inst, double tgt, bool soc)
 {
     INST_PTRS
     SOC_PTRS
@@ -659,7 +660,7 @@ __device__ double build_rhs(const DV &d, int inst, double tgt, bool soc)
 // xv, which the panel kernels of the factorisation turn into L^-1 rhs on the fly (fused forward elimination).
 // Runs for every instance in PH_FACTOR, i.e. again before each re-factorisation.  In predictor-corrector mode
 // this is the predictor's (affine-scaling, target 0) right-hand side.
-static __device__ void b_build_rhs(const DV &d)
+static __device__ __forceinline__ void b_build_rhs(const DV &d)
 {
     const int inst = blockIdx.x;
     if (d.phase[inst] != ph_fact(d)) return;
@@ -695,7 +696,7 @@ __global__ __launch_bounds__(TPB, SQPHIP_VEC_WAVES_PER_EU) void k_inertia(DV d)
 // becomes the next right-hand side, the sweep runs one more forward/backward solve and calls this kernel with last = 1.
 // part: 3 = the whole routine (one workgroup per instance does everything), 1 = accumulation only, 2 = residual and decision
 // only (d.flat: the sparse products of each part are formed by flat kernels in front of it, ipm_sweep)
-static __device__ void b_refine(const DV &d, int last, int want, int part = 3)
+static __device__ __forceinline__ void b_refine(const DV &d, int last, int want, int part = 3)
 {
     const int inst = blockIdx.x;
     if (d.phase[inst] != want) return;
@@ -810,7 +811,7 @@ __device__ __forceinline__ double ratio(double x, double dx, double a)
 
 // expand the solution of the reduced system to all directions (centring target tgt, minus the second-order terms
 // when soc); ap / ad: this thread's largest primal / dual steps to the boundary
-__device__ void expand_directions(const DV &d, int inst, double tgt, bool soc, double &ap, double &ad)
+__device__ __forceinline__ void expand_directions(const DV &d, int inst, double tgt, bool soc, double &ap, double &ad)
 {
     INST_PTRS
     SOC_PTRS
@@ -855,7 +856,7 @@ __device__ void expand_directions(const DV &d, int inst, double tgt, bool soc, d
 // corrector's right-hand side goes through the same factorisation.  If this factorisation needed an inertia
 // correction the sub-problem is not convex along the path: the solve falls back to the monotone rule for good,
 // restarted from the current average complementarity.
-static __device__ void b_mpc(const DV &d)
+static __device__ __forceinline__ void b_mpc(const DV &d)
 {
     const int inst = blockIdx.x;
     if (d.phase[inst] != PH_MPC) return;
@@ -915,7 +916,7 @@ static __device__ void b_mpc(const DV &d)
 }
 
 // directions, fraction-to-boundary step lengths, update
-static __device__ void b_ipm_step(const DV &d)
+static __device__ __forceinline__ void b_ipm_step(const DV &d)
 {
     const int inst = blockIdx.x;
     if (d.phase[inst] != PH_STEP) return;
@@ -965,7 +966,7 @@ static __device__ void b_ipm_step(const DV &d)
 // ---------------------------------------------------------------------------------------------
 // outcome of a finished interior-point run: accept, phase 1, penalty escalation, or infeasible;
 // final results in the JuMP sign convention (collect_solution!, subproblem_JuMP.jl:514-563)
-__global__ __launch_bounds__(TPB, SQPHIP_VEC_WAVES_PER_EU) void k_qp_finish(DV d)
+static __device__ __forceinline__ void b_qp_finish(const DV &d)
 {
     const int inst = blockIdx.x;
     if (d.phase[inst] != PH_DONE) return;
@@ -1041,6 +1042,8 @@ __global__ __launch_bounds__(TPB, SQPHIP_VEC_WAVES_PER_EU) void k_qp_finish(DV d
     }
     if (threadIdx.x == 0) { st.status = status; st.prev_mode = status == SQPHIP_MOI_LOCALLY_SOLVED ? st.mode + 1 : 0; d.phase[inst] = PH_IDLE; }
 }
+
+__global__ __launch_bounds__(TPB, SQPHIP_VEC_WAVES_PER_EU) void k_qp_finish(DV d) { b_qp_finish(d); }
 
 __global__ void k_count(DV d)
 {
@@ -1152,6 +1155,55 @@ __global__ __launch_bounds__(TPB, SQPHIP_VEC_WAVES_PER_EU) void k_ipm_post(DV d,
         __syncthreads();
         b_build_rhs(d);
     }
+    if (host_slot) b_sweep_count(d, host_slot);
+}
+
+// Transitions between sub-problems inside the post launch (Ctx::trans_ride).  The workgroup of an
+// instance that is between two sub-problems has nothing to do in k_ipm_post and returns at once; here it does the work of the
+// three transition kernels for its instance instead, beside the post work of everybody else, and ipm_sweep launches none of
+// them behind the first sweep of a run.  What a workgroup does is decided from the state of its instance at kernel ENTRY,
+// read by every thread before any thread writes state:
+//   start set                                -> ride 2: the blocks of k_ipm_head (the next sub-problem, its first right-hand side);
+//   PH_DONE, or idle with its run not over   -> ride 1: b_qp_finish, then the stage blocks of k_sqp_stage (chain: and on into
+//                                               the head blocks in the same launch -- SQPHIP_TRANS_RIDE=1, the A/B of the split);
+//   anything else                            -> the post path of k_ipm_post<PH_SOLVE, true>, `also` included.
+// An instance whose b_ipm_prepare ends its run inside this launch is finished by the NEXT post launch: post + transitions in
+// one workgroup would lengthen every sweep.  All state a transition touches is the instance's own (the scenario queue's
+// counter is atomic), the blocks and their barriers are those of the three kernels: the same bits whichever launch serves.
+__global__ __launch_bounds__(TPB, SQPHIP_VEC_WAVES_PER_EU) void k_ipm_post_ride(DV d, int last, int also, int *host_slot, int chain)
+{
+    const int inst = blockIdx.x;
+    const SqpState &S = d.sst[inst];
+    const int ph = __builtin_amdgcn_readfirstlane(d.phase[inst]);
+    const int start = __builtin_amdgcn_readfirstlane(d.ist[inst].start);
+    const int done = __builtin_amdgcn_readfirstlane(S.done), budget = __builtin_amdgcn_readfirstlane(S.budget),
+              stage = __builtin_amdgcn_readfirstlane(S.stage);
+    const int scen = d.stream.M > 0 ? __builtin_amdgcn_readfirstlane(d.stream.slot_scen[inst]) : -1;
+    __syncthreads();
+    // work left in this run: what b_sweep_count counts, or a terminated slot of the scenario queue that has not found it empty
+    const bool live = done ? scen != -1 : (budget > 0 || stage != ST_TOP);
+    // (the blocks are __forceinline__: left as a call, a block takes the 1 920-byte device view through scratch memory)
+    if (start || ph == PH_DONE || (ph == PH_IDLE && live)) {
+        if (!start) {
+            b_qp_finish(d);
+            __syncthreads();
+            b_sqp_stage(d);
+            __syncthreads();
+        }
+        if (start || chain) {
+            b_qp_gather(d);
+            __syncthreads();
+            b_ipm_start(d);
+        }
+    } else {
+        b_refine(d, last, ph == also ? also : (int)PH_SOLVE);
+        __syncthreads();
+        b_ipm_step(d);
+    }
+    __syncthreads();
+    b_ipm_prepare(d);            // (PH_PREP: behind the step of the post path, behind the start of a ride)
+    __syncthreads();
+    b_build_rhs(d);
     if (host_slot) b_sweep_count(d, host_slot);
 }
 
@@ -1279,14 +1331,26 @@ bool ipm_sweep(Ctx &C, bool sqp_level, int *host_slot)
     // (round 4, monotone rule -- shorter sweeps, the transitions weigh more: every fourth sweep from groups of eight on;
     //  512 x IEEE-118 P = 3 / 4 / 5 -> 8 836 / 8 878 / 8 894 QP/s, 64 scenarios P = 1 / 2 / 4 / 5 -> 2 458 / 2 555 / 2 584 / 2 567)
     const int period = C.trans_period > 0 ? C.trans_period : (d.ipm_corrector == 0 ? (d.B >= 8 ? 4 : 1) : (d.B >= 64 ? 3 : (d.B >= 32 ? 2 : 1)));
-    const bool trans = !sqp_level || period <= 1 || (C.run_sweep % period) == 0;
+    const bool mono = d.ipm_corrector == 0;
+    const bool top_inertia = d.sparse && mf_solve_tests_inertia(C);      // the streamed solve kernel tests the inertia itself
+    // what rides in the solve chain and the post launch of a sweep (monotone rule, sparse path, streamed top, one-workgroup vector
+    // stages): the refinement solves (below), and -- SQP level, groups of at least eight instances, Ctx::trans_ride -- the
+    // transitions: k_ipm_post_ride serves them from the workgroups k_ipm_post leaves idle, the three transition kernels are
+    // launched in the first sweep of a run only (a run that starts with idle slots draws its scenarios and first requests there)
+    // and the period above is without effect.  1: finish, stage and start in one launch; 2: the start in the launch after.
+    // Default by group size, as measured: two rides from 32 instances on -- with one ride the post launch
+    // of a group of 128 lasts as long as a whole transition and 512 resident scenarios lose 1.3 % against the inline launches --,
+    // one ride below, where the launch is short either way and the sweep saved counts (64 resident scenarios: +3.8 % / +2.5 %).
+    // Measured: groups of 16, 128 and 512.  Groups of 8 - 15 take the setting of 16 and groups of 32 - 127 that of 128 by extrapolation.
+    const bool ride = mono && d.sparse && !d.flat && top_inertia && !C.refine_slot && !C.post_split;
+    const int tride = ride && sqp_level && !C.side_on && d.B >= 8 ? (C.trans_ride >= 0 ? C.trans_ride : (d.B >= 32 ? 2 : 1)) : 0;
+    const bool trans = tride ? C.run_sweep == 0 : (!sqp_level || period <= 1 || (C.run_sweep % period) == 0);
     C.run_sweep++;
     const dim3 gP((d.n + d.m + 255) / 256, d.B), gX((d.Fpad + 255) / 256, d.B), b256(256);       // flat products (d.flat)
     // monotone rule: the Newton right-hand side of an iteration is built by the kernel that ends the iteration before
     // (k_ipm_post) or starts the sub-problem (k_ipm_head); the sparse factorisation leaves the working vector of a failed
     // inertia trial as it was, so a sweep without transitions starts with the matrix values (the dense path consumes the
     // vector in place and keeps k_ipm_rhs)
-    const bool mono = d.ipm_corrector == 0;
     // Transitions on a side stream (Ctx::side_on; ctx.hpp, the PH_ enum): from the second sweep of a run on, the three
     // transition kernels of EVERY sweep run beside the factorisation / solve / post kernels of the same sweep, on the instances
     // that had finished a sub-problem when the sweep before ended; what they start joins the next sweep.  The main chain loses
@@ -1305,6 +1369,7 @@ bool ipm_sweep(Ctx &C, bool sqp_level, int *host_slot)
         SQPHIP_HIP_OK(hipEventRecord(C.evS[k & 3], C.side));
     } else if (side || trans) {
         DV d0 = d; d0.side = 0;              // (in line: the first sweep of a run with the side stream, every P-th without)
+        C.n_trans_inline++;
         C.tm.open(s);
         hipLaunchKernelGGL(k_qp_finish, gB, bT, 0, s, d0);
         if (sqp_level) sqp_stage_kernels(C, s, d0);
@@ -1324,7 +1389,6 @@ bool ipm_sweep(Ctx &C, bool sqp_level, int *host_slot)
     if (d.sparse) { mf_factor(C, PH_FACTOR, true, d.vals_inline != 0); C.tm.n_factor++; }
     else ldlt_factor(C.plan, d.K, d.dinv, d.phase, PH_FACTOR, &C.tm, d.xv, d.vv);
     if (C.tm.enabled) { hipEventRecord(ev.second, s); C.tm.pending_factor.push_back(ev); }
-    const bool top_inertia = d.sparse && mf_solve_tests_inertia(C);      // the streamed solve kernel tests the inertia itself
     // Refinement solves in the sweep's own solve chain (monotone rule, sparse path, streamed top, one-workgroup vector stages):
     // an instance in PH_RESOLVE is gated out of the values and of every front launch, so its factors stay valid in its arena
     // until a later sweep's solve chain serves it -- forward level launches gated to it ahead of the top launch, then the top,
@@ -1332,7 +1396,6 @@ bool ipm_sweep(Ctx &C, bool sqp_level, int *host_slot)
     // each as long as its slowest instance, for the one or two instances of a group that wait) stays behind SQPHIP_REFINE_SLOT=1.
     // Which sweep serves an instance changes nothing it computes.  Served every refine_period-th sweep of a run once the host
     // has seen a request.
-    const bool ride = mono && d.sparse && !d.flat && top_inertia && !C.refine_slot && !C.post_split;
     const int rperiod = C.refine_period > 0 ? C.refine_period : 1;
     const int also = ride && C.want_resolve && (!sqp_level || rperiod <= 1 || (C.run_sweep % rperiod) == 0) ? (int)PH_RESOLVE : -1;
     if (also >= 0) C.resolve_served = C.run_sweep - 1;      // (this sweep's position in the run: sqp_run_lane reads it with the counter)
@@ -1378,7 +1441,8 @@ bool ipm_sweep(Ctx &C, bool sqp_level, int *host_slot)
                     if (want == PH_SOLVE) hipLaunchKernelGGL((k_ipm_post<PH_SOLVE, false>), gB, bT, vlds, s, d, last, -1, no_slot);
                     else hipLaunchKernelGGL((k_ipm_post<PH_RESOLVE, false>), gB, bT, vlds, s, d, last, -1, no_slot);
                     hipLaunchKernelGGL(k_ipm_rhs, gB, bT, vlds, s, d);
-                } else if (want == PH_SOLVE) hipLaunchKernelGGL((k_ipm_post<PH_SOLVE, true>), gB, bT, vlds, s, d, last, also, ride && !C.side_on ? host_slot : no_slot);
+                } else if (want == PH_SOLVE && tride) hipLaunchKernelGGL(k_ipm_post_ride, gB, bT, vlds, s, d, last, also, host_slot, tride == 1 ? 1 : 0);
+                else if (want == PH_SOLVE) hipLaunchKernelGGL((k_ipm_post<PH_SOLVE, true>), gB, bT, vlds, s, d, last, also, ride && !C.side_on ? host_slot : no_slot);
                 else hipLaunchKernelGGL((k_ipm_post<PH_RESOLVE, true>), gB, bT, vlds, s, d, last, -1, no_slot);
                 return;
             }

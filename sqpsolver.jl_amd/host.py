@@ -354,6 +354,13 @@ class Context:
         self._ck(self.L.sqphip_mf_census(self.h, _l(cnt), names, nk.value, C.byref(nk)))
         return {names.raw[64 * k:64 * (k + 1)].split(b"\0")[0].decode(): int(cnt[k]) for k in range(nk.value)}
 
+    def trans_inline_groups(self):
+        """Sweeps, summed over the instance groups, that launched the three transition kernels in line
+        (`sqphip_trans_inline_groups`); with the transitions riding in the post launch: the first sweep of every run only."""
+        out = C.c_int64()
+        self._ck(self.L.sqphip_trans_inline_groups(self.h, C.byref(out)))
+        return int(out.value)
+
     # ---- merit path
     def norm_violations(self, E, x, p=1):
         out = C.c_double()
