@@ -311,8 +311,8 @@ int sqphip_acopf_set_dclines(sqphip_ctx *ctx, int32_t ndc, const double *loss1);
 int sqphip_acopf_set_instance(sqphip_ctx *ctx, int32_t inst, const double *ohm, const double *c2, const double *c1,
                               const double *x0);
 /* Evaluate the five callbacks on the device for instance `inst` at host point x (parity tests): the attached device
- * callbacks, whichever attach provided them (ACOPF, dense, QCQP).  Any output may be NULL. lambda/sigma only matter for
- * hval. */
+ * callbacks, whichever attach provided them (ACOPF, dense, QCQP, factorable NLP).  Any output may be NULL.
+ * lambda/sigma only matter for hval. */
 int sqphip_acopf_eval(sqphip_ctx *ctx, int32_t inst, const double *x, double sigma,
                       const double *lambda, double *f, double *grad, double *g, double *jval,
                       double *hval);
@@ -353,6 +353,43 @@ int sqphip_qcqp_attach(sqphip_ctx *ctx, int64_t nnzQ0, const int64_t *q0r, const
  * contingency-style scenarios.  Bounds go through sqphip_set_bounds. */
 int sqphip_qcqp_set_instance(sqphip_ctx *ctx, int32_t inst, const double *f0, const double *c, const double *q0v,
                              const double *g0, const double *av, const double *qv, const double *x0);
+/* A sparse factorable NLP for the batched run -- any user model whose objective and rows are sums of products of
+ * univariate functions:
+ *     min  f0 + sum_{t: trow[t] = 0} c_t prod_k phi_tk(x_{v_tk})
+ *     s.t. gL_i <= g0_i + sum_{t: trow[t] = i} c_t prod_k phi_tk(x_{v_tk}) <= gU_i  (i = 1..m),   xL <= x <= xU
+ * Every factor is phi(x) = kappa(a x + b) with kappa = fkind: 0 POW u^e (integer e = fexp, 1 <= |e| <= 32; fexp is read
+ * for POW only), 1 SIN, 2 COS, 3 EXP, 4 LOG; a = fscale, b = fshift.  Term t has the factors tptr[t] .. tptr[t + 1] - 1 of
+ * the factor arrays, at least 1 and at most 8, on distinct variables (x x is written x^2); a constant belongs in f0 / g0.
+ * The context must have been created with a Jacobian COO that holds (i, v) for every factor of a term of row i and --
+ * unless nnzH = 0, the SLP path -- a Hessian COO that holds the lower entry (v, w) for every two factors of one term
+ * and (v, v) for every factor that is not a plain linear POW with e = 1; a term of rows 1..num_linear is a single POW
+ * factor with e = 1, a = 1, b = 0.  The structure (rows, variables, kinds, e, a, b) is shared by the batch; the values
+ * given here (g0 [m] may be NULL: zeros) start every instance.  Once, on the host, the call builds gather plans from
+ * the terms and the COO structures (per row, per variable, per Jacobian and per Hessian COO slot; the first COO copy
+ * of a duplicated slot owns its plan, the other copies stay 0); the device evaluates per instance in two passes --
+ * phi, phi', phi'' of every factor, then products over the plans -- with fixed summation orders (bit-reproducible,
+ * independent of the slot).
+ * Domain is the caller's business: LOG and negative powers need bounds that keep a x + b positive at every point the
+ * solver visits.  Note that the linear-feasibility phase moves to x = 0 when the linear rows are infeasible inside the
+ * first trust region (its outputs are zeroed on an infeasible LP), whatever the bounds say: start from a point that
+ * satisfies the linear rows when a factor is undefined at 0.
+ * Returns SQPHIP_EINVAL, sqphip_last_error naming the 1-based term (and factor), on an index out of range, an unknown
+ * kind, an exponent of 0 or beyond +-32, a term with no or with more than 8 factors, a variable twice in one term, a
+ * nonlinear term in a linear row, or an entry the COO structures lack; SQPHIP_ESTATE on a context attached before (any
+ * *_attach).  On such a context sqphip_sqp_reset / _run / _get / _status / _trace / _work / _qp_log* / _last_request
+ * and the counters work unchanged, sqphip_acopf_eval probes the evaluator and sqphip_acopf_armijo works;
+ * sqphip_acopf_set_instance, _set_shunts, _set_dclines, sqphip_qcqp_set_instance and both queues' _stream_begin / _set
+ * return SQPHIP_EINVAL (the scenario queue does not carry these values yet).
+ * An instance's values are one block of doubles (f0 | g0 | c, padded to an even count). */
+int sqphip_nlp_attach(sqphip_ctx *ctx, int64_t nterms, const int64_t *trow /* 0: objective, i: row i */,
+                      const double *tcoef, const int64_t *tptr /* [nterms + 1], offsets into the factor arrays */,
+                      const int64_t *fvar /* 1-based */, const int32_t *fkind, const int32_t *fexp,
+                      const double *fscale, const double *fshift /* either may be NULL: 1 and 0 */,
+                      const double *g0 /* [m] or NULL */, double f0);
+/* Per-instance values (f0 one value, g0 [m], tcoef [nterms] in the term order of the attach) and the start x0 [n];
+ * any pointer may be NULL: keep.  Bounds go through sqphip_set_bounds. */
+int sqphip_nlp_set_instance(sqphip_ctx *ctx, int32_t inst, const double *f0, const double *g0,
+                            const double *tcoef, const double *x0);   /* NULL: keep; bounds via sqphip_set_bounds */
 /* Run SQP-TR for every instance until each has terminated or done `max_outer` more outer
  * iterations (0 = no cap beyond options.max_iter).  Restartable: state stays on the device. */
 int sqphip_sqp_reset(sqphip_ctx *ctx);

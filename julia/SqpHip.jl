@@ -224,6 +224,21 @@ hip_qcqp_set_instance(ctx::Ptr{Cvoid}, inst::Integer; f0 = nothing, c = nothing,
                       (Ptr{Cvoid}, Int32, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble},
                        Ptr{Cdouble}), ctx, inst, _vals(f0 === nothing ? nothing : Float64[f0]), _vals(c), _vals(q0v), _vals(g0),
                       _vals(av), _vals(qv), _vals(x0)))
+# ---- a sparse factorable NLP in the batched run (sqphip_nlp_attach): sums of products of univariate functions
+# kappa(a x + b), kappa = fkind: 0 u^e (integer e = fexp), 1 sin, 2 cos, 3 exp, 4 log.  trow: 0 objective, i row i; term t has
+# the factors tptr[t] + 1 : tptr[t + 1] (tptr is 0-based offsets, nterms + 1 long); fvar is 1-based.  At most 8 factors per
+# term on distinct variables; the context's Jacobian / Hessian COO must hold every entry the terms need.
+hip_nlp_attach(ctx::Ptr{Cvoid}, trow::Vector{Int64}, tcoef::Vector{Float64}, tptr::Vector{Int64}, fvar::Vector{Int64},
+               fkind::Vector{Int32}, fexp::Vector{Int32}, fscale::Vector{Float64}, fshift::Vector{Float64},
+               g0::Vector{Float64}, f0::Real) =
+    _check(ctx, ccall((:sqphip_nlp_attach, LIBSQPHIP), Cint,
+                      (Ptr{Cvoid}, Int64, Ptr{Int64}, Ptr{Cdouble}, Ptr{Int64}, Ptr{Int64}, Ptr{Int32}, Ptr{Int32},
+                       Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Cdouble),
+                      ctx, length(trow), trow, tcoef, tptr, fvar, fkind, fexp, fscale, fshift, g0, f0))
+hip_nlp_set_instance(ctx::Ptr{Cvoid}, inst::Integer; f0 = nothing, g0 = nothing, tcoef = nothing, x0 = nothing) =
+    _check(ctx, ccall((:sqphip_nlp_set_instance, LIBSQPHIP), Cint,
+                      (Ptr{Cvoid}, Int32, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}),
+                      ctx, inst, _vals(f0 === nothing ? nothing : Float64[f0]), _vals(g0), _vals(tcoef), _vals(x0)))
 hip_sqp_run(ctx::Ptr{Cvoid}, max_outer::Integer = 0) =
     _check(ctx, ccall((:sqphip_sqp_run, LIBSQPHIP), Cint, (Ptr{Cvoid}, Int32), ctx, max_outer))
 hip_stream_begin(ctx::Ptr{Cvoid}, n_scenarios::Integer) =

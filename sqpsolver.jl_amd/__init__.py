@@ -6,6 +6,7 @@ fallback: every entry point raises if the library has not been built."""
 from . import acopf_synth  # noqa: F401
 from . import dense_synth  # noqa: F401
 from . import qcqp  # noqa: F401
+from . import nlp_terms  # noqa: F401
 from . import _lib  # noqa: F401
 from . import host  # noqa: F401
 from .host import (Context, QpData, QpHip, default_options, SqpHipError, kkt_order,  # noqa: F401

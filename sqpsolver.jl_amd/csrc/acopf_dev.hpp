@@ -3,6 +3,7 @@
 #include "ctx.hpp"
 #include "dev_util.hpp"
 #include "qcqp_dev.hpp"
+#include "nlp_dev.hpp"
 #include <cmath>
 
 namespace sqphip {
@@ -445,6 +446,7 @@ static __device__ __forceinline__ void acopf_eval(const DV &d, int inst, const d
                            double *jv, double *hv)
 {
     if (d.qc) { qcqp_eval(d, inst, x, sigma, lam, f_out, grad, gv, jv, hv); return; }          // uniform over the launch
+    if (d.nlp) { nlp_eval(d, inst, x, sigma, lam, f_out, grad, gv, jv, hv); return; }
     acopf_eval_dedicated(d, inst, x, sigma, lam, f_out, grad, gv, jv, hv);
 }
 

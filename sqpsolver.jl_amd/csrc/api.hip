@@ -4,6 +4,7 @@
 // sqp.jl:96-101), lays the batch out in HBM and forwards to the kernels.
 #include "ctx.hpp"
 #include "qcqp_dev.hpp"
+#include "nlp_dev.hpp"
 #include <algorithm>
 #include <array>
 #include <chrono>
@@ -144,6 +145,7 @@ void make_lanes(Ctx &C)
         L->trans_period = C.trans_period; L->trans_ride = C.trans_ride; L->refine_slot = C.refine_slot; L->refine_period = C.refine_period; L->mf_big_lds = C.mf_big_lds; L->post_split = C.post_split; L->side_mode = C.side_mode; L->spec_tail = C.spec_tail; L->spec_mode0 = C.spec_mode0;
         L->d = group_view(C.d, lo, hi - lo, g);
         if (L->d.qcv) L->d.qcv += (long)lo * C.qc_nv;
+        if (L->d.nlv) { L->d.nlv += (long)lo * C.nl_nv; L->d.nlw += (long)lo * 3 * C.nl_nfac; }
         // the first group runs on the owner's stream (idle during sqphip_sqp_run): HIP maps streams onto four hardware
         // queues by default, and a fifth stream would share one -- measured: 3131 QP/s with five streams against 5216
         // with four (or with GPU_MAX_HW_QUEUES=8)
@@ -1352,17 +1354,25 @@ extern "C" int sqphip_acopf_attach_acwr(sqphip_ctx *h, int32_t nb, int32_t ng, i
     });
 }
 
-static int qcqp_refuse(sqphip_ctx *h, const char *fn)
+// The tables of sqphip_acopf_set_* and of the ACOPF scenario queue (sqphip_sqp_stream_begin / _set) exist on a context
+// attached with one of the three ACOPF forms only: on a dense, QCQP or factorable-NLP context those entry points are
+// refused here, on the host, before anything touches the device.  Returns 0 on an ACOPF (or unattached) context.
+static int acopf_only(sqphip_ctx *h, const char *fn)
 {
-    h->c.err = std::string(fn) + ": not available on a QCQP context (sqphip_qcqp_attach; use sqphip_qcqp_set_instance, "
-               "sqphip_qcqp_stream_begin / _set)";
+    if (!h) return 0;
+    const DV &d = h->c.d;
+    const char *what = d.qc ? "a QCQP context (sqphip_qcqp_attach; use sqphip_qcqp_set_instance, sqphip_qcqp_stream_begin / _set)"
+                     : d.nlp ? "an NLP context (sqphip_nlp_attach; use sqphip_nlp_set_instance)"
+                     : d.dense_nlp ? "a dense context (sqphip_dense_attach; use sqphip_dense_set_instance)" : nullptr;
+    if (!what) return 0;
+    h->c.err = std::string(fn) + ": not available on " + what;
     return SQPHIP_EINVAL;
 }
 
 extern "C" int sqphip_acopf_set_shunts(sqphip_ctx *h, int32_t nsh, const int32_t *sh_bus, const double *gs,
                                        const double *bs)
 {
-    if (h && h->c.d.qc) return qcqp_refuse(h, "sqphip_acopf_set_shunts");
+    if (acopf_only(h, "sqphip_acopf_set_shunts")) return SQPHIP_EINVAL;
     if (!h || !h->c.acopf_attached || nsh < 0) return SQPHIP_EINVAL;
     Ctx &C0 = h->c;
     const int nl = C0.d.nl, ng = C0.d.ng, nb = C0.d.nb;
@@ -1392,7 +1402,7 @@ extern "C" int sqphip_acopf_set_shunts(sqphip_ctx *h, int32_t nsh, const int32_t
 
 extern "C" int sqphip_acopf_set_dclines(sqphip_ctx *h, int32_t ndc, const double *loss1)
 {
-    if (h && h->c.d.qc) return qcqp_refuse(h, "sqphip_acopf_set_dclines");
+    if (acopf_only(h, "sqphip_acopf_set_dclines")) return SQPHIP_EINVAL;
     if (!h || !h->c.acopf_attached || ndc != h->c.d.ndc || (ndc > 0 && !loss1)) return SQPHIP_EINVAL;
     if (ndc == 0) return SQPHIP_OK;
     return guarded(h, [&](Ctx &C) {
@@ -1406,7 +1416,7 @@ extern "C" int sqphip_acopf_set_dclines(sqphip_ctx *h, int32_t ndc, const double
 extern "C" int sqphip_acopf_set_instance(sqphip_ctx *h, int32_t inst, const double *ohm, const double *c2,
                                          const double *c1, const double *x0)
 {
-    if (h && h->c.d.qc) return qcqp_refuse(h, "sqphip_acopf_set_instance");
+    if (acopf_only(h, "sqphip_acopf_set_instance")) return SQPHIP_EINVAL;
     if (!h || !h->c.acopf_attached || inst < 0 || inst >= h->c.d.B) return SQPHIP_EINVAL;
     return guarded(h, [&](Ctx &C) {
         DV &d = C.d;
@@ -1608,6 +1618,10 @@ extern "C" int sqphip_qcqp_attach(sqphip_ctx *h, int64_t nnzQ0, const int64_t *q
 extern "C" int sqphip_qcqp_set_instance(sqphip_ctx *h, int32_t inst, const double *f0, const double *c, const double *q0v,
                                         const double *g0, const double *av, const double *qv, const double *x0)
 {
+    if (h && !h->c.d.qc && h->c.acopf_attached) {
+        h->c.err = "sqphip_qcqp_set_instance: the context has no QCQP attached (sqphip_qcqp_attach)";
+        return SQPHIP_EINVAL;
+    }
     if (!h || !h->c.d.qc || inst < 0 || inst >= h->c.d.B) return SQPHIP_EINVAL;
     return guarded(h, [&](Ctx &C) {
         DV &d = C.d;
@@ -1615,6 +1629,167 @@ extern "C" int sqphip_qcqp_set_instance(sqphip_ctx *h, int32_t inst, const doubl
         double *v = d.qcv + (size_t)inst * C.qc_nv;
         const double *src[6] = {f0, c, q0v, g0, av, qv};
         for (int k = 0; k < 6; ++k) h2d(C, v + o[k], src[k], (size_t)(o[k + 1] - o[k]));
+        h2d(C, d.x0 + (size_t)inst * d.n, x0, d.n);
+        SQPHIP_HIP_OK(hipStreamSynchronize(C.stream));
+        return SQPHIP_OK;
+    });
+}
+
+// ---- a sparse factorable NLP (nlp_dev.hpp nlp_eval): sums of products of univariate functions.  The gather plans are
+// built here, once, from the terms and the COO structures of sqphip_create
+static int nlp_fail(sqphip_ctx *h, int64_t t, int64_t k, const std::string &msg)
+{
+    h->c.err = "sqphip_nlp_attach: term " + std::to_string(t + 1) + (k >= 0 ? " factor " + std::to_string(k + 1) : std::string()) + ": " + msg;
+    return SQPHIP_EINVAL;
+}
+
+// owners of a plan's entries (in production order) -> CSR row pointers and the stable order of the entries by owner
+static void plan_order(int owners, const std::vector<int> &own, std::vector<int> &ptr, std::vector<int> &ord)
+{
+    ptr.assign(owners + 1, 0);
+    for (int o : own) ptr[o + 1]++;
+    for (int r = 0; r < owners; ++r) ptr[r + 1] += ptr[r];
+    std::vector<int> fill(ptr.begin(), ptr.end() - 1);
+    ord.assign(own.size(), 0);
+    for (size_t e = 0; e < own.size(); ++e) ord[fill[own[e]]++] = (int)e;
+}
+
+extern "C" int sqphip_nlp_attach(sqphip_ctx *h, int64_t nterms, const int64_t *trow, const double *tcoef, const int64_t *tptr,
+                                 const int64_t *fvar, const int32_t *fkind, const int32_t *fexp, const double *fscale,
+                                 const double *fshift, const double *g0, double f0)
+{
+    if (!h) return SQPHIP_EINVAL;
+    Ctx &C0 = h->c;
+    if (C0.acopf_attached) {
+        C0.err = "sqphip_nlp_attach: the context already has device callbacks (an earlier *_attach)";
+        return SQPHIP_ESTATE;
+    }
+    auto fail = [&](const char *msg) { C0.err = std::string("sqphip_nlp_attach: ") + msg; return (int)SQPHIP_EINVAL; };
+    if (nterms < 0) return fail("negative term count");
+    if (!tptr || (nterms > 0 && (!trow || !tcoef))) return fail("null term array");
+    if (tptr[0] != 0) return fail("tptr[0] must be 0");
+    for (int64_t t = 0; t < nterms; ++t)
+        if (tptr[t + 1] < tptr[t]) return nlp_fail(h, t, -1, "tptr decreases");
+    const int64_t nfac = tptr[nterms];
+    if (nfac > 0 && (!fvar || !fkind || !fexp)) return fail("null factor array");
+    if (nfac > (1 << 28) || nterms > (1 << 28)) return fail("too many terms");
+    const int64_t n = C0.d.n, m = C0.d.m, nlin = C0.d.nlin, nnzJ = C0.d.nnzj_coo, nnzH = C0.d.nnzh_coo;
+    // first COO slot of every structural entry (later duplicates get no plan entries: 0, gather_csc sums them)
+    std::unordered_map<int64_t, int> jslot, hslot;
+    for (int64_t k = nnzJ - 1; k >= 0; --k) jslot[(C0.h_jrow[k] - 1) * n + (C0.h_jcol[k] - 1)] = (int)k;
+    for (int64_t k = nnzH - 1; k >= 0; --k) {
+        const int64_t r = C0.h_hrow[k] - 1, cc = C0.h_hcol[k] - 1;
+        hslot[std::max(r, cc) * n + std::min(r, cc)] = (int)k;
+    }
+    auto jfind = [&](int64_t i, int64_t j) { auto it = jslot.find(i * n + j); return it == jslot.end() ? -1 : it->second; };
+    auto hfind = [&](int64_t r, int64_t cc) {
+        auto it = hslot.find(std::max(r, cc) * n + std::min(r, cc)); return it == hslot.end() ? -1 : it->second; };
+    std::vector<int> ot, g_own, g_t, f_own, j_own, h_own;
+    std::vector<int2> f_e, j_e;
+    std::vector<int4> h_e;
+    std::vector<int> fke((size_t)std::max<int64_t>(nfac, 1), 0), fv(fke.size(), 0);
+    std::vector<double2> fab(fke.size(), double2{1.0, 0.0});
+    for (int64_t t = 0; t < nterms; ++t) {
+        const int64_t i = trow[t], k0 = tptr[t], k1 = tptr[t + 1];
+        if (i < 0 || i > m) return nlp_fail(h, t, -1, "row " + std::to_string(i) + " out of range (0: objective, 1.." + std::to_string(m) + ")");
+        if (k1 == k0) return nlp_fail(h, t, -1, "no factors (a constant belongs in f0 / g0)");
+        if (k1 - k0 > 8) return nlp_fail(h, t, -1, "more than 8 factors");
+        bool plain[8];
+        for (int64_t k = k0; k < k1; ++k) {
+            const int64_t v = fvar[k] - 1, kf = k - k0;
+            const double a = fscale ? fscale[k] : 1.0, b = fshift ? fshift[k] : 0.0;
+            if (v < 0 || v >= n) return nlp_fail(h, t, kf, "variable " + std::to_string(fvar[k]) + " out of range");
+            if (fkind[k] < NLP_POW || fkind[k] > NLP_LOG) return nlp_fail(h, t, kf, "unknown kind " + std::to_string(fkind[k]));
+            const int e = fkind[k] == NLP_POW ? fexp[k] : 1;
+            if (e == 0 || e > 32 || e < -32) return nlp_fail(h, t, kf, "exponent " + std::to_string(e) + " (1 <= |e| <= 32)");
+            for (int64_t k2 = k0; k2 < k; ++k2)
+                if (fvar[k2] == fvar[k]) return nlp_fail(h, t, kf, "variable " + std::to_string(fvar[k]) + " twice in one term (write x^2)");
+            plain[kf] = fkind[k] == NLP_POW && e == 1;
+            if (i >= 1 && i <= nlin && !(k1 - k0 == 1 && plain[kf] && a == 1.0 && b == 0.0))
+                return nlp_fail(h, t, kf, "row " + std::to_string(i) + " is one of the num_linear = " + std::to_string(nlin) +
+                                          " linear rows: a single POW factor with e = 1, a = 1, b = 0 only");
+            fv[k] = (int)v; fke[k] = fkind[k] + 8 * (e + 32); fab[k] = double2{a, b};
+        }
+        if (i == 0) ot.push_back((int)t); else { g_own.push_back((int)i - 1); g_t.push_back((int)t); }
+        for (int64_t k = k0; k < k1; ++k) {
+            if (i == 0) { f_own.push_back(fv[k]); f_e.push_back(int2{(int)t, (int)k}); continue; }
+            const int js = jfind(i - 1, fv[k]);
+            if (js < 0) return nlp_fail(h, t, k - k0, "needs the Jacobian entry (" + std::to_string(i) + ", " + std::to_string(fvar[k]) +
+                                                      ") that the structure of sqphip_create lacks");
+            j_own.push_back(js); j_e.push_back(int2{(int)t, (int)k});
+        }
+        if (nnzH > 0)
+            for (int64_t k = k0; k < k1; ++k)
+                for (int64_t k2 = k0; k2 <= k; ++k2) {
+                    if (k2 == k && plain[k - k0]) continue;            // phi'' = 0
+                    const int hs = hfind(fv[k], fv[k2]);
+                    if (hs < 0) return nlp_fail(h, t, k - k0, "needs the Hessian entry (" + std::to_string(std::max(fvar[k], fvar[k2])) + ", " +
+                                                              std::to_string(std::min(fvar[k], fvar[k2])) + ") that the structure of sqphip_create lacks");
+                    h_own.push_back(hs); h_e.push_back(int4{(int)t, (int)k2, (int)k, (int)i - 1});
+                }
+    }
+    // CSR by owner, the entries of one owner kept in production (term) order
+    std::vector<int> g_ptr, f_ptr, j_ptr, h_ptr, ord;
+    plan_order((int)m, g_own, g_ptr, ord);
+    std::vector<int> ge(std::max<size_t>(ord.size(), 1), 0);
+    for (size_t e = 0; e < ord.size(); ++e) ge[e] = g_t[ord[e]];
+    plan_order((int)n, f_own, f_ptr, ord);
+    std::vector<int2> fe(std::max<size_t>(ord.size(), 1), int2{0, 0});
+    for (size_t e = 0; e < ord.size(); ++e) fe[e] = f_e[ord[e]];
+    plan_order((int)nnzJ, j_own, j_ptr, ord);
+    std::vector<int2> je(std::max<size_t>(ord.size(), 1), int2{0, 0});
+    for (size_t e = 0; e < ord.size(); ++e) je[e] = j_e[ord[e]];
+    plan_order((int)nnzH, h_own, h_ptr, ord);
+    std::vector<int4> he(std::max<size_t>(ord.size(), 1), int4{0, 0, 0, 0});
+    for (size_t e = 0; e < ord.size(); ++e) he[e] = h_e[ord[e]];
+    std::vector<int> ptr(g_ptr);
+    const int fp = (int)ptr.size(); ptr.insert(ptr.end(), f_ptr.begin(), f_ptr.end());
+    const int jp = (int)ptr.size(); ptr.insert(ptr.end(), j_ptr.begin(), j_ptr.end());
+    const int hp = (int)ptr.size(); ptr.insert(ptr.end(), h_ptr.begin(), h_ptr.end());
+    std::vector<int> tp((size_t)nterms + 1);
+    for (int64_t t = 0; t <= nterms; ++t) tp[t] = (int)tptr[t];
+    // values of an instance: f0 | g0 | c, the stride padded to even: every block is 16-byte aligned, as the QCQP blocks are
+    const long nvals = 1 + (long)m + nterms, nv = (nvals + 1) & ~1L;
+    std::vector<double> val0(nv, 0.0);
+    val0[0] = f0;
+    if (g0) std::copy(g0, g0 + m, val0.begin() + 1);
+    if (nterms) std::copy(tcoef, tcoef + nterms, val0.begin() + 1 + m);
+    const int nobj = (int)ot.size();
+    if (ot.empty()) ot.push_back(0);
+    return guarded(h, [&](Ctx &C) {
+        DV &d = C.d;
+        NlpDev P = {};
+        P.n = (int)n; P.m = (int)m; P.nterms = (int)nterms; P.nfac = (int)nfac; P.nv = (int)nv; P.nobj = nobj;
+        P.f_ptr = fp; P.j_ptr = jp; P.h_ptr = hp;
+        P.ptr = C.upload(ptr); P.tptr = C.upload(tp); P.fvar = C.upload(fv); P.fke = C.upload(fke); P.fab = C.upload(fab);
+        P.ot = C.upload(ot); P.ge = C.upload(ge); P.fe = C.upload(fe); P.je = C.upload(je); P.he = C.upload(he);
+        NlpDev *pd = (NlpDev *)C.dalloc<char>(sizeof(NlpDev));
+        SQPHIP_HIP_OK(hipMemcpyAsync(pd, &P, sizeof(NlpDev), hipMemcpyHostToDevice, C.stream));
+        std::vector<double> all((size_t)d.B * nv);
+        for (int b = 0; b < d.B; ++b) std::copy(val0.begin(), val0.end(), all.begin() + (size_t)b * nv);
+        d.nlv = C.upload(all);
+        d.nlw = C.dalloc<double>((size_t)d.B * 3 * (size_t)nfac);
+        d.nlp = pd;
+        C.nl_nv = nv; C.nl_nfac = nfac; C.nl_nterms = nterms;
+        SQPHIP_HIP_OK(hipStreamSynchronize(C.stream));
+        C.acopf_attached = true;           // (the batched run! has its device callbacks)
+        make_lanes(C);
+        return SQPHIP_OK;
+    });
+}
+
+extern "C" int sqphip_nlp_set_instance(sqphip_ctx *h, int32_t inst, const double *f0, const double *g0, const double *tcoef,
+                                       const double *x0)
+{
+    if (h && !h->c.d.nlp) {
+        h->c.err = "sqphip_nlp_set_instance: the context has no factorable NLP attached (sqphip_nlp_attach)";
+        return SQPHIP_EINVAL;
+    }
+    if (!h || inst < 0 || inst >= h->c.d.B) return SQPHIP_EINVAL;
+    return guarded(h, [&](Ctx &C) {
+        DV &d = C.d;
+        double *v = d.nlv + (size_t)inst * C.nl_nv;           // f0 | g0 | c
+        h2d(C, v, f0, 1); h2d(C, v + 1, g0, d.m); h2d(C, v + 1 + d.m, tcoef, (size_t)C.nl_nterms);
         h2d(C, d.x0 + (size_t)inst * d.n, x0, d.n);
         SQPHIP_HIP_OK(hipStreamSynchronize(C.stream));
         return SQPHIP_OK;
@@ -1877,7 +2052,7 @@ extern "C" int sqphip_sqp_last_request(sqphip_ctx *h, int32_t inst, int32_t *mod
 // ---- scenario queue: more scenarios than slots ----------------------------------------------------------------
 extern "C" int sqphip_sqp_stream_begin(sqphip_ctx *h, int32_t n_scenarios)
 {
-    if (h && h->c.d.qc) return qcqp_refuse(h, "sqphip_sqp_stream_begin");
+    if (acopf_only(h, "sqphip_sqp_stream_begin")) return SQPHIP_EINVAL;
     if (!h || !h->c.acopf_attached || n_scenarios <= 0) return SQPHIP_EINVAL;
     return guarded(h, [&](Ctx &C) {
         DV &d = C.d;
@@ -1914,7 +2089,7 @@ extern "C" int sqphip_sqp_stream_set(sqphip_ctx *h, int32_t scen, const double *
                                      const double *gU, const double *ohm, const double *c2, const double *c1,
                                      const double *x0)
 {
-    if (h && h->c.d.qc) return qcqp_refuse(h, "sqphip_sqp_stream_set");
+    if (acopf_only(h, "sqphip_sqp_stream_set")) return SQPHIP_EINVAL;
     if (!h || scen < 0 || scen >= h->c.d.stream.M || !xL || !xU || !gL || !gU || !ohm || !c2 || !c1 || !x0) return SQPHIP_EINVAL;
     for (int i = 0; i < h->c.d.m; ++i) {
         if (gL[i] == -INFINITY && gU[i] == INFINITY) return SQPHIP_EINVAL;

@@ -129,6 +129,7 @@ struct StreamDev {
 };
 
 struct QcqpDev;                           // qcqp_dev.hpp
+struct NlpDev;                            // nlp_dev.hpp
 
 // everything kernels need, by value
 struct DV {
@@ -206,6 +207,9 @@ struct DV {
     // ---- general sparse QCQP evaluator data
     const QcqpDev *qc;                    // non-null: a general sparse QCQP (qcqp_dev.hpp qcqp_eval; sqphip_qcqp_attach), its plans in HBM
     double *qcv;                          // ... its values [B][qc->nv] (nv even)
+    // ---- sparse factorable NLP evaluator data
+    const NlpDev *nlp;                    // non-null: sums of products of univariate functions (nlp_dev.hpp nlp_eval; sqphip_nlp_attach), its plans in HBM
+    double *nlv, *nlw;                    // ... its values [B][nlp->nv] (nv even) and the factor workspace [B][3 nlp->nfac]
 };
 
 // phase codes by the side a kernel runs on (see the enum)
@@ -270,6 +274,7 @@ struct Ctx {
     long qc_nv = 0;             // doubles per instance of an attached QCQP (DV::qcv; even: the blocks are 16-byte aligned) ...
     long qc_off[7] = {};        // ... and where its parts start: f0, c, Q0, g0, A, Q, end
     std::vector<double> h_qc_base;              // ... the values given to sqphip_qcqp_attach (NULL parts of a queue scenario)
+    long nl_nv = 0, nl_nfac = 0, nl_nterms = 0; // doubles per instance of an attached factorable NLP (DV::nlv: f0 | g0 | c, padded to even), its factors and terms
     std::vector<double> h_xL, h_xU, h_gL, h_gU; // the bounds given to sqphip_create (NULL bounds of a queue scenario)
     bool acopf_attached = false;
     bool mf_big_lds = false;        // the multifrontal kernels were granted 160 KB of dynamic LDS on this context's device (mf_device_setup)

@@ -1,0 +1,154 @@
+// nlp_dev.hpp -- device-side evaluator of a sparse factorable NLP (sqphip_nlp_attach): sums of products of univariate
+// functions,
+//     min  f0 + sum_{t: row(t) = 0} c_t prod_k phi_tk(x_{v_tk})
+//     s.t. gL_i <= g0_i + sum_{t: row(t) = i} c_t prod_k phi_tk(x_{v_tk}) <= gU_i,   xL <= x <= xU
+// with phi(x) = kappa(a x + b), kappa one of u^e (integer e), sin, cos, exp, log.  A term has at most 8 factors on distinct
+// variables.  The structure of the batch (rows, variables, kinds, e, a, b) is fixed at attach; an instance carries its own
+// values [f0 | g0 (m) | c (nterms)].  Two passes per evaluation, one workgroup per instance:
+//   1. one thread per factor writes phi, phi', phi'' (chain factors a, a^2 included) into the instance's workspace in HBM
+//      -- the only place that calls sincos / exp / log; integer powers by repeated multiplication, one reciprocal for a
+//      negative exponent; only phi when just f / g are asked for (trial points, Armijo probes), phi'' only with the Hessian;
+//   2. the gather plans of the host (CSR, indices only: per row, per variable, per Jacobian COO slot, per Hessian COO slot)
+//      combine the stored values by multiplications only: c prod phi, c phi'_a prod_{k != a} phi_k,
+//      c phi'_a phi'_b prod_{others}, c phi''_a prod_{k != a} phi_k, each times sigma or lambda_i.
+// Every output entry is one thread's sum over its plan row in plan order: no atomics, bit-reproducible results that do not
+// depend on the slot an instance sits in.
+#pragma once
+#include "ctx.hpp"
+#include "dev_util.hpp"
+#include <cmath>
+
+namespace sqphip {
+
+enum { NLP_POW = 0, NLP_SIN = 1, NLP_COS = 2, NLP_EXP = 3, NLP_LOG = 4 };
+
+struct NlpDev {
+    int n, m, nterms, nfac, nv, nobj;     // variables, rows, terms, factors, values per instance (even), objective terms
+    int f_ptr, j_ptr, h_ptr;              // where the row pointers of the variable / Jacobian / Hessian plans start in ptr
+    const int *ptr;                       // the four CSR row pointers back to back: rows [m + 1], variables [n + 1], slots
+    const int *tptr;                      // [nterms + 1] factors of a term
+    const int *fvar;                      // [nfac] variable of a factor (0-based)
+    const int *fke;                       // [nfac] kind + 8 * (exponent + 32)
+    const double2 *fab;                   // [nfac] (a, b)
+    const int *ot;                        // [nobj] the objective's terms
+    const int *ge;                        // row i: g0_i + sum over terms t
+    const int2 *fe;                       // variable j: sum over (term, factor) of objective terms
+    const int2 *je;                       // Jacobian slot: sum over (term, factor)
+    const int4 *he;                       // Hessian slot: sum over (term, factor a, factor b or a, row or -1) times lambda[row] or sigma
+};
+
+// c-free product of term t with factors a and b differentiated (a == b: twice; -1: not at all), in factor order
+static __device__ __forceinline__ double nlp_prod(const int *__restrict__ tptr, const double *__restrict__ w, int nf, int t,
+                                                  int a, int b)
+{
+    double p = 1.0;
+    #pragma unroll 1
+    for (int k = tptr[t]; k < tptr[t + 1]; ++k) p *= w[((k == a) + (k == b)) * nf + k];
+    return p;
+}
+
+// pass 1 for factor k at u = a x + b
+static __device__ __forceinline__ void nlp_factor(int ke, double a, double u, bool d1, bool d2, double *__restrict__ w, int nf, int k)
+{
+    const int kind = ke & 7;
+    double p0, p1 = 0.0, p2 = 0.0;
+    if (kind == NLP_POW) {
+        const int e = (ke >> 3) - 32, ae = e < 0 ? -e : e;
+        const double q = e < 0 ? 1.0 / u : u;
+        // lo = q^(ae - 2) (e >= 2) or 1; then u^(e-2), u^(e-1), u^e upwards (e > 0) or q^ae, q^(ae+1), q^(ae+2) (e < 0)
+        double lo = 1.0;
+        #pragma unroll 1
+        for (int i = (e < 0 ? 0 : 2); i < ae; ++i) lo *= q;
+        if (e > 0) {
+            const double m1 = e >= 2 ? lo * u : 1.0;
+            p0 = m1 * u; p1 = e * m1 * a; p2 = (double)(e * (e - 1)) * lo * (a * a);
+        } else {
+            const double m1 = lo * q;
+            p0 = lo; p1 = e * m1 * a; p2 = (double)(e * (e - 1)) * (m1 * q) * (a * a);
+        }
+    } else if (kind == NLP_EXP) {
+        p0 = exp(u); p1 = a * p0; p2 = a * a * p0;
+    } else if (kind == NLP_LOG) {
+        const double r = 1.0 / u;
+        p0 = log(u); p1 = a * r; p2 = -(a * a) * (r * r);
+    } else {
+        double s, c;
+        sincos(u, &s, &c);
+        if (kind == NLP_SIN) { p0 = s; p1 = a * c; p2 = -(a * a) * s; }
+        else { p0 = c; p1 = -a * s; p2 = -(a * a) * c; }
+    }
+    w[k] = p0;
+    if (d1) w[nf + k] = p1;
+    if (d2) w[2 * nf + k] = p2;
+}
+
+// the acopf_eval signature; any of f_out, grad, gv, jv, hv may be null.  Called by every thread of the workgroup.
+static __device__ __forceinline__ void nlp_eval(const DV &d, int inst, const double *__restrict__ x, double sigma,
+                                                const double *__restrict__ lam, double *f_out, double *grad, double *gv,
+                                                double *jv, double *hv)
+{
+    const NlpDev &q = *d.nlp;
+    const int nf = q.nfac;
+    const double *__restrict__ val = d.nlv + (long)inst * q.nv;
+    double *__restrict__ w = d.nlw + (long)inst * 3 * nf;
+    const double *__restrict__ cf = val + 1 + q.m;
+    const int *__restrict__ tptr = q.tptr;
+    const bool d1 = grad || jv || hv, d2 = hv != nullptr;     // phi'' is read by the Hessian plan only
+    __syncthreads();                        // x is complete; nobody still reads the workspace of an earlier evaluation
+    #pragma unroll 1
+    for (int k = threadIdx.x; k < nf; k += TPB) {
+        const double2 ab = q.fab[k];
+        nlp_factor(q.fke[k], ab.x, ab.x * x[q.fvar[k]] + ab.y, d1, d2, w, nf, k);
+    }
+    __syncthreads();
+    if (f_out) {
+        double f = 0.0;
+        #pragma unroll 1
+        for (int e = threadIdx.x; e < q.nobj; e += TPB) { const int t = q.ot[e]; f += cf[t] * nlp_prod(tptr, w, nf, t, -1, -1); }
+        f = block_reduce<OpSum>(f);
+        if (threadIdx.x == 0) *f_out = val[0] + f;
+    }
+    if (grad) {
+        const int *ptr = q.ptr + q.f_ptr;
+        #pragma unroll 1
+        for (int j = threadIdx.x; j < q.n; j += TPB) {
+            double s = 0.0;
+            #pragma unroll 1
+            for (int k = ptr[j]; k < ptr[j + 1]; ++k) { const int2 e = q.fe[k]; s += cf[e.x] * nlp_prod(tptr, w, nf, e.x, e.y, -1); }
+            grad[j] = s;
+        }
+    }
+    if (gv)
+        #pragma unroll 1
+        for (int i = threadIdx.x; i < q.m; i += TPB) {
+            double s = val[1 + i];
+            #pragma unroll 1
+            for (int k = q.ptr[i]; k < q.ptr[i + 1]; ++k) { const int t = q.ge[k]; s += cf[t] * nlp_prod(tptr, w, nf, t, -1, -1); }
+            gv[i] = s;
+        }
+    if (jv) {
+        const int *ptr = q.ptr + q.j_ptr;
+        #pragma unroll 1
+        for (int s_ = threadIdx.x; s_ < d.nnzj_coo; s_ += TPB) {
+            double s = 0.0;
+            #pragma unroll 1
+            for (int k = ptr[s_]; k < ptr[s_ + 1]; ++k) { const int2 e = q.je[k]; s += cf[e.x] * nlp_prod(tptr, w, nf, e.x, e.y, -1); }
+            jv[s_] = s;
+        }
+    }
+    if (hv) {
+        const int *ptr = q.ptr + q.h_ptr;
+        #pragma unroll 1
+        for (int s_ = threadIdx.x; s_ < d.nnzh_coo; s_ += TPB) {
+            double s = 0.0;
+            #pragma unroll 1
+            for (int k = ptr[s_]; k < ptr[s_ + 1]; ++k) {
+                const int4 e = q.he[k];
+                s += cf[e.x] * nlp_prod(tptr, w, nf, e.x, e.y, e.z) * (e.w < 0 ? sigma : lam[e.w]);
+            }
+            hv[s_] = s;
+        }
+    }
+}
+
+}  // namespace sqphip

@@ -469,6 +469,28 @@ class Context:
         arr = [None if values.get(k) is None else _f(np.atleast_1d(values[k])) for k in ("f0", "c", "q0v", "g0", "av", "qv")]
         self._ck(self.L.sqphip_qcqp_set_instance(self.h, inst, *[_d(a) for a in arr], _d(_f(x0))))
 
+    # ---- a sparse factorable NLP (nlp_terms.py; csrc/nlp_dev.hpp nlp_eval)
+    def nlp_attach(self, p):
+        """Structure of the batch and the values every instance starts with (sqphip_nlp_attach); p: nlp_terms.NlpTerms."""
+        t = [np.ascontiguousarray(a, dtype=np.int64) for a in (p.trow, p.tptr, p.fvar)]
+        k = [np.ascontiguousarray(a, dtype=np.int32) for a in (p.fkind, p.fexp)]
+        v = [_f(a) for a in (p.tcoef, p.fscale, p.fshift, p.g0)]
+        self._ck(self.L.sqphip_nlp_attach(self.h, len(t[0]), _l(t[0]), _d(v[0]), _l(t[1]), _l(t[2]), _i(k[0]), _i(k[1]),
+                                          _d(v[1]), _d(v[2]), _d(v[3]), float(p.f0)))
+
+    def nlp_set_instance(self, inst, p=None, x0=None, **values):
+        """Per-instance values (sqphip_nlp_set_instance).  With an NlpTerms p: its bounds, every value and its start; keywords
+        f0, g0, tcoef override single parts, and what is given neither way is kept."""
+        if p is not None:
+            self.set_bounds(inst, p)
+            values = {**{k: getattr(p, k) for k in ("f0", "g0", "tcoef")}, **values}
+            x0 = p.x0 if x0 is None else x0
+        bad = set(values) - {"f0", "g0", "tcoef"}
+        if bad:
+            raise TypeError(f"nlp_set_instance: unknown values {sorted(bad)}")
+        arr = [None if values.get(k) is None else _f(np.atleast_1d(values[k])) for k in ("f0", "g0", "tcoef")]
+        self._ck(self.L.sqphip_nlp_set_instance(self.h, inst, *[_d(a) for a in arr], _d(_f(x0))))
+
     def acopf_eval(self, inst, x, sigma=1.0, lam=None):
         f = C.c_double(); grad = np.zeros(self.n); g = np.zeros(self.m)
         jv = np.zeros(self.nnzj); hv = np.zeros(self.nnzh) if lam is not None else None

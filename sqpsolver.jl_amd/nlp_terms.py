@@ -1,0 +1,270 @@
+"""A sparse factorable NLP for the batched device run (sqphip_nlp_attach): sums of products of univariate functions,
+
+    min  f0 + sum_{t: row(t) = 0} c_t prod_k phi_tk(x_{v_tk})
+    s.t. gL_i <= g0_i + sum_{t: row(t) = i} c_t prod_k phi_tk(x_{v_tk}) <= gU_i   (i = 1..m),   xL <= x <= xU
+
+Every factor is phi(x) = kappa(a x + b) with kappa one of POW (u^e, integer e, 1 <= |e| <= 32), SIN, COS, EXP, LOG.  A term
+has 1 to 8 factors on distinct variables (x x is written x^2); rows 1..num_linear carry single plain factors (POW, e = 1,
+a = 1, b = 0) only.  The structure (rows, variables, kinds, e, a, b) is shared by a batch; an instance has its own
+f0, g0 and term coefficients.  Domain is the caller's business: LOG and negative powers need bounds that keep a x + b
+positive.
+
+    NlpTerms             the data (terms, factors, values, bounds, start)
+    make_nlp_terms       ... from a list of (row, coefficient, [(variable, kind, e, a, b), ...])
+    nlp_terms_layout     the structures a Context is created with (1-based Jacobian COO, lower Hessian COO, bounds, start)
+    nlp_terms_rows       g(x) in numpy
+    nlp_terms_synth      a seeded test problem over the whole menu with a start that satisfies every row
+    nlp_terms_scenario   scenario s of a problem: the same structure, other coefficients, the same feasible start
+    from_qcqp            a Qcqp (qcqp.py) restated as terms
+    from_polar_acopf     the polar ACOPF of acopf_layout restated as terms, on that layout's COO structures
+
+Device evaluator: csrc/nlp_dev.hpp nlp_eval."""
+from __future__ import annotations
+
+import dataclasses
+
+import numpy as np
+
+POW, SIN, COS, EXP, LOG = 0, 1, 2, 3, 4
+MAX_FACTORS = 8
+
+
+@dataclasses.dataclass
+class NlpTerms:
+    n: int
+    m: int
+    num_linear: int
+    trow: np.ndarray       # [nterms] 0: objective, i: row i (1-based)
+    tcoef: np.ndarray      # [nterms]
+    tptr: np.ndarray       # [nterms + 1] offsets into the factor arrays
+    fvar: np.ndarray       # [nfac] variable (1-based)
+    fkind: np.ndarray      # [nfac] POW .. LOG
+    fexp: np.ndarray       # [nfac] exponent (POW only; 1 elsewhere)
+    fscale: np.ndarray     # [nfac] a
+    fshift: np.ndarray     # [nfac] b
+    g0: np.ndarray         # [m]
+    f0: float
+    xL: np.ndarray
+    xU: np.ndarray
+    gL: np.ndarray
+    gU: np.ndarray
+    x0: np.ndarray
+
+
+@dataclasses.dataclass
+class NlpTermsLayout:
+    """What SqpSolver.Model holds for this problem (1-based COO structures, bounds, start)."""
+    n: int
+    m: int
+    num_linear: int
+    jrow: np.ndarray
+    jcol: np.ndarray
+    hrow: np.ndarray
+    hcol: np.ndarray
+    xL: np.ndarray
+    xU: np.ndarray
+    gL: np.ndarray
+    gU: np.ndarray
+    x0: np.ndarray
+
+
+def _i64(a):
+    return np.ascontiguousarray(a, dtype=np.int64)
+
+
+def _f64(a):
+    return np.ascontiguousarray(a, dtype=np.float64)
+
+
+def make_nlp_terms(n, m, num_linear, terms, g0=None, f0=0.0, xL=None, xU=None, gL=None, gU=None, x0=None) -> NlpTerms:
+    """terms: (row, coefficient, factors) with row 0 for the objective and factors (variable, kind[, e[, a[, b]]]), 1-based
+    variables; missing vectors are zeros, missing bounds infinite."""
+    inf = np.inf
+    full = lambda v, k, d: _f64(np.full(k, d) if v is None else v)
+    trow, tcoef, tptr, fv, fk, fe, fa, fb = [], [], [0], [], [], [], [], []
+    for row, coef, factors in terms:
+        trow.append(int(row)); tcoef.append(float(coef))
+        for fac in factors:
+            var, kind, e, a, b = (tuple(fac) + (1, 1.0, 0.0)[len(fac) - 2:])[:5]
+            fv.append(int(var)); fk.append(int(kind)); fe.append(int(e)); fa.append(float(a)); fb.append(float(b))
+        tptr.append(len(fv))
+    return NlpTerms(n, m, num_linear, _i64(trow), _f64(tcoef), _i64(tptr), _i64(fv), np.ascontiguousarray(fk, dtype=np.int32),
+                    np.ascontiguousarray(fe, dtype=np.int32), _f64(fa), _f64(fb), full(g0, m, 0.0), float(f0),
+                    full(xL, n, -inf), full(xU, n, inf), full(gL, m, -inf), full(gU, m, inf), full(x0, n, 0.0))
+
+
+def _term_of_factor(p: NlpTerms) -> np.ndarray:
+    return np.repeat(np.arange(len(p.trow), dtype=np.int64), np.diff(p.tptr))
+
+
+def nlp_terms_layout(p: NlpTerms) -> NlpTermsLayout:
+    """Jacobian COO: (i, v) of every factor of a term of row i, row-major; Hessian COO: the lower entry (v, w) of every two
+    factors of one term and (v, v) of every factor that is not plain linear (POW, e = 1), column-major.  Each once."""
+    n = p.n
+    tf = _term_of_factor(p)
+    rows = p.trow[tf]
+    inrow = rows > 0
+    jkey = np.unique((rows[inrow] - 1) * n + (p.fvar[inrow] - 1))
+    hk = []
+    curved = ~((p.fkind == POW) & (p.fexp == 1))
+    hk.append((p.fvar[curved] - 1) * n + (p.fvar[curved] - 1))
+    for t in range(len(p.trow)):
+        v = p.fvar[p.tptr[t]:p.tptr[t + 1]]
+        if len(v) > 1:
+            a, b = np.triu_indices(len(v), 1)
+            hk.append((np.minimum(v[a], v[b]) - 1) * n + np.maximum(v[a], v[b]) - 1)      # column-major key of the lower entry
+    hkey = np.unique(np.concatenate(hk)) if hk else np.zeros(0, np.int64)
+    return NlpTermsLayout(n, p.m, p.num_linear, jkey // n + 1, jkey % n + 1, hkey % n + 1, hkey // n + 1,
+                          p.xL.copy(), p.xU.copy(), p.gL.copy(), p.gU.copy(), p.x0.copy())
+
+
+def factor_values(p: NlpTerms, x) -> np.ndarray:
+    """phi of every factor at x."""
+    u = p.fscale * _f64(x)[p.fvar - 1] + p.fshift
+    out = np.empty(len(u))
+    with np.errstate(all="ignore"):
+        for kind, fn in ((SIN, np.sin), (COS, np.cos), (EXP, np.exp), (LOG, np.log)):
+            k = p.fkind == kind
+            out[k] = fn(u[k])
+        k = p.fkind == POW
+        out[k] = u[k] ** p.fexp[k].astype(np.float64)
+    return out
+
+
+def _term_values(p: NlpTerms, x) -> np.ndarray:
+    phi = factor_values(p, x)
+    return p.tcoef * (np.multiply.reduceat(phi, p.tptr[:-1]) if len(phi) else np.zeros(0))
+
+
+def nlp_terms_rows(p: NlpTerms, x) -> np.ndarray:
+    """g(x) (used to place the bounds of generated problems)."""
+    tv = _term_values(p, x)
+    g = p.g0.copy()
+    k = p.trow > 0
+    np.add.at(g, p.trow[k] - 1, tv[k])
+    return g
+
+
+def nlp_terms_synth(n: int = 24, m: int = 14, seed: int = 1, terms_per_row: int = 3) -> NlpTerms:
+    """Seeded problem over the whole menu: the objective sum w_j (x_j - a_j)^2 with a = x0 +- 0.3, two leading linear rows,
+    then rows of terms_per_row terms with 1-4 factors on distinct variables, kinds uniform over the menu.  Bounds [0.2, 3]
+    keep LOG and negative powers inside their domain; g0 and the row bounds are placed so that every row holds at the start
+    x0 (uniform in [0.6, 1.4]): equalities at their value, one-sided and range rows with slack 0.2 - 1.  (A start that
+    violates the linear rows sends the solver's feasibility phase to x = 0 and out of the domain.)"""
+    rng = np.random.default_rng(seed)
+    nlin = 2
+    x0 = rng.uniform(0.6, 1.4, n)
+    terms = []
+    a = x0 + 0.3 * rng.choice([-1.0, 1.0], n)
+    w = rng.uniform(0.5, 2.0, n)
+    for j in range(n):
+        terms.append((0, w[j], [(j + 1, POW, 2, 1.0, -a[j])]))
+    kinds = []
+    for i in range(1, m + 1):
+        if i <= nlin:
+            for j in rng.choice(n, terms_per_row, replace=False) + 1:
+                terms.append((i, rng.uniform(-1, 1), [(int(j), POW, 1, 1.0, 0.0)]))
+            kinds.append("eq" if i % 2 else "range")
+            continue
+        for _ in range(terms_per_row):
+            facs = []
+            for j in rng.choice(n, int(rng.integers(1, 5)), replace=False) + 1:
+                kind = int(rng.integers(0, 5))
+                e = int(rng.choice([-2, -1, 1, 2, 3])) if kind == POW else 1
+                sc = float(rng.choice([1.0, -1.0, 0.5, 2.0])) if kind in (SIN, COS, EXP) else 1.0
+                sh = float(rng.choice([0.0, 0.3])) if kind != POW else 0.0
+                facs.append((int(j), kind, e, sc, sh))
+            terms.append((i, rng.uniform(-1, 1), facs))
+        kinds.append(("eq", "upper", "range")[(i - nlin - 1) % 3])
+    p = make_nlp_terms(n, m, nlin, terms, g0=rng.uniform(-0.2, 0.2, m), f0=float(rng.standard_normal()),
+                       xL=np.full(n, 0.2), xU=np.full(n, 3.0), x0=x0)
+    g = nlp_terms_rows(p, x0)
+    for i, kind in enumerate(kinds):
+        s = rng.uniform(0.2, 1.0)
+        if kind == "eq":
+            p.gL[i] = p.gU[i] = g[i]
+        elif kind == "upper":
+            p.gL[i], p.gU[i] = -np.inf, g[i] + s
+        else:
+            p.gL[i], p.gU[i] = g[i] - s, g[i] + s
+    return p
+
+
+def nlp_terms_scenario(p: NlpTerms, s: int, seed: int = 1) -> NlpTerms:
+    """Scenario s of p (s = 0: p itself): every coefficient scaled by 1 + 5 % noise, g0 moved so that every row keeps its
+    value at x0 -- the bounds (and the feasibility of x0) stay."""
+    if s == 0:
+        return p
+    rng = np.random.default_rng(seed * 1000 + s)
+    out = dataclasses.replace(p, tcoef=p.tcoef * (1.0 + 0.05 * rng.standard_normal(len(p.tcoef))), f0=p.f0 + 0.1 * s)
+    out.g0 = p.g0 + (nlp_terms_rows(p, p.x0) - nlp_terms_rows(out, p.x0))
+    return out
+
+
+def from_qcqp(q) -> NlpTerms:
+    """The Qcqp q as terms: c_j x_j for every variable, an off-diagonal Q entry v as v x_r x_c, a diagonal one as
+    (v / 2) x_r^2, A entries as single plain factors.  The term structure depends on q's structure only."""
+    terms = [(0, q.c[j], [(j + 1, POW)]) for j in range(q.n)]
+    quad = lambda row, r, c, v: (row, v, [(int(r), POW), (int(c), POW)]) if r != c else (row, 0.5 * v, [(int(r), POW, 2)])
+    terms += [quad(0, r, c, v) for r, c, v in zip(q.q0r, q.q0c, q.q0v)]
+    terms += [(int(i), v, [(int(j), POW)]) for i, j, v in zip(q.ar, q.ac, q.av)]
+    terms += [quad(int(i), r, c, v) for i, r, c, v in zip(q.qi, q.qr, q.qc, q.qv)]
+    return make_nlp_terms(q.n, q.m, q.num_linear, terms, g0=q.g0, f0=q.f0, xL=q.xL, xU=q.xU, gL=q.gL, gU=q.gU, x0=q.x0)
+
+
+def from_polar_acopf(net, lay) -> NlpTerms:
+    """The polar model of acopf_layout(net) as terms, for a Context created with lay's own COO structures (duplicates
+    included).  Flow k of a branch, F = A v_self^2 + v_f v_t (Bc cos(th_f - th_t) + Bs sin(th_f - th_t)), becomes
+    A v_self^2 and four four-factor terms through cos(th_f - th_t) = cos th_f cos th_t + sin th_f sin th_t and
+    sin(th_f - th_t) = sin th_f cos th_t - cos th_f sin th_t; the twelve coefficients per branch are net.branch_coeffs().
+    The structure depends on the topology only: contingency scenarios differ in their coefficients."""
+    nb, ng, nl, ndc = net.nb, net.ng, net.nl, net.ndc
+    VA, VM, PG = 1, nb + 1, 2 * nb + 1                     # 1-based first variables
+    PF = 2 * nb + 2 * ng + 1
+    own = [PF, PF + 2 * nl, PF + nl, PF + 3 * nl]          # p_f, q_f, p_t, q_t
+    DC = PF + 4 * nl
+    T0 = 2 * nl + 1 + 2 * nb                               # rows before the thermal rows
+    O0 = T0 + 2 * nl
+    co = net.branch_coeffs()
+    lin = lambda j: [(int(j), POW)]
+    terms = []
+    for g in range(ng):
+        terms.append((0, net.c2[g], [(PG + g, POW, 2)]))
+        terms.append((0, net.c1[g], lin(PG + g)))
+    for l in range(nl):
+        f, t = int(net.f_bus[l]), int(net.t_bus[l])
+        for off in (0, nl):                                # angle <= and >= rows
+            terms.append((off + l + 1, 1.0, lin(VA + f)))
+            terms.append((off + l + 1, -1.0, lin(VA + t)))
+    terms.append((2 * nl + 1, 1.0, lin(VA + net.ref_bus)))
+    gs = np.zeros(nb); bs = np.zeros(nb)
+    gs[lay.sh_bus] = lay.sh_gs; bs[lay.sh_bus] = lay.sh_bs
+    shunted = np.zeros(nb, bool); shunted[lay.sh_bus] = True
+    for i in range(nb):
+        for k in range(lay.bal_ptr[i], lay.bal_ptr[i + 1]):
+            terms.append((2 * nl + 2 + 2 * i, lay.bal_coef[k], lin(lay.bal_colP[k] + 1)))
+            terms.append((2 * nl + 3 + 2 * i, lay.bal_coef[k], lin(lay.bal_colQ[k] + 1)))
+        if shunted[i]:
+            terms.append((2 * nl + 2 + 2 * i, gs[i], [(VM + i, POW, 2)]))
+            terms.append((2 * nl + 3 + 2 * i, -bs[i], [(VM + i, POW, 2)]))
+    for l in range(nl):
+        terms.append((T0 + 2 * l + 1, 1.0, [(own[0] + l, POW, 2)])); terms.append((T0 + 2 * l + 1, 1.0, [(own[1] + l, POW, 2)]))
+        terms.append((T0 + 2 * l + 2, 1.0, [(own[2] + l, POW, 2)])); terms.append((T0 + 2 * l + 2, 1.0, [(own[3] + l, POW, 2)]))
+    for l in range(nl):
+        f, t = int(net.f_bus[l]), int(net.t_bus[l])
+        vf, vt = (VM + f, POW), (VM + t, POW)
+        cf, sf, ct, st = (VA + f, COS), (VA + f, SIN), (VA + t, COS), (VA + t, SIN)
+        for k in range(4):
+            A, Bc, Bs = co[l, 3 * k:3 * k + 3]
+            row = O0 + 4 * l + k + 1
+            terms.append((row, 1.0, lin(own[k] + l)))
+            terms.append((row, -A, [(VM + (t if k >= 2 else f), POW, 2)]))
+            terms.append((row, -Bc, [vf, vt, cf, ct]))
+            terms.append((row, -Bc, [vf, vt, sf, st]))
+            terms.append((row, -Bs, [vf, vt, sf, ct]))
+            terms.append((row, Bs, [vf, vt, cf, st]))
+    for d in range(ndc):                                   # loss rows: (1 - loss1) p_dc_f + p_dc_t = loss0
+        row = O0 + 4 * nl + d + 1
+        terms.append((row, 1.0 - lay.dc_loss1[d], lin(DC + d)))
+        terms.append((row, 1.0, lin(DC + ndc + d)))
+    return make_nlp_terms(lay.n, lay.m, lay.num_linear, terms, xL=lay.xL, xU=lay.xU, gL=lay.gL, gU=lay.gU, x0=lay.x0)
