@@ -378,8 +378,10 @@ int sqphip_qcqp_set_instance(sqphip_ctx *ctx, int32_t inst, const double *f0, co
  * nonlinear term in a linear row, or an entry the COO structures lack; SQPHIP_ESTATE on a context attached before (any
  * *_attach).  On such a context sqphip_sqp_reset / _run / _get / _status / _trace / _work / _qp_log* / _last_request
  * and the counters work unchanged, sqphip_acopf_eval probes the evaluator and sqphip_acopf_armijo works;
- * sqphip_acopf_set_instance, _set_shunts, _set_dclines, sqphip_qcqp_set_instance and both queues' _stream_begin / _set
- * return SQPHIP_EINVAL (the scenario queue does not carry these values yet).
+ * sqphip_acopf_set_instance, _set_shunts, _set_dclines, sqphip_qcqp_set_instance and the ACOPF and QCQP queues'
+ * _stream_begin / _set (sqphip_sqp_stream_begin, sqphip_qcqp_stream_begin) return SQPHIP_EINVAL: their tables are those
+ * of the other evaluators.  The scenario queue of an NLP context is begun and filled with sqphip_nlp_stream_begin / _set
+ * (below) and then run, shared and read with the sqphip_sqp_stream_* calls.
  * An instance's values are one block of doubles (f0 | g0 | c, padded to an even count). */
 int sqphip_nlp_attach(sqphip_ctx *ctx, int64_t nterms, const int64_t *trow /* 0: objective, i: row i */,
                       const double *tcoef, const int64_t *tptr /* [nterms + 1], offsets into the factor arrays */,
@@ -435,9 +437,25 @@ int sqphip_qcqp_stream_begin(sqphip_ctx *ctx, int32_t n_scenarios, int32_t keep_
 int sqphip_qcqp_stream_set(sqphip_ctx *ctx, int32_t scenario, const double *xL, const double *xU, const double *gL,
                            const double *gU, const double *f0, const double *c, const double *q0v, const double *g0,
                            const double *av, const double *qv, const double *x0);
+/* The queue of a factorable-NLP context (sqphip_nlp_attach): the same, for any sparse factorable NLP.  _run, _run_some,
+ * _assign, _append, _release and _get above work on it unchanged; a slot loads a scenario by one streaming copy of its
+ * block of values (f0 | g0 | c, padded to an even count: the layout of sqphip_nlp_set_instance) into the slot's own.
+ * tables for n_scenarios on an NLP context; keep_multipliers = 1 also allocates result tables for g, mult_g, mult_x_L,
+ * mult_x_U.  SQPHIP_EINVAL on a context without sqphip_nlp_attach (unattached, ACOPF, dense, QCQP) and for
+ * n_scenarios <= 0. */
+int sqphip_nlp_stream_begin(sqphip_ctx *ctx, int32_t n_scenarios, int32_t keep_multipliers);
+/* one scenario: bounds as sqphip_set_bounds, values as sqphip_nlp_set_instance (f0 one value, g0 [m], tcoef [nterms] in
+ * the term order of the attach), start x0.  A NULL value part means "the value given to sqphip_nlp_attach" (not what an
+ * instance holds now); NULL bounds mean the bounds given to sqphip_create; NULL x0 is refused.  SQPHIP_EINVAL,
+ * sqphip_last_error naming the scenario or the row (0-based), for a scenario outside the queue, a row unbounded on both
+ * sides and, with options.kkt_condense = 1, an equality row that was not one at sqphip_create; before
+ * sqphip_nlp_stream_begin the call is refused too. */
+int sqphip_nlp_stream_set(sqphip_ctx *ctx, int32_t scenario, const double *xL, const double *xU, const double *gL,
+                          const double *gU, const double *f0, const double *g0, const double *tcoef, const double *x0);
 /* everything sqphip_sqp_get returns, for a scenario of a queue begun with keep_multipliers = 1 (same signs as
  * sqphip_sqp_get: mult_g = -lambda, mult_x_U negated; any pointer may be NULL): the slot files them with the final
- * point before it draws its next scenario.  SQPHIP_ESTATE when the tables were not asked for. */
+ * point before it draws its next scenario.  SQPHIP_ESTATE when the tables were not asked for (sqphip_qcqp_stream_begin
+ * or sqphip_nlp_stream_begin with keep_multipliers = 0, or the ACOPF queue). */
 int sqphip_sqp_stream_get_full(sqphip_ctx *ctx, int32_t scenario, double *x, double *g, double *mult_g,
                                double *mult_x_L, double *mult_x_U, double *obj_val, int32_t *status, int32_t *iter);
 int sqphip_sqp_get(sqphip_ctx *ctx, int32_t inst, double *x, double *g, double *mult_g,

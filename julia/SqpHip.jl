@@ -254,6 +254,26 @@ function hip_stream_get(ctx::Ptr{Cvoid}, s::Integer, n::Integer)
                       ctx, s, x, obj, st, it))
     return x, obj[], st[], it[]
 end
+# ... on a factorable-NLP context (hip_nlp_attach): tables for n_scenarios, with keep_multipliers also for g and the
+# multipliers (hip_stream_get_full); one scenario (s is 0-based) with `nothing` for a value of hip_nlp_attach or a bound of
+# the context's creation; hip_stream_run / hip_stream_get are shared
+hip_nlp_stream_begin(ctx::Ptr{Cvoid}, n_scenarios::Integer; keep_multipliers::Bool = false) =
+    _check(ctx, ccall((:sqphip_nlp_stream_begin, LIBSQPHIP), Cint, (Ptr{Cvoid}, Int32, Int32), ctx, n_scenarios, keep_multipliers ? 1 : 0))
+hip_nlp_stream_set(ctx::Ptr{Cvoid}, s::Integer, x0::Vector{Float64}; xL = nothing, xU = nothing, gL = nothing, gU = nothing,
+                   f0 = nothing, g0 = nothing, tcoef = nothing) =
+    _check(ctx, ccall((:sqphip_nlp_stream_set, LIBSQPHIP), Cint,
+                      (Ptr{Cvoid}, Int32, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble},
+                       Ptr{Cdouble}, Ptr{Cdouble}), ctx, s, _vals(xL), _vals(xU), _vals(gL), _vals(gU),
+                      _vals(f0 === nothing ? nothing : Float64[f0]), _vals(g0), _vals(tcoef), x0))
+# everything of a scenario of a queue begun with keep_multipliers (signs as sqphip_sqp_get)
+function hip_stream_get_full(ctx::Ptr{Cvoid}, s::Integer, n::Integer, m::Integer)
+    x = zeros(n); g = zeros(m); mg = zeros(m); ml = zeros(n); mu = zeros(n)
+    obj = Ref{Cdouble}(0.0); st = Ref{Cint}(0); it = Ref{Cint}(0)
+    _check(ctx, ccall((:sqphip_sqp_stream_get_full, LIBSQPHIP), Cint,
+                      (Ptr{Cvoid}, Int32, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ref{Cdouble},
+                       Ref{Cint}, Ref{Cint}), ctx, s, x, g, mg, ml, mu, obj, st, it))
+    return (x = x, g = g, mult_g = mg, mult_x_L = ml, mult_x_U = mu, obj_val = obj[], status = st[], iter = it[])
+end
 # work of a batched run by instance (sub-problems, interior-point iterations, factorisations)
 function hip_sqp_work(ctx::Ptr{Cvoid}, batch::Integer)
     qp, ipm, fac = zeros(Int64, batch), zeros(Int64, batch), zeros(Int64, batch)

@@ -238,6 +238,9 @@ def lib():
             L.sqphip_qcqp_stream_begin.argtypes = [vp, C.c_int32, C.c_int32]
             L.sqphip_qcqp_stream_set.argtypes = [vp, C.c_int32] + [dp] * 11
             L.sqphip_sqp_stream_get_full.argtypes = [vp, C.c_int32, dp, dp, dp, dp, dp, dp, ip, ip]
+            if not os.environ.get("SQPHIP_SO") or hasattr(L, "sqphip_nlp_stream_begin"):   # (an older build given through SQPHIP_SO lacks the NLP queue)
+                L.sqphip_nlp_stream_begin.argtypes = [vp, C.c_int32, C.c_int32]
+                L.sqphip_nlp_stream_set.argtypes = [vp, C.c_int32] + [dp] * 8
             L.sqphip_sqp_work.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
             L.sqphip_reset_counters.argtypes = [vp]
             L.sqphip_set_timing.argtypes = [vp, C.c_int32]
@@ -258,6 +261,6 @@ EXPORTS = [
     "sqphip_kkt_order", "sqphip_kkt_symbolic", "sqphip_mf_host_solve", "sqphip_mf_host_top2_err", "sqphip_mf_host_spine_err", "sqphip_mf_solve_test", "sqphip_mf_batch_test", "sqphip_mf_census", "sqphip_trans_inline_groups", "sqphip_mf_plan_info", "sqphip_acopf_attach", "sqphip_acopf_attach_acr", "sqphip_acopf_attach_acwr", "sqphip_acopf_set_shunts", "sqphip_acopf_set_dclines", "sqphip_acopf_set_instance", "sqphip_dense_attach", "sqphip_dense_set_instance", "sqphip_qcqp_attach", "sqphip_qcqp_set_instance", "sqphip_nlp_attach", "sqphip_nlp_set_instance", "sqphip_acopf_eval", "sqphip_sqp_reset",
     "sqphip_sqp_run", "sqphip_sqp_get", "sqphip_sqp_status", "sqphip_sqp_trace",
     "sqphip_comm_available", "sqphip_comm_unique_id", "sqphip_comm_init", "sqphip_gather_status", "sqphip_comm_destroy",
-    "sqphip_get_counters", "sqphip_get_mode_counters", "sqphip_sqp_work", "sqphip_sqp_stream_begin", "sqphip_sqp_stream_set", "sqphip_sqp_stream_run", "sqphip_sqp_stream_get", "sqphip_sqp_stream_assign", "sqphip_sqp_stream_append", "sqphip_sqp_stream_release", "sqphip_sqp_stream_run_some", "sqphip_qcqp_stream_begin", "sqphip_qcqp_stream_set", "sqphip_sqp_stream_get_full", "sqphip_sqp_last_request", "sqphip_sqp_qp_log", "sqphip_reset_counters", "sqphip_set_timing", "sqphip_get_kernel_times", "sqphip_ldlt_factor_host",
+    "sqphip_get_counters", "sqphip_get_mode_counters", "sqphip_sqp_work", "sqphip_sqp_stream_begin", "sqphip_sqp_stream_set", "sqphip_sqp_stream_run", "sqphip_sqp_stream_get", "sqphip_sqp_stream_assign", "sqphip_sqp_stream_append", "sqphip_sqp_stream_release", "sqphip_sqp_stream_run_some", "sqphip_qcqp_stream_begin", "sqphip_qcqp_stream_set", "sqphip_nlp_stream_begin", "sqphip_nlp_stream_set", "sqphip_sqp_stream_get_full", "sqphip_sqp_last_request", "sqphip_sqp_qp_log", "sqphip_reset_counters", "sqphip_set_timing", "sqphip_get_kernel_times", "sqphip_ldlt_factor_host",
     "sqphip_ldlt_solve_host", "sqphip_ldlt_bench", "sqphip_ldlt_stress", "sqphip_ldlt_tile_masks", "sqphip_ldlt_case_test", "sqphip_mfma_f64_peak", "sqphip_armijo_alpha", "sqphip_compute_mu_rule",
 ]

@@ -1362,7 +1362,7 @@ static int acopf_only(sqphip_ctx *h, const char *fn)
     if (!h) return 0;
     const DV &d = h->c.d;
     const char *what = d.qc ? "a QCQP context (sqphip_qcqp_attach; use sqphip_qcqp_set_instance, sqphip_qcqp_stream_begin / _set)"
-                     : d.nlp ? "an NLP context (sqphip_nlp_attach; use sqphip_nlp_set_instance)"
+                     : d.nlp ? "an NLP context (sqphip_nlp_attach; use sqphip_nlp_set_instance, sqphip_nlp_stream_begin / _set)"
                      : d.dense_nlp ? "a dense context (sqphip_dense_attach; use sqphip_dense_set_instance)" : nullptr;
     if (!what) return 0;
     h->c.err = std::string(fn) + ": not available on " + what;
@@ -1771,6 +1771,7 @@ extern "C" int sqphip_nlp_attach(sqphip_ctx *h, int64_t nterms, const int64_t *t
         d.nlw = C.dalloc<double>((size_t)d.B * 3 * (size_t)nfac);
         d.nlp = pd;
         C.nl_nv = nv; C.nl_nfac = nfac; C.nl_nterms = nterms;
+        C.h_nl_base = val0;                // (the instances' blocks are overwritten by sqphip_nlp_set_instance)
         SQPHIP_HIP_OK(hipStreamSynchronize(C.stream));
         C.acopf_attached = true;           // (the batched run! has its device callbacks)
         make_lanes(C);
@@ -2237,13 +2238,11 @@ extern "C" int sqphip_sqp_stream_get(sqphip_ctx *h, int32_t scen, double *x, dou
     });
 }
 
-// ---- the queue on a QCQP context: a scenario is one block of values in the layout of DV::qcv, so that the loader of the
-// stage kernel (sqp.hip, b_sqp_stream) is one streaming copy; _run / _run_some / _assign / _append / _release / _get are shared
-extern "C" int sqphip_qcqp_stream_begin(sqphip_ctx *h, int32_t n_scenarios, int32_t keep_multipliers)
+// ---- the queue on a QCQP or factorable-NLP context: a scenario is one block of values in the layout of DV::qcv / DV::nlv, so
+// that the loader of the stage kernel (sqp_dev.hpp, b_sqp_stream) is one streaming copy; _run / _run_some / _assign / _append /
+// _release / _get are shared.  The tables of a queue of n_scenarios blocks of nv doubles:
+static int value_stream_begin(sqphip_ctx *h, int32_t n_scenarios, int32_t keep_multipliers, long nv)
 {
-    if (!h) return SQPHIP_EINVAL;
-    if (!h->c.d.qc) { h->c.err = "sqphip_qcqp_stream_begin: the context has no QCQP attached (sqphip_qcqp_attach)"; return SQPHIP_EINVAL; }
-    if (n_scenarios <= 0) { h->c.err = "sqphip_qcqp_stream_begin: n_scenarios must be positive"; return SQPHIP_EINVAL; }
     return guarded(h, [&](Ctx &C) {
         DV &d = C.d;
         StreamDev Q = {};
@@ -2260,7 +2259,7 @@ extern "C" int sqphip_qcqp_stream_begin(sqphip_ctx *h, int32_t n_scenarios, int3
         C.stream_started = false;
         Q.xL = C.dalloc<double>(M * d.n); Q.xU = C.dalloc<double>(M * d.n); Q.x0 = C.dalloc<double>(M * d.n);
         Q.gL = C.dalloc<double>(M * d.m); Q.gU = C.dalloc<double>(M * d.m);
-        Q.qcv = C.dalloc<double>(M * (size_t)C.qc_nv);
+        Q.val = C.dalloc<double>(M * (size_t)nv);
         Q.rx = C.dalloc<double>(M * d.n); Q.robj = C.dalloc<double>(M);
         Q.rstat = C.dalloc<int>(M); Q.riter = C.dalloc<int>(M);
         if (keep_multipliers) {
@@ -2277,33 +2276,39 @@ extern "C" int sqphip_qcqp_stream_begin(sqphip_ctx *h, int32_t n_scenarios, int3
     });
 }
 
-extern "C" int sqphip_qcqp_stream_set(sqphip_ctx *h, int32_t scen, const double *xL, const double *xU, const double *gL,
-                                      const double *gU, const double *f0, const double *c, const double *q0v,
-                                      const double *g0, const double *av, const double *qv, const double *x0)
+// the checks of a scenario that both value queues share (fn: the entry point, for the message); NULL bounds become those
+// of sqphip_create
+static int value_stream_check(sqphip_ctx *h, const char *fn, int32_t scen, const double *&xL, const double *&xU,
+                              const double *&gL, const double *&gU, const double *x0)
 {
-    if (!h) return SQPHIP_EINVAL;
-    if (!h->c.d.qc || !h->c.d.stream.qcv) { h->c.err = "sqphip_qcqp_stream_set: no QCQP queue (sqphip_qcqp_stream_begin)"; return SQPHIP_EINVAL; }
+    const std::string f(fn);
     if (scen < 0 || scen >= h->c.d.stream.M) {
-        h->c.err = "sqphip_qcqp_stream_set: scenario " + std::to_string(scen) + " is outside the " + std::to_string(h->c.d.stream.M) + " of the queue";
+        h->c.err = f + ": scenario " + std::to_string(scen) + " is outside the " + std::to_string(h->c.d.stream.M) + " of the queue";
         return SQPHIP_EINVAL;
     }
-    if (!x0) { h->c.err = "sqphip_qcqp_stream_set: x0 is NULL (a scenario needs its start)"; return SQPHIP_EINVAL; }
-    // NULL bounds: those of sqphip_create
+    if (!x0) { h->c.err = f + ": x0 is NULL (a scenario needs its start)"; return SQPHIP_EINVAL; }
     if (!xL) xL = h->c.h_xL.data();
     if (!xU) xU = h->c.h_xU.data();
     if (!gL) gL = h->c.h_gL.data();
     if (!gU) gU = h->c.h_gU.data();
     for (int i = 0; i < h->c.d.m; ++i) {
         if (gL[i] == -INFINITY && gU[i] == INFINITY) {
-            h->c.err = "sqphip_qcqp_stream_set: row " + std::to_string(i) + " is unbounded on both sides";
+            h->c.err = f + ": row " + std::to_string(i) + " is unbounded on both sides";
             return SQPHIP_EINVAL;
         }
         if (h->c.d.condense && gL[i] == gU[i] && h->c.h_kpos[i] < 0) {
-            h->c.err = "sqphip_qcqp_stream_set: row " + std::to_string(i) + " is an equality for this scenario but was not one when "
+            h->c.err = f + ": row " + std::to_string(i) + " is an equality for this scenario but was not one when "
                        "the context was created (options.kkt_condense = 1 fixes the kept rows)";
             return SQPHIP_EINVAL;
         }
     }
+    return SQPHIP_OK;
+}
+
+// ... and the upload: bounds, start and the block v of nv values
+static int value_stream_upload(sqphip_ctx *h, int32_t scen, const double *xL, const double *xU, const double *gL,
+                               const double *gU, const double *x0, const std::vector<double> &v)
+{
     return guarded(h, [&](Ctx &C) {
         DV &d = C.d;
         const StreamDev &Q = d.stream;
@@ -2311,15 +2316,58 @@ extern "C" int sqphip_qcqp_stream_set(sqphip_ctx *h, int32_t scen, const double 
         h2d(C, const_cast<double *>(Q.xL) + s * d.n, xL, d.n); h2d(C, const_cast<double *>(Q.xU) + s * d.n, xU, d.n);
         h2d(C, const_cast<double *>(Q.x0) + s * d.n, x0, d.n);
         h2d(C, const_cast<double *>(Q.gL) + s * d.m, gL, d.m); h2d(C, const_cast<double *>(Q.gU) + s * d.m, gU, d.m);
-        // the scenario's block: the values of the attach, overlaid with the parts given (f0 | c | Q0 | g0 | A | Q)
-        std::vector<double> v(C.h_qc_base);
-        const long *o = C.qc_off;
-        const double *src[6] = {f0, c, q0v, g0, av, qv};
-        for (int k = 0; k < 6; ++k) if (src[k]) std::copy(src[k], src[k] + (o[k + 1] - o[k]), v.begin() + o[k]);
-        h2d(C, const_cast<double *>(Q.qcv) + s * (size_t)C.qc_nv, v.data(), v.size());
+        h2d(C, const_cast<double *>(Q.val) + s * v.size(), v.data(), v.size());
         SQPHIP_HIP_OK(hipStreamSynchronize(C.stream));
         return SQPHIP_OK;
     });
+}
+
+extern "C" int sqphip_qcqp_stream_begin(sqphip_ctx *h, int32_t n_scenarios, int32_t keep_multipliers)
+{
+    if (!h) return SQPHIP_EINVAL;
+    if (!h->c.d.qc) { h->c.err = "sqphip_qcqp_stream_begin: the context has no QCQP attached (sqphip_qcqp_attach)"; return SQPHIP_EINVAL; }
+    if (n_scenarios <= 0) { h->c.err = "sqphip_qcqp_stream_begin: n_scenarios must be positive"; return SQPHIP_EINVAL; }
+    return value_stream_begin(h, n_scenarios, keep_multipliers, h->c.qc_nv);
+}
+
+extern "C" int sqphip_qcqp_stream_set(sqphip_ctx *h, int32_t scen, const double *xL, const double *xU, const double *gL,
+                                      const double *gU, const double *f0, const double *c, const double *q0v,
+                                      const double *g0, const double *av, const double *qv, const double *x0)
+{
+    if (!h) return SQPHIP_EINVAL;
+    if (!h->c.d.qc || !h->c.d.stream.val) { h->c.err = "sqphip_qcqp_stream_set: no QCQP queue (sqphip_qcqp_stream_begin)"; return SQPHIP_EINVAL; }
+    if (int rc = value_stream_check(h, "sqphip_qcqp_stream_set", scen, xL, xU, gL, gU, x0)) return rc;
+    // the scenario's block: the values of the attach, overlaid with the parts given (f0 | c | Q0 | g0 | A | Q)
+    std::vector<double> v(h->c.h_qc_base);
+    const long *o = h->c.qc_off;
+    const double *src[6] = {f0, c, q0v, g0, av, qv};
+    for (int k = 0; k < 6; ++k) if (src[k]) std::copy(src[k], src[k] + (o[k + 1] - o[k]), v.begin() + o[k]);
+    return value_stream_upload(h, scen, xL, xU, gL, gU, x0, v);
+}
+
+// ---- the queue on a factorable-NLP context: the same tables, the block in the layout of DV::nlv (f0 | g0 | c, padded to even)
+extern "C" int sqphip_nlp_stream_begin(sqphip_ctx *h, int32_t n_scenarios, int32_t keep_multipliers)
+{
+    if (!h) return SQPHIP_EINVAL;
+    if (!h->c.d.nlp) { h->c.err = "sqphip_nlp_stream_begin: the context has no factorable NLP attached (sqphip_nlp_attach)"; return SQPHIP_EINVAL; }
+    if (n_scenarios <= 0) { h->c.err = "sqphip_nlp_stream_begin: n_scenarios must be positive"; return SQPHIP_EINVAL; }
+    return value_stream_begin(h, n_scenarios, keep_multipliers, h->c.nl_nv);
+}
+
+extern "C" int sqphip_nlp_stream_set(sqphip_ctx *h, int32_t scen, const double *xL, const double *xU, const double *gL,
+                                     const double *gU, const double *f0, const double *g0, const double *tcoef,
+                                     const double *x0)
+{
+    if (!h) return SQPHIP_EINVAL;
+    if (!h->c.d.nlp || !h->c.d.stream.val) { h->c.err = "sqphip_nlp_stream_set: no NLP queue (sqphip_nlp_stream_begin)"; return SQPHIP_EINVAL; }
+    if (int rc = value_stream_check(h, "sqphip_nlp_stream_set", scen, xL, xU, gL, gU, x0)) return rc;
+    // the scenario's block: the values of the attach, overlaid with the parts given
+    std::vector<double> v(h->c.h_nl_base);
+    const long m = h->c.d.m;
+    if (f0) v[0] = *f0;
+    if (g0) std::copy(g0, g0 + m, v.begin() + 1);
+    if (tcoef) std::copy(tcoef, tcoef + h->c.nl_nterms, v.begin() + 1 + m);
+    return value_stream_upload(h, scen, xL, xU, gL, gU, x0, v);
 }
 
 extern "C" int sqphip_sqp_stream_get_full(sqphip_ctx *h, int32_t scen, double *x, double *g, double *mult_g, double *mult_x_L,
@@ -2327,7 +2375,7 @@ extern "C" int sqphip_sqp_stream_get_full(sqphip_ctx *h, int32_t scen, double *x
 {
     if (!h || scen < 0 || scen >= h->c.d.stream.M) return SQPHIP_EINVAL;
     if (!h->c.d.stream.rE) {
-        h->c.err = "sqphip_sqp_stream_get_full: the queue keeps no multipliers (sqphip_qcqp_stream_begin with keep_multipliers = 1)";
+        h->c.err = "sqphip_sqp_stream_get_full: the queue keeps no multipliers (sqphip_qcqp_stream_begin / sqphip_nlp_stream_begin with keep_multipliers = 1)";
         return SQPHIP_ESTATE;
     }
     return guarded(h, [&](Ctx &C) {

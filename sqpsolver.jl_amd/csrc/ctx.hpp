@@ -122,8 +122,9 @@ struct StreamDev {
     const double *xL, *xU, *gL, *gU, *ohm, *c2, *c1, *x0;   // [M][.] scenario tables
     double *rx, *robj;                                // results: final point [M][n], objective
     int *rstat, *riter;                               // ... run! status (src/status.jl), iterations
-    // queue of a QCQP context (sqphip_qcqp_stream_*; the ohm / c2 / c1 tables are null there)
-    const double *qcv;                                // [M][qc->nv] values of the scenarios, the layout of DV::qcv
+    // queue of a QCQP or factorable-NLP context (sqphip_qcqp_stream_* / sqphip_nlp_stream_*; the ohm / c2 / c1 tables are
+    // null there)
+    const double *val;                                // [M][qc->nv | nlp->nv] values of the scenarios, the layout of DV::qcv / DV::nlv
     double *rE, *rlam, *rmxL, *rmxU;                  // keep_multipliers: g [M][m], lambda [M][m], mult_x_L / _U [M][n] as the
                                                       // device holds them (signs: sqphip_sqp_stream_get_full); null: not kept
 };
@@ -275,6 +276,7 @@ struct Ctx {
     long qc_off[7] = {};        // ... and where its parts start: f0, c, Q0, g0, A, Q, end
     std::vector<double> h_qc_base;              // ... the values given to sqphip_qcqp_attach (NULL parts of a queue scenario)
     long nl_nv = 0, nl_nfac = 0, nl_nterms = 0; // doubles per instance of an attached factorable NLP (DV::nlv: f0 | g0 | c, padded to even), its factors and terms
+    std::vector<double> h_nl_base;              // ... the values given to sqphip_nlp_attach (NULL parts of a queue scenario)
     std::vector<double> h_xL, h_xU, h_gL, h_gU; // the bounds given to sqphip_create (NULL bounds of a queue scenario)
     bool acopf_attached = false;
     bool mf_big_lds = false;        // the multifrontal kernels were granted 160 KB of dynamic LDS on this context's device (mf_device_setup)

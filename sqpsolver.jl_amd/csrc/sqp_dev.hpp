@@ -452,8 +452,35 @@ static __device__ __forceinline__ void b_sqp_soc_finish(const DV &d)
 
 // Scenario queue (ctx.hpp StreamDev): a slot whose run has terminated files its result under its scenario id, takes the
 // next id, loads that scenario and runs the prologue of run! -- all inside the stage kernel of the sweep in which the
-// run ended, so the slot never idles while scenarios are left.  On a QCQP context (sqphip_qcqp_stream_*) the scenario's
-// data is its block of values; with keep_multipliers the row values and the multipliers are filed next to the point.
+// run ended, so the slot never idles while scenarios are left.  On a QCQP or factorable-NLP context (sqphip_qcqp_stream_*,
+// sqphip_nlp_stream_*) the scenario's data is its block of values; with keep_multipliers the row values and the multipliers
+// are filed next to the point.
+
+// The block copy of those two loaders: 2 nv2 doubles from a scenario's block of StreamDev::val into the slot's block of
+// DV::qcv / DV::nlv.  The strides are even and both arrays come from the allocator, so every block is 16-byte aligned: two
+// values per access, two accesses in flight per thread, every load of an iteration before its stores.
+static __device__ __forceinline__ void stream_copy_block(double *dst, const double *src, int nv2)
+{
+    const double2 *sv = reinterpret_cast<const double2 *>(src);
+    double2 *vw = reinterpret_cast<double2 *>(dst);
+    for (int k = threadIdx.x; k < nv2; k += 2 * TPB) {
+        const bool two = k + TPB < nv2;
+        const double2 a = sv[k], b = two ? sv[k + TPB] : a;
+        vw[k] = a;
+        if (two) vw[k + TPB] = b;
+    }
+}
+
+// ... and their copy of the scenario's bounds and start (one access in flight per table)
+static __device__ __forceinline__ void stream_copy_bounds(const DV &d, const StreamDev &Q, int sc, long on, long om)
+{
+    double *xLw = d.xL + on, *xUw = d.xU + on, *gLw = d.gL + om, *gUw = d.gU + om, *x0w = d.x0 + on;
+    const double *sxL = Q.xL + (long)sc * d.n, *sxU = Q.xU + (long)sc * d.n, *sx0 = Q.x0 + (long)sc * d.n;
+    const double *sgL = Q.gL + (long)sc * d.m, *sgU = Q.gU + (long)sc * d.m;
+    for (int j = threadIdx.x; j < d.n; j += TPB) { const double a = sxL[j], b = sxU[j], c = sx0[j]; xLw[j] = a; xUw[j] = b; x0w[j] = c; }
+    for (int i = threadIdx.x; i < d.m; i += TPB) { const double a = sgL[i], b = sgU[i]; gLw[i] = a; gUw[i] = b; }
+}
+
 static __device__ __forceinline__ void b_sqp_stream(const DV &d)
 {
     const int inst = blockIdx.x;
@@ -487,22 +514,18 @@ static __device__ __forceinline__ void b_sqp_stream(const DV &d)
     }
     if (d.qc) {
         // A QCQP scenario is one block of qc->nv values in the layout of the slot's block of DV::qcv, next to its bounds and
-        // start.  nv is even and both arrays come from the allocator, so every block is 16-byte aligned: two values per
-        // access, two accesses in flight per thread, every load of an iteration before its stores.
-        double *xLw = d.xL + on, *xUw = d.xU + on, *gLw = d.gL + om, *gUw = d.gU + om, *x0w = d.x0 + on;
-        const double *sxL = Q.xL + (long)sc * d.n, *sxU = Q.xU + (long)sc * d.n, *sx0 = Q.x0 + (long)sc * d.n;
-        const double *sgL = Q.gL + (long)sc * d.m, *sgU = Q.gU + (long)sc * d.m;
+        // start.
         const int nv2 = d.qc->nv >> 1;
-        const double2 *sv = reinterpret_cast<const double2 *>(Q.qcv + (long)sc * (2 * nv2));
-        double2 *vw = reinterpret_cast<double2 *>(d.qcv + (long)inst * (2 * nv2));
-        for (int k = threadIdx.x; k < nv2; k += 2 * TPB) {
-            const bool two = k + TPB < nv2;
-            const double2 a = sv[k], b = two ? sv[k + TPB] : a;
-            vw[k] = a;
-            if (two) vw[k + TPB] = b;
-        }
-        for (int j = threadIdx.x; j < d.n; j += TPB) { const double a = sxL[j], b = sxU[j], c = sx0[j]; xLw[j] = a; xUw[j] = b; x0w[j] = c; }
-        for (int i = threadIdx.x; i < d.m; i += TPB) { const double a = sgL[i], b = sgU[i]; gLw[i] = a; gUw[i] = b; }
+        stream_copy_block(d.qcv + (long)inst * (2 * nv2), Q.val + (long)sc * (2 * nv2), nv2);
+        stream_copy_bounds(d, Q, sc, on, om);
+    } else if (d.nlp) {
+        // The same for a factorable NLP: nlp->nv values (f0 | g0 | c, padded to even) into the slot's block of DV::nlv.  The
+        // factor workspace DV::nlw needs no reset: every evaluation rewrites in its first pass what its second pass reads
+        // (phi always, phi' / phi'' whenever a plan that reads them runs), behind the barrier at the entry of nlp_eval --
+        // and the barrier below orders this copy before the first evaluation of the new scenario (b_sqp_begin).
+        const int nv2 = d.nlp->nv >> 1;
+        stream_copy_block(d.nlv + (long)inst * (2 * nv2), Q.val + (long)sc * (2 * nv2), nv2);
+        stream_copy_bounds(d, Q, sc, on, om);
     } else {
         double *xLw = d.xL + on, *xUw = d.xU + on, *gLw = d.gL + om, *gUw = d.gU + om, *x0w = d.x0 + on;
         double *ohm = d.br_ohm + (long)inst * d.nl * 12, *c2 = d.c2 + (long)inst * d.ng, *c1 = d.c1 + (long)inst * d.ng;

@@ -660,6 +660,25 @@ class Context:
         arr = [None if values.get(k) is None else _f(np.atleast_1d(values[k])) for k in bnames + names]
         self._ck(self.L.sqphip_qcqp_stream_set(self.h, int(scen), *[_d(a) for a in arr], _d(_f(x0))))
 
+    # ... on a factorable-NLP context (nlp_attach): the same calls are shared
+    def nlp_stream_begin(self, n_scenarios, keep_multipliers=False):
+        """Tables for n_scenarios (sqphip_nlp_stream_begin); keep_multipliers: stream_get_full returns g and the multipliers."""
+        self._ck(self.L.sqphip_nlp_stream_begin(self.h, int(n_scenarios), int(bool(keep_multipliers))))
+
+    def nlp_stream_set(self, scen, p=None, x0=None, **values):
+        """One scenario (sqphip_nlp_stream_set), with the conventions of qcqp_stream_set.  With an NlpTerms p: its bounds, every
+        value and its start; keywords f0, g0, tcoef override single parts and xL, xU, gL, gU single bounds.  A value given
+        neither way is the one of nlp_attach, a bound given neither way the one the context was created with."""
+        names, bnames = ("f0", "g0", "tcoef"), ("xL", "xU", "gL", "gU")
+        if p is not None:
+            values = {**{k: getattr(p, k) for k in names + bnames}, **values}
+            x0 = p.x0 if x0 is None else x0
+        bad = set(values) - set(names + bnames)
+        if bad:
+            raise TypeError(f"nlp_stream_set: unknown values {sorted(bad)}")
+        arr = [None if values.get(k) is None else _f(np.atleast_1d(values[k])) for k in bnames + names]
+        self._ck(self.L.sqphip_nlp_stream_set(self.h, int(scen), *[_d(a) for a in arr], _d(_f(x0))))
+
     def stream_get_full(self, scen):
         """The dict of sqp_get for a scenario of a queue begun with keep_multipliers (sqphip_sqp_stream_get_full)."""
         x = np.zeros(self.n); g = np.zeros(self.m); mg = np.zeros(self.m)

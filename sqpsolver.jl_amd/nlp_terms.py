@@ -190,13 +190,14 @@ def nlp_terms_synth(n: int = 24, m: int = 14, seed: int = 1, terms_per_row: int 
     return p
 
 
-def nlp_terms_scenario(p: NlpTerms, s: int, seed: int = 1) -> NlpTerms:
-    """Scenario s of p (s = 0: p itself): every coefficient scaled by 1 + 5 % noise, g0 moved so that every row keeps its
-    value at x0 -- the bounds (and the feasibility of x0) stay."""
+def nlp_terms_scenario(p: NlpTerms, s: int, seed: int = 1, noise: float = 0.05) -> NlpTerms:
+    """Scenario s of p (s = 0: p itself): every coefficient scaled by 1 + noise * N(0, 1) (5 % by default), g0 moved so
+    that every row keeps its value at x0 -- the bounds (and the feasibility of x0) stay.  A larger noise spreads the
+    iteration counts of the scenarios (the queue tests: slots that refill at different times)."""
     if s == 0:
         return p
     rng = np.random.default_rng(seed * 1000 + s)
-    out = dataclasses.replace(p, tcoef=p.tcoef * (1.0 + 0.05 * rng.standard_normal(len(p.tcoef))), f0=p.f0 + 0.1 * s)
+    out = dataclasses.replace(p, tcoef=p.tcoef * (1.0 + noise * rng.standard_normal(len(p.tcoef))), f0=p.f0 + 0.1 * s)
     out.g0 = p.g0 + (nlp_terms_rows(p, p.x0) - nlp_terms_rows(out, p.x0))
     return out
 
