@@ -388,6 +388,41 @@ int sqphip_nlp_attach(sqphip_ctx *ctx, int64_t nterms, const int64_t *trow /* 0:
                       const int64_t *fvar /* 1-based */, const int32_t *fkind, const int32_t *fexp,
                       const double *fscale, const double *fshift /* either may be NULL: 1 and 0 */,
                       const double *g0 /* [m] or NULL */, double f0);
+/* The same model with factors of affine multi-variable arguments -- least-squares residuals (a'x - b)^2, exp(a'x),
+ * log(a'x + b), 1 / (a'x + b), sin(th_f - th_t):
+ *     factor k = kappa(u_k),   u_k = sum_{j = aptr[k] .. aptr[k + 1] - 1} acoef[j] x_{avar[j]} + fshift[k]
+ * with kappa = fkind[k] from the menu above (fexp for POW, 1 <= |e| <= 32).  u is summed in argument order and the shift
+ * is added last: u = 0, then u = fma(acoef[j], x, u) for every argument -- each step one fused multiply-add, so only the
+ * first product is rounded on its own --, then u + fshift[k].  An evaluator that rounds every product separately follows
+ * the same order and agrees to a few units in the last place of the largest partial sum (about 1e-13 relative in the
+ * outputs), not bit for bit.  A factor of one argument is evaluated as sqphip_nlp_attach evaluates it, u = a x + b in one
+ * fused expression.  Term t has the factors tptr[t] .. tptr[t + 1] - 1, at least 1 and at most 8; a factor
+ * has at least 1 and at most 8 arguments; the variables of a term are distinct across all arguments of all its factors
+ * (so every Hessian entry of a term is a single product).  A term of rows 1..num_linear is a single POW factor with
+ * e = 1, one argument with coefficient 1 and shift 0.
+ * The context must have been created with a Jacobian COO that holds (i, v) for every argument of every factor of a term
+ * of row i and -- unless nnzH = 0 -- a Hessian COO that holds the lower entry (v, w) for every two distinct variables of
+ * one term, except two arguments of the same plain linear factor (POW, e = 1: kappa'' = 0), and (v, v) for every argument
+ * of a factor that is not plain linear.  With v in factor a and w in factor b the device files
+ *     d/dx_v = c a_v kappa'_a prod_{k != a} kappa_k,    d2/dx_v dx_w = c a_v a_w kappa'_a kappa'_b prod_{others}  (a != b),
+ *     d2/dx_v dx_w = c a_v a_w kappa''_a prod_{k != a} kappa_k  (a = b, v = w included),
+ * products in factor order, one thread per output entry summing in term order, no atomics (bit-reproducible,
+ * independent of the slot).  A model with one argument per factor files the bits it files through sqphip_nlp_attach.
+ * The structure, acoef included, is shared by the batch; an instance's values are f0 | g0 | c as above, so
+ * sqphip_nlp_set_instance, sqphip_nlp_stream_begin / _set, sqphip_sqp_stream_* and everything sqphip_nlp_attach lists
+ * work on such a context unchanged (it is an NLP context to every other entry point).
+ * Domain is the caller's business, as above: LOG and negative powers need u > 0 at every point the solver visits.
+ * Returns SQPHIP_EINVAL, sqphip_last_error naming the 1-based term and factor, on aptr[0] != 0 or a decreasing aptr, a
+ * factor with no or with more than 8 arguments, a variable out of range, a variable twice in one factor or twice across
+ * the factors of one term, an unknown kind, an exponent of 0 or beyond +-32, a term with no or with more than 8 factors,
+ * a term in a linear row that is not the plain one above, or a Jacobian / Hessian entry (named) that the COO structures
+ * lack; SQPHIP_ESTATE on a context attached before (any *_attach). */
+int sqphip_nlp_attach_affine(sqphip_ctx *ctx, int64_t nterms, const int64_t *trow, const double *tcoef,
+                             const int64_t *tptr /* [nterms + 1] factors of a term */,
+                             const int64_t *aptr /* [nfac + 1] arguments of a factor */,
+                             const int64_t *avar /* [nargs] 1-based */, const double *acoef /* [nargs] or NULL: ones */,
+                             const int32_t *fkind, const int32_t *fexp, const double *fshift /* [nfac] or NULL: zeros */,
+                             const double *g0 /* [m] or NULL */, double f0);
 /* Per-instance values (f0 one value, g0 [m], tcoef [nterms] in the term order of the attach) and the start x0 [n];
  * any pointer may be NULL: keep.  Bounds go through sqphip_set_bounds. */
 int sqphip_nlp_set_instance(sqphip_ctx *ctx, int32_t inst, const double *f0, const double *g0,

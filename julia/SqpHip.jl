@@ -235,6 +235,16 @@ hip_nlp_attach(ctx::Ptr{Cvoid}, trow::Vector{Int64}, tcoef::Vector{Float64}, tpt
                       (Ptr{Cvoid}, Int64, Ptr{Int64}, Ptr{Cdouble}, Ptr{Int64}, Ptr{Int64}, Ptr{Int32}, Ptr{Int32},
                        Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Cdouble),
                       ctx, length(trow), trow, tcoef, tptr, fvar, fkind, fexp, fscale, fshift, g0, f0))
+# ... with factors of affine multi-variable arguments (sqphip_nlp_attach_affine): factor k is kappa(sum_j acoef[j] x_avar[j] +
+# fshift[k]) over the arguments aptr[k] + 1 : aptr[k + 1] (0-based offsets, nfac + 1 long; avar is 1-based), 1 to 8 of them,
+# all variables of a term distinct.  Per-instance values and the scenario queue as for hip_nlp_attach.
+hip_nlp_attach_affine(ctx::Ptr{Cvoid}, trow::Vector{Int64}, tcoef::Vector{Float64}, tptr::Vector{Int64}, aptr::Vector{Int64},
+                      avar::Vector{Int64}, acoef::Vector{Float64}, fkind::Vector{Int32}, fexp::Vector{Int32},
+                      fshift::Vector{Float64}, g0::Vector{Float64}, f0::Real) =
+    _check(ctx, ccall((:sqphip_nlp_attach_affine, LIBSQPHIP), Cint,
+                      (Ptr{Cvoid}, Int64, Ptr{Int64}, Ptr{Cdouble}, Ptr{Int64}, Ptr{Int64}, Ptr{Int64}, Ptr{Cdouble}, Ptr{Int32},
+                       Ptr{Int32}, Ptr{Cdouble}, Ptr{Cdouble}, Cdouble),
+                      ctx, length(trow), trow, tcoef, tptr, aptr, avar, acoef, fkind, fexp, fshift, g0, f0))
 hip_nlp_set_instance(ctx::Ptr{Cvoid}, inst::Integer; f0 = nothing, g0 = nothing, tcoef = nothing, x0 = nothing) =
     _check(ctx, ccall((:sqphip_nlp_set_instance, LIBSQPHIP), Cint,
                       (Ptr{Cvoid}, Int32, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}),

@@ -1637,9 +1637,9 @@ extern "C" int sqphip_qcqp_set_instance(sqphip_ctx *h, int32_t inst, const doubl
 
 // ---- a sparse factorable NLP (nlp_dev.hpp nlp_eval): sums of products of univariate functions.  The gather plans are
 // built here, once, from the terms and the COO structures of sqphip_create
-static int nlp_fail(sqphip_ctx *h, int64_t t, int64_t k, const std::string &msg)
+static int nlp_fail(sqphip_ctx *h, const char *who, int64_t t, int64_t k, const std::string &msg)
 {
-    h->c.err = "sqphip_nlp_attach: term " + std::to_string(t + 1) + (k >= 0 ? " factor " + std::to_string(k + 1) : std::string()) + ": " + msg;
+    h->c.err = std::string(who) + ": term " + std::to_string(t + 1) + (k >= 0 ? " factor " + std::to_string(k + 1) : std::string()) + ": " + msg;
     return SQPHIP_EINVAL;
 }
 
@@ -1654,25 +1654,41 @@ static void plan_order(int owners, const std::vector<int> &own, std::vector<int>
     for (size_t e = 0; e < own.size(); ++e) ord[fill[own[e]]++] = (int)e;
 }
 
-extern "C" int sqphip_nlp_attach(sqphip_ctx *h, int64_t nterms, const int64_t *trow, const double *tcoef, const int64_t *tptr,
-                                 const int64_t *fvar, const int32_t *fkind, const int32_t *fexp, const double *fscale,
-                                 const double *fshift, const double *g0, double f0)
+// Both entry points.  !affine: sqphip_nlp_attach, aptr is null and factor k has the one argument avar[k] with coefficient acoef[k].
+// A one-argument factor keeps its coefficient in pass 1 (fab, chain factors folded into phi', phi'') and weight 1.0 in the
+// plans; a factor of several arguments stores kappa', kappa'' and its arguments weigh a_v (nlp_dev.hpp).
+static int nlp_attach_impl(sqphip_ctx *h, const char *who, bool affine, int64_t nterms, const int64_t *trow, const double *tcoef, const int64_t *tptr,
+                           const int64_t *aptr, const int64_t *avar, const double *acoef, const int32_t *fkind, const int32_t *fexp,
+                           const double *fshift, const double *g0, double f0)
 {
     if (!h) return SQPHIP_EINVAL;
     Ctx &C0 = h->c;
     if (C0.acopf_attached) {
-        C0.err = "sqphip_nlp_attach: the context already has device callbacks (an earlier *_attach)";
+        C0.err = std::string(who) + ": the context already has device callbacks (an earlier *_attach)";
         return SQPHIP_ESTATE;
     }
-    auto fail = [&](const char *msg) { C0.err = std::string("sqphip_nlp_attach: ") + msg; return (int)SQPHIP_EINVAL; };
+    auto fail = [&](const char *msg) { C0.err = std::string(who) + ": " + msg; return (int)SQPHIP_EINVAL; };
+    if (affine && !aptr) return fail("null aptr");
     if (nterms < 0) return fail("negative term count");
     if (!tptr || (nterms > 0 && (!trow || !tcoef))) return fail("null term array");
     if (tptr[0] != 0) return fail("tptr[0] must be 0");
     for (int64_t t = 0; t < nterms; ++t)
-        if (tptr[t + 1] < tptr[t]) return nlp_fail(h, t, -1, "tptr decreases");
+        if (tptr[t + 1] < tptr[t]) return nlp_fail(h, who, t, -1, "tptr decreases");
     const int64_t nfac = tptr[nterms];
-    if (nfac > 0 && (!fvar || !fkind || !fexp)) return fail("null factor array");
+    if (nfac > 0 && (!avar || !fkind || !fexp)) return fail("null factor array");
     if (nfac > (1 << 28) || nterms > (1 << 28)) return fail("too many terms");
+    if (affine) {
+        if (aptr[0] != 0) return fail("aptr[0] must be 0");
+        for (int64_t t = 0; t < nterms; ++t)
+            for (int64_t k = tptr[t]; k < tptr[t + 1]; ++k) {
+                if (aptr[k + 1] < aptr[k]) return nlp_fail(h, who, t, k - tptr[t], "aptr decreases");
+                if (aptr[k + 1] == aptr[k]) return nlp_fail(h, who, t, k - tptr[t], "no arguments");
+                if (aptr[k + 1] - aptr[k] > 8) return nlp_fail(h, who, t, k - tptr[t], "more than 8 arguments");
+            }
+    }
+    const int64_t nargs = affine ? aptr[nfac] : nfac;
+    if (nargs > (1 << 28)) return fail("too many arguments");
+    auto a0 = [&](int64_t k) { return affine ? aptr[k] : k; };
     const int64_t n = C0.d.n, m = C0.d.m, nlin = C0.d.nlin, nnzJ = C0.d.nnzj_coo, nnzH = C0.d.nnzh_coo;
     // first COO slot of every structural entry (later duplicates get no plan entries: 0, gather_csc sums them)
     std::unordered_map<int64_t, int> jslot, hslot;
@@ -1689,44 +1705,66 @@ extern "C" int sqphip_nlp_attach(sqphip_ctx *h, int64_t nterms, const int64_t *t
     std::vector<int4> h_e;
     std::vector<int> fke((size_t)std::max<int64_t>(nfac, 1), 0), fv(fke.size(), 0);
     std::vector<double2> fab(fke.size(), double2{1.0, 0.0});
+    std::vector<int> ap((size_t)nfac + 1, 0), av((size_t)std::max<int64_t>(nargs, 1), 0);
+    std::vector<double> ac(av.size(), 1.0), aw(av.size(), 1.0);
+    bool multi = false;
     for (int64_t t = 0; t < nterms; ++t) {
         const int64_t i = trow[t], k0 = tptr[t], k1 = tptr[t + 1];
-        if (i < 0 || i > m) return nlp_fail(h, t, -1, "row " + std::to_string(i) + " out of range (0: objective, 1.." + std::to_string(m) + ")");
-        if (k1 == k0) return nlp_fail(h, t, -1, "no factors (a constant belongs in f0 / g0)");
-        if (k1 - k0 > 8) return nlp_fail(h, t, -1, "more than 8 factors");
+        if (i < 0 || i > m) return nlp_fail(h, who, t, -1, "row " + std::to_string(i) + " out of range (0: objective, 1.." + std::to_string(m) + ")");
+        if (k1 == k0) return nlp_fail(h, who, t, -1, "no factors (a constant belongs in f0 / g0)");
+        if (k1 - k0 > 8) return nlp_fail(h, who, t, -1, "more than 8 factors");
         bool plain[8];
         for (int64_t k = k0; k < k1; ++k) {
-            const int64_t v = fvar[k] - 1, kf = k - k0;
-            const double a = fscale ? fscale[k] : 1.0, b = fshift ? fshift[k] : 0.0;
-            if (v < 0 || v >= n) return nlp_fail(h, t, kf, "variable " + std::to_string(fvar[k]) + " out of range");
-            if (fkind[k] < NLP_POW || fkind[k] > NLP_LOG) return nlp_fail(h, t, kf, "unknown kind " + std::to_string(fkind[k]));
+            const int64_t kf = k - k0, j0 = a0(k), j1 = a0(k + 1);
+            const double b = fshift ? fshift[k] : 0.0;
+            for (int64_t j = j0; j < j1; ++j)
+                if (avar[j] < 1 || avar[j] > n) return nlp_fail(h, who, t, kf, "variable " + std::to_string(avar[j]) + " out of range");
+            if (fkind[k] < NLP_POW || fkind[k] > NLP_LOG) return nlp_fail(h, who, t, kf, "unknown kind " + std::to_string(fkind[k]));
             const int e = fkind[k] == NLP_POW ? fexp[k] : 1;
-            if (e == 0 || e > 32 || e < -32) return nlp_fail(h, t, kf, "exponent " + std::to_string(e) + " (1 <= |e| <= 32)");
-            for (int64_t k2 = k0; k2 < k; ++k2)
-                if (fvar[k2] == fvar[k]) return nlp_fail(h, t, kf, "variable " + std::to_string(fvar[k]) + " twice in one term (write x^2)");
+            if (e == 0 || e > 32 || e < -32) return nlp_fail(h, who, t, kf, "exponent " + std::to_string(e) + " (1 <= |e| <= 32)");
+            for (int64_t j = j0; j < j1; ++j) {
+                for (int64_t j2 = j0; j2 < j; ++j2)
+                    if (avar[j2] == avar[j]) return nlp_fail(h, who, t, kf, "variable " + std::to_string(avar[j]) + " twice in one factor (add the coefficients)");
+                for (int64_t j2 = a0(k0); j2 < j0; ++j2)
+                    if (avar[j2] == avar[j]) return nlp_fail(h, who, t, kf, "variable " + std::to_string(avar[j]) + " twice in one term (write x^2)");
+            }
             plain[kf] = fkind[k] == NLP_POW && e == 1;
-            if (i >= 1 && i <= nlin && !(k1 - k0 == 1 && plain[kf] && a == 1.0 && b == 0.0))
-                return nlp_fail(h, t, kf, "row " + std::to_string(i) + " is one of the num_linear = " + std::to_string(nlin) +
-                                          " linear rows: a single POW factor with e = 1, a = 1, b = 0 only");
-            fv[k] = (int)v; fke[k] = fkind[k] + 8 * (e + 32); fab[k] = double2{a, b};
+            const bool one = j1 - j0 == 1;
+            multi = multi || !one;
+            const double a = one && acoef ? acoef[j0] : 1.0;
+            if (i >= 1 && i <= nlin && !(k1 - k0 == 1 && one && plain[kf] && a == 1.0 && b == 0.0))
+                return nlp_fail(h, who, t, kf, "row " + std::to_string(i) + " is one of the num_linear = " + std::to_string(nlin) +
+                                          (affine ? " linear rows: a single POW factor with e = 1, one argument with coefficient 1, shift 0 only"
+                                                  : " linear rows: a single POW factor with e = 1, a = 1, b = 0 only"));
+            fv[k] = one ? (int)avar[j0] - 1 : -1; fke[k] = fkind[k] + 8 * (e + 32); fab[k] = double2{a, b};
+            ap[k] = (int)j0; ap[k + 1] = (int)j1;
+            for (int64_t j = j0; j < j1; ++j) {
+                av[j] = (int)avar[j] - 1; ac[j] = acoef ? acoef[j] : 1.0; aw[j] = one ? 1.0 : ac[j];
+            }
         }
         if (i == 0) ot.push_back((int)t); else { g_own.push_back((int)i - 1); g_t.push_back((int)t); }
-        for (int64_t k = k0; k < k1; ++k) {
-            if (i == 0) { f_own.push_back(fv[k]); f_e.push_back(int2{(int)t, (int)k}); continue; }
-            const int js = jfind(i - 1, fv[k]);
-            if (js < 0) return nlp_fail(h, t, k - k0, "needs the Jacobian entry (" + std::to_string(i) + ", " + std::to_string(fvar[k]) +
-                                                      ") that the structure of sqphip_create lacks");
-            j_own.push_back(js); j_e.push_back(int2{(int)t, (int)k});
-        }
+        // a plan entry names an argument and, in the bits above 2^28, its factor within the term
+        auto ent = [&](int64_t k, int64_t j) { return (int)(j | ((k - k0) << 28)); };
+        for (int64_t k = k0; k < k1; ++k)
+            for (int64_t j = a0(k); j < a0(k + 1); ++j) {
+                if (i == 0) { f_own.push_back(av[j]); f_e.push_back(int2{(int)t, ent(k, j)}); continue; }
+                const int js = jfind(i - 1, av[j]);
+                if (js < 0) return nlp_fail(h, who, t, k - k0, "needs the Jacobian entry (" + std::to_string(i) + ", " + std::to_string(avar[j]) +
+                                                          ") that the structure of sqphip_create lacks");
+                j_own.push_back(js); j_e.push_back(int2{(int)t, ent(k, j)});
+            }
         if (nnzH > 0)
             for (int64_t k = k0; k < k1; ++k)
-                for (int64_t k2 = k0; k2 <= k; ++k2) {
-                    if (k2 == k && plain[k - k0]) continue;            // phi'' = 0
-                    const int hs = hfind(fv[k], fv[k2]);
-                    if (hs < 0) return nlp_fail(h, t, k - k0, "needs the Hessian entry (" + std::to_string(std::max(fvar[k], fvar[k2])) + ", " +
-                                                              std::to_string(std::min(fvar[k], fvar[k2])) + ") that the structure of sqphip_create lacks");
-                    h_own.push_back(hs); h_e.push_back(int4{(int)t, (int)k2, (int)k, (int)i - 1});
-                }
+                for (int64_t j = a0(k); j < a0(k + 1); ++j)
+                    for (int64_t k2 = k0; k2 <= k; ++k2) {
+                        if (k2 == k && plain[k - k0]) continue;            // phi'' = 0
+                        for (int64_t j2 = a0(k2); j2 < (k2 == k ? j + 1 : a0(k2 + 1)); ++j2) {
+                            const int hs = hfind(av[j], av[j2]);
+                            if (hs < 0) return nlp_fail(h, who, t, k - k0, "needs the Hessian entry (" + std::to_string(std::max(avar[j], avar[j2])) + ", " +
+                                                                      std::to_string(std::min(avar[j], avar[j2])) + ") that the structure of sqphip_create lacks");
+                            h_own.push_back(hs); h_e.push_back(int4{(int)t, ent(k2, j2), ent(k, j), (int)i - 1});
+                        }
+                    }
     }
     // CSR by owner, the entries of one owner kept in production (term) order
     std::vector<int> g_ptr, f_ptr, j_ptr, h_ptr, ord;
@@ -1763,6 +1801,7 @@ extern "C" int sqphip_nlp_attach(sqphip_ctx *h, int64_t nterms, const int64_t *t
         P.f_ptr = fp; P.j_ptr = jp; P.h_ptr = hp;
         P.ptr = C.upload(ptr); P.tptr = C.upload(tp); P.fvar = C.upload(fv); P.fke = C.upload(fke); P.fab = C.upload(fab);
         P.ot = C.upload(ot); P.ge = C.upload(ge); P.fe = C.upload(fe); P.je = C.upload(je); P.he = C.upload(he);
+        P.aptr = C.upload(ap); P.avar = C.upload(av); P.acoef = C.upload(ac); P.aw = C.upload(aw); P.multi = multi ? 1 : 0;
         NlpDev *pd = (NlpDev *)C.dalloc<char>(sizeof(NlpDev));
         SQPHIP_HIP_OK(hipMemcpyAsync(pd, &P, sizeof(NlpDev), hipMemcpyHostToDevice, C.stream));
         std::vector<double> all((size_t)d.B * nv);
@@ -1777,6 +1816,20 @@ extern "C" int sqphip_nlp_attach(sqphip_ctx *h, int64_t nterms, const int64_t *t
         make_lanes(C);
         return SQPHIP_OK;
     });
+}
+
+extern "C" int sqphip_nlp_attach(sqphip_ctx *h, int64_t nterms, const int64_t *trow, const double *tcoef, const int64_t *tptr,
+                                 const int64_t *fvar, const int32_t *fkind, const int32_t *fexp, const double *fscale,
+                                 const double *fshift, const double *g0, double f0)
+{
+    return nlp_attach_impl(h, "sqphip_nlp_attach", false, nterms, trow, tcoef, tptr, nullptr, fvar, fscale, fkind, fexp, fshift, g0, f0);
+}
+
+extern "C" int sqphip_nlp_attach_affine(sqphip_ctx *h, int64_t nterms, const int64_t *trow, const double *tcoef, const int64_t *tptr,
+                                        const int64_t *aptr, const int64_t *avar, const double *acoef, const int32_t *fkind,
+                                        const int32_t *fexp, const double *fshift, const double *g0, double f0)
+{
+    return nlp_attach_impl(h, "sqphip_nlp_attach_affine", true, nterms, trow, tcoef, tptr, aptr, avar, acoef, fkind, fexp, fshift, g0, f0);
 }
 
 extern "C" int sqphip_nlp_set_instance(sqphip_ctx *h, int32_t inst, const double *f0, const double *g0, const double *tcoef,

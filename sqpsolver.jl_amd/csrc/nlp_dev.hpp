@@ -13,6 +13,14 @@
 //      c phi'_a phi'_b prod_{others}, c phi''_a prod_{k != a} phi_k, each times sigma or lambda_i.
 // Every output entry is one thread's sum over its plan row in plan order: no atomics, bit-reproducible results that do not
 // depend on the slot an instance sits in.
+// sqphip_nlp_attach_affine: a factor may be kappa(u) of an affine form u = sum_j a_j x_{v_j} + b of up to 8 variables (summed
+// in argument order, the shift added last).  Such a factor stores the plain kappa, kappa', kappa'' in pass 1 and the chain
+// factors a_v (a_v a_w for a Hessian entry) reach pass 2 as the weights aw of its arguments, which the derivative plans name
+// next to (term, factor).  A one-argument factor keeps the arithmetic above -- u = a x + b in one expression, a and a^2
+// folded into phi', phi'' -- and its argument carries the weight 1.0: sqphip_nlp_attach builds such factors only, and
+// c (prod 1.0) rounds as c prod does, so both entry points file the same bits for the same one-argument model.  A context
+// without any multi-argument factor (NlpDev::multi = 0, uniform over the launch) skips the weight loads: the same bits, since
+// the weights it skips are 1.0.
 #pragma once
 #include "ctx.hpp"
 #include "dev_util.hpp"
@@ -21,29 +29,39 @@
 namespace sqphip {
 
 enum { NLP_POW = 0, NLP_SIN = 1, NLP_COS = 2, NLP_EXP = 3, NLP_LOG = 4 };
+enum { NLP_NONE = -(1 << 30), NLP_ARG = (1 << 28) - 1 };     // no factor of a term; the argument bits of a plan entry (nargs <= 2^28)
 
 struct NlpDev {
     int n, m, nterms, nfac, nv, nobj;     // variables, rows, terms, factors, values per instance (even), objective terms
     int f_ptr, j_ptr, h_ptr;              // where the row pointers of the variable / Jacobian / Hessian plans start in ptr
     const int *ptr;                       // the four CSR row pointers back to back: rows [m + 1], variables [n + 1], slots
     const int *tptr;                      // [nterms + 1] factors of a term
-    const int *fvar;                      // [nfac] variable of a factor (0-based)
+    const int *fvar;                      // [nfac] variable of a one-argument factor (0-based); -1: the arguments aptr[k] .. aptr[k + 1] - 1
     const int *fke;                       // [nfac] kind + 8 * (exponent + 32)
     const double2 *fab;                   // [nfac] (a, b)
     const int *ot;                        // [nobj] the objective's terms
     const int *ge;                        // row i: g0_i + sum over terms t
-    const int2 *fe;                       // variable j: sum over (term, factor) of objective terms
-    const int2 *je;                       // Jacobian slot: sum over (term, factor)
-    const int4 *he;                       // Hessian slot: sum over (term, factor a, factor b or a, row or -1) times lambda[row] or sigma
+    const int2 *fe;                       // variable j: sum over (term, argument + 2^28 its factor within the term) of objective terms
+    const int2 *je;                       // Jacobian slot: sum over (term, argument + 2^28 its factor within the term)
+    const int4 *he;                       // Hessian slot: sum over (term, the same for factor a, for factor b or a, row or -1) times
+                                          // lambda[row] or sigma
+    const int *aptr;                      // [nfac + 1] arguments of a factor
+    const int *avar;                      // [nargs] variable of an argument (0-based)
+    const double *acoef;                  // [nargs] its coefficient (pass 1)
+    const double *aw;                     // [nargs] its weight in the derivative plans: the coefficient, 1.0 in a one-argument factor
+    int multi;                            // some factor has several arguments; 0: every weight is 1.0 and the plans do not load aw
 };
 
-// c-free product of term t with factors a and b differentiated (a == b: twice; -1: not at all), in factor order
+// c-free product of term t with its factors a and b (counted within the term) differentiated (a == b: twice;
+// NLP_NONE: not at all), in factor order
 static __device__ __forceinline__ double nlp_prod(const int *__restrict__ tptr, const double *__restrict__ w, int nf, int t,
                                                   int a, int b)
 {
     double p = 1.0;
+    const int k0 = tptr[t];
+    a += k0; b += k0;
     #pragma unroll 1
-    for (int k = tptr[t]; k < tptr[t + 1]; ++k) p *= w[((k == a) + (k == b)) * nf + k];
+    for (int k = k0; k < tptr[t + 1]; ++k) p *= w[((k == a) + (k == b)) * nf + k];
     return p;
 }
 
@@ -94,17 +112,24 @@ static __device__ __forceinline__ void nlp_eval(const DV &d, int inst, const dou
     const double *__restrict__ cf = val + 1 + q.m;
     const int *__restrict__ tptr = q.tptr;
     const bool d1 = grad || jv || hv, d2 = hv != nullptr;     // phi'' is read by the Hessian plan only
+    const bool multi = q.multi != 0;
+    const double *__restrict__ aw = q.aw;
     __syncthreads();                        // x is complete; nobody still reads the workspace of an earlier evaluation
     #pragma unroll 1
     for (int k = threadIdx.x; k < nf; k += TPB) {
         const double2 ab = q.fab[k];
-        nlp_factor(q.fke[k], ab.x, ab.x * x[q.fvar[k]] + ab.y, d1, d2, w, nf, k);
+        const int v = q.fvar[k];
+        if (v >= 0) { nlp_factor(q.fke[k], ab.x, ab.x * x[v] + ab.y, d1, d2, w, nf, k); continue; }
+        double u = 0.0;
+        #pragma unroll 1
+        for (int j = q.aptr[k]; j < q.aptr[k + 1]; ++j) u += q.acoef[j] * x[q.avar[j]];
+        nlp_factor(q.fke[k], 1.0, u + ab.y, d1, d2, w, nf, k);
     }
     __syncthreads();
     if (f_out) {
         double f = 0.0;
         #pragma unroll 1
-        for (int e = threadIdx.x; e < q.nobj; e += TPB) { const int t = q.ot[e]; f += cf[t] * nlp_prod(tptr, w, nf, t, -1, -1); }
+        for (int e = threadIdx.x; e < q.nobj; e += TPB) { const int t = q.ot[e]; f += cf[t] * nlp_prod(tptr, w, nf, t, NLP_NONE, NLP_NONE); }
         f = block_reduce<OpSum>(f);
         if (threadIdx.x == 0) *f_out = val[0] + f;
     }
@@ -114,7 +139,10 @@ static __device__ __forceinline__ void nlp_eval(const DV &d, int inst, const dou
         for (int j = threadIdx.x; j < q.n; j += TPB) {
             double s = 0.0;
             #pragma unroll 1
-            for (int k = ptr[j]; k < ptr[j + 1]; ++k) { const int2 e = q.fe[k]; s += cf[e.x] * nlp_prod(tptr, w, nf, e.x, e.y, -1); }
+            for (int k = ptr[j]; k < ptr[j + 1]; ++k) {
+                const int2 e = q.fe[k];
+                s += cf[e.x] * (nlp_prod(tptr, w, nf, e.x, e.y >> 28, NLP_NONE) * (multi ? aw[e.y & NLP_ARG] : 1.0));
+            }
             grad[j] = s;
         }
     }
@@ -123,7 +151,7 @@ static __device__ __forceinline__ void nlp_eval(const DV &d, int inst, const dou
         for (int i = threadIdx.x; i < q.m; i += TPB) {
             double s = val[1 + i];
             #pragma unroll 1
-            for (int k = q.ptr[i]; k < q.ptr[i + 1]; ++k) { const int t = q.ge[k]; s += cf[t] * nlp_prod(tptr, w, nf, t, -1, -1); }
+            for (int k = q.ptr[i]; k < q.ptr[i + 1]; ++k) { const int t = q.ge[k]; s += cf[t] * nlp_prod(tptr, w, nf, t, NLP_NONE, NLP_NONE); }
             gv[i] = s;
         }
     if (jv) {
@@ -132,7 +160,10 @@ static __device__ __forceinline__ void nlp_eval(const DV &d, int inst, const dou
         for (int s_ = threadIdx.x; s_ < d.nnzj_coo; s_ += TPB) {
             double s = 0.0;
             #pragma unroll 1
-            for (int k = ptr[s_]; k < ptr[s_ + 1]; ++k) { const int2 e = q.je[k]; s += cf[e.x] * nlp_prod(tptr, w, nf, e.x, e.y, -1); }
+            for (int k = ptr[s_]; k < ptr[s_ + 1]; ++k) {
+                const int2 e = q.je[k];
+                s += cf[e.x] * (nlp_prod(tptr, w, nf, e.x, e.y >> 28, NLP_NONE) * (multi ? aw[e.y & NLP_ARG] : 1.0));
+            }
             jv[s_] = s;
         }
     }
@@ -144,7 +175,8 @@ static __device__ __forceinline__ void nlp_eval(const DV &d, int inst, const dou
             #pragma unroll 1
             for (int k = ptr[s_]; k < ptr[s_ + 1]; ++k) {
                 const int4 e = q.he[k];
-                s += cf[e.x] * nlp_prod(tptr, w, nf, e.x, e.y, e.z) * (e.w < 0 ? sigma : lam[e.w]);
+                s += cf[e.x] * (nlp_prod(tptr, w, nf, e.x, e.y >> 28, e.z >> 28) * (multi ? aw[e.y & NLP_ARG] * aw[e.z & NLP_ARG] : 1.0)) *
+                     (e.w < 0 ? sigma : lam[e.w]);
             }
             hv[s_] = s;
         }

@@ -471,7 +471,15 @@ class Context:
 
     # ---- a sparse factorable NLP (nlp_terms.py; csrc/nlp_dev.hpp nlp_eval)
     def nlp_attach(self, p):
-        """Structure of the batch and the values every instance starts with (sqphip_nlp_attach); p: nlp_terms.NlpTerms."""
+        """Structure of the batch and the values every instance starts with; p: nlp_terms.NlpTerms.  A p with argument arrays
+        (affine multi-variable factors) goes through sqphip_nlp_attach_affine, any other through sqphip_nlp_attach."""
+        if getattr(p, "aptr", None) is not None:
+            t = [np.ascontiguousarray(a, dtype=np.int64) for a in (p.trow, p.tptr, p.aptr, p.avar)]
+            k = [np.ascontiguousarray(a, dtype=np.int32) for a in (p.fkind, p.fexp)]
+            v = [_f(a) for a in (p.tcoef, p.acoef, p.fshift, p.g0)]
+            self._ck(self.L.sqphip_nlp_attach_affine(self.h, len(t[0]), _l(t[0]), _d(v[0]), _l(t[1]), _l(t[2]), _l(t[3]), _d(v[1]),
+                                                     _i(k[0]), _i(k[1]), _d(v[2]), _d(v[3]), float(p.f0)))
+            return
         t = [np.ascontiguousarray(a, dtype=np.int64) for a in (p.trow, p.tptr, p.fvar)]
         k = [np.ascontiguousarray(a, dtype=np.int32) for a in (p.fkind, p.fexp)]
         v = [_f(a) for a in (p.tcoef, p.fscale, p.fshift, p.g0)]

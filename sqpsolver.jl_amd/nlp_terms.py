@@ -9,11 +9,19 @@ a = 1, b = 0) only.  The structure (rows, variables, kinds, e, a, b) is shared b
 f0, g0 and term coefficients.  Domain is the caller's business: LOG and negative powers need bounds that keep a x + b
 positive.
 
+A factor may also take an affine form of several variables (sqphip_nlp_attach_affine): kappa(sum_j a_j x_{v_j} + b), 1 to 8
+arguments, the variables of a term distinct across all arguments of all its factors.  Such a problem carries the argument
+arrays aptr / avar / acoef (None in the one-argument form above, where fvar / fscale say it all); in it fvar / fscale hold
+the first argument of every factor.
+
     NlpTerms             the data (terms, factors, values, bounds, start)
-    make_nlp_terms       ... from a list of (row, coefficient, [(variable, kind, e, a, b), ...])
+    make_nlp_terms       ... from a list of (row, coefficient, [(variable, kind, e, a, b), ...]); a factor may be
+                         ([(variable, coefficient), ...], kind, e, b) instead
+    nlp_terms_args       (aptr, avar, acoef) of a problem of either form
     nlp_terms_layout     the structures a Context is created with (1-based Jacobian COO, lower Hessian COO, bounds, start)
     nlp_terms_rows       g(x) in numpy
     nlp_terms_synth      a seeded test problem over the whole menu with a start that satisfies every row
+    nlp_affine_synth     the same with affine arguments and least-squares residuals in the objective
     nlp_terms_scenario   scenario s of a problem: the same structure, other coefficients, the same feasible start
     from_qcqp            a Qcqp (qcqp.py) restated as terms
     from_polar_acopf     the polar ACOPF of acopf_layout restated as terms, on that layout's COO structures
@@ -27,6 +35,7 @@ import numpy as np
 
 POW, SIN, COS, EXP, LOG = 0, 1, 2, 3, 4
 MAX_FACTORS = 8
+MAX_ARGS = 8
 
 
 @dataclasses.dataclass
@@ -49,6 +58,20 @@ class NlpTerms:
     gL: np.ndarray
     gU: np.ndarray
     x0: np.ndarray
+    aptr: np.ndarray | None = None     # [nfac + 1] offsets into the argument arrays; None: one argument per factor (fvar, fscale)
+    avar: np.ndarray | None = None     # [nargs] variable (1-based)
+    acoef: np.ndarray | None = None    # [nargs] coefficient
+
+    @property
+    def affine(self) -> bool:
+        return self.aptr is not None
+
+
+def nlp_terms_args(p: NlpTerms):
+    """(aptr, avar, acoef) of either form."""
+    if p.aptr is not None:
+        return p.aptr, p.avar, p.acoef
+    return np.arange(len(p.fvar) + 1, dtype=np.int64), p.fvar, p.fscale
 
 
 @dataclasses.dataclass
@@ -78,19 +101,30 @@ def _f64(a):
 
 def make_nlp_terms(n, m, num_linear, terms, g0=None, f0=0.0, xL=None, xU=None, gL=None, gU=None, x0=None) -> NlpTerms:
     """terms: (row, coefficient, factors) with row 0 for the objective and factors (variable, kind[, e[, a[, b]]]), 1-based
-    variables; missing vectors are zeros, missing bounds infinite."""
+    variables; a factor may be (args, kind[, e[, b]]) with args a list of (variable, coefficient) pairs, and one such factor
+    makes the problem an affine one (aptr / avar / acoef set).  Missing vectors are zeros, missing bounds infinite."""
     inf = np.inf
     full = lambda v, k, d: _f64(np.full(k, d) if v is None else v)
     trow, tcoef, tptr, fv, fk, fe, fa, fb = [], [], [0], [], [], [], [], []
+    aptr, avar, acoef, affine = [0], [], [], False
     for row, coef, factors in terms:
         trow.append(int(row)); tcoef.append(float(coef))
         for fac in factors:
-            var, kind, e, a, b = (tuple(fac) + (1, 1.0, 0.0)[len(fac) - 2:])[:5]
-            fv.append(int(var)); fk.append(int(kind)); fe.append(int(e)); fa.append(float(a)); fb.append(float(b))
+            if isinstance(fac[0], (list, tuple)):
+                affine = True
+                args, kind, e, b = (tuple(fac) + (1, 0.0)[len(fac) - 2:])[:4]
+                args = [(int(v), float(c)) for v, c in args]
+            else:
+                var, kind, e, a, b = (tuple(fac) + (1, 1.0, 0.0)[len(fac) - 2:])[:5]
+                args = [(int(var), float(a))]
+            fv.append(args[0][0] if args else 0); fa.append(args[0][1] if args else 1.0)
+            fk.append(int(kind)); fe.append(int(e)); fb.append(float(b))
+            avar += [v for v, _ in args]; acoef += [c for _, c in args]; aptr.append(len(avar))
         tptr.append(len(fv))
+    extra = (_i64(aptr), _i64(avar), _f64(acoef)) if affine else ()
     return NlpTerms(n, m, num_linear, _i64(trow), _f64(tcoef), _i64(tptr), _i64(fv), np.ascontiguousarray(fk, dtype=np.int32),
                     np.ascontiguousarray(fe, dtype=np.int32), _f64(fa), _f64(fb), full(g0, m, 0.0), float(f0),
-                    full(xL, n, -inf), full(xU, n, inf), full(gL, m, -inf), full(gU, m, inf), full(x0, n, 0.0))
+                    full(xL, n, -inf), full(xU, n, inf), full(gL, m, -inf), full(gU, m, inf), full(x0, n, 0.0), *extra)
 
 
 def _term_of_factor(p: NlpTerms) -> np.ndarray:
@@ -98,20 +132,27 @@ def _term_of_factor(p: NlpTerms) -> np.ndarray:
 
 
 def nlp_terms_layout(p: NlpTerms) -> NlpTermsLayout:
-    """Jacobian COO: (i, v) of every factor of a term of row i, row-major; Hessian COO: the lower entry (v, w) of every two
-    factors of one term and (v, v) of every factor that is not plain linear (POW, e = 1), column-major.  Each once."""
+    """Jacobian COO: (i, v) of every argument of every factor of a term of row i, row-major; Hessian COO: the lower entry
+    (v, w) of every two distinct variables of one term -- except two arguments of one plain linear factor (POW, e = 1) --
+    and (v, v) of every argument of a factor that is not plain linear, column-major.  Each once."""
     n = p.n
-    tf = _term_of_factor(p)
-    rows = p.trow[tf]
+    aptr, avar, _ = nlp_terms_args(p)
+    nargs = np.diff(aptr)
+    fa = np.repeat(np.arange(len(p.fkind), dtype=np.int64), nargs)      # factor of an argument
+    rows = p.trow[_term_of_factor(p)][fa]
     inrow = rows > 0
-    jkey = np.unique((rows[inrow] - 1) * n + (p.fvar[inrow] - 1))
+    jkey = np.unique((rows[inrow] - 1) * n + (avar[inrow] - 1))
     hk = []
     curved = ~((p.fkind == POW) & (p.fexp == 1))
-    hk.append((p.fvar[curved] - 1) * n + (p.fvar[curved] - 1))
+    ca = curved[fa]
+    hk.append((avar[ca] - 1) * n + (avar[ca] - 1))
     for t in range(len(p.trow)):
-        v = p.fvar[p.tptr[t]:p.tptr[t + 1]]
+        j0, j1 = aptr[p.tptr[t]], aptr[p.tptr[t + 1]]
+        v, f = avar[j0:j1], fa[j0:j1]
         if len(v) > 1:
             a, b = np.triu_indices(len(v), 1)
+            keep = (f[a] != f[b]) | curved[f[a]]
+            a, b = a[keep], b[keep]
             hk.append((np.minimum(v[a], v[b]) - 1) * n + np.maximum(v[a], v[b]) - 1)      # column-major key of the lower entry
     hkey = np.unique(np.concatenate(hk)) if hk else np.zeros(0, np.int64)
     return NlpTermsLayout(n, p.m, p.num_linear, jkey // n + 1, jkey % n + 1, hkey % n + 1, hkey // n + 1,
@@ -120,7 +161,11 @@ def nlp_terms_layout(p: NlpTerms) -> NlpTermsLayout:
 
 def factor_values(p: NlpTerms, x) -> np.ndarray:
     """phi of every factor at x."""
-    u = p.fscale * _f64(x)[p.fvar - 1] + p.fshift
+    if p.aptr is None:
+        u = p.fscale * _f64(x)[p.fvar - 1] + p.fshift
+    else:
+        prod = p.acoef * _f64(x)[p.avar - 1]
+        u = (np.add.reduceat(prod, p.aptr[:-1]) if len(prod) else np.zeros(0)) + p.fshift
     out = np.empty(len(u))
     with np.errstate(all="ignore"):
         for kind, fn in ((SIN, np.sin), (COS, np.cos), (EXP, np.exp), (LOG, np.log)):
@@ -190,6 +235,64 @@ def nlp_terms_synth(n: int = 24, m: int = 14, seed: int = 1, terms_per_row: int 
     return p
 
 
+def nlp_affine_synth(n: int = 24, m: int = 14, seed: int = 1, terms_per_row: int = 3, max_args: int = 3) -> NlpTerms:
+    """Seeded problem with affine arguments: the objective sum w_j (x_j - a_j)^2 with a = x0 +- 0.3 plus four least-squares
+    residuals (sum_3 c_i x_i - r)^2 with r the value at x0 +- 0.3, two leading linear rows, then rows of terms_per_row terms
+    of 1-3 factors, each with 1-max_args arguments, all variables of a term distinct, kinds uniform over the menu.  LOG and
+    negative powers take positive coefficients (0.5, 1, 2) and shift 0 or 0.3, so their argument is positive on the whole
+    box [0.2, 3]; the others take 1, -1, 0.5, 2, halved for EXP.  g0 and the row bounds are placed as nlp_terms_synth
+    places them: every row holds at the start x0 (uniform in [0.6, 1.4])."""
+    assert n >= 3 * max_args and 1 <= max_args <= MAX_ARGS
+    rng = np.random.default_rng(seed)
+    nlin = 2
+    x0 = rng.uniform(0.6, 1.4, n)
+    terms = []
+    a = x0 + 0.3 * rng.choice([-1.0, 1.0], n)
+    w = rng.uniform(0.5, 2.0, n)
+    for j in range(n):
+        terms.append((0, w[j], [(j + 1, POW, 2, 1.0, -a[j])]))
+    for _ in range(4):
+        js = rng.choice(n, 3, replace=False)
+        c = rng.choice([1.0, -1.0, 0.5, 2.0], 3)
+        r = float(c @ x0[js]) + 0.3 * float(rng.choice([-1.0, 1.0]))
+        terms.append((0, 1.0, [([(int(j) + 1, float(cj)) for j, cj in zip(js, c)], POW, 2, -r)]))
+    kinds = []
+    for i in range(1, m + 1):
+        if i <= nlin:
+            for j in rng.choice(n, terms_per_row, replace=False) + 1:
+                terms.append((i, rng.uniform(-1, 1), [(int(j), POW, 1, 1.0, 0.0)]))
+            kinds.append("eq" if i % 2 else "range")
+            continue
+        for _ in range(terms_per_row):
+            nargs = [int(rng.integers(1, max_args + 1)) for _ in range(int(rng.integers(1, 4)))]
+            js = rng.choice(n, sum(nargs), replace=False) + 1
+            facs, at = [], 0
+            for na in nargs:
+                kind = int(rng.integers(0, 5))
+                e = int(rng.choice([-2, -1, 1, 2, 3])) if kind == POW else 1
+                positive = kind == LOG or (kind == POW and e < 0)
+                c = rng.choice([0.5, 1.0, 2.0] if positive else [1.0, -1.0, 0.5, 2.0], na)
+                if kind == EXP:
+                    c = 0.5 * c
+                sh = float(rng.choice([0.0, 0.3]))
+                facs.append(([(int(j), float(cj)) for j, cj in zip(js[at:at + na], c)], kind, e, sh))
+                at += na
+            terms.append((i, rng.uniform(-1, 1), facs))
+        kinds.append(("eq", "upper", "range")[(i - nlin - 1) % 3])
+    p = make_nlp_terms(n, m, nlin, terms, g0=rng.uniform(-0.2, 0.2, m), f0=float(rng.standard_normal()),
+                       xL=np.full(n, 0.2), xU=np.full(n, 3.0), x0=x0)
+    g = nlp_terms_rows(p, x0)
+    for i, kind in enumerate(kinds):
+        s = rng.uniform(0.2, 1.0)
+        if kind == "eq":
+            p.gL[i] = p.gU[i] = g[i]
+        elif kind == "upper":
+            p.gL[i], p.gU[i] = -np.inf, g[i] + s
+        else:
+            p.gL[i], p.gU[i] = g[i] - s, g[i] + s
+    return p
+
+
 def nlp_terms_scenario(p: NlpTerms, s: int, seed: int = 1, noise: float = 0.05) -> NlpTerms:
     """Scenario s of p (s = 0: p itself): every coefficient scaled by 1 + noise * N(0, 1) (5 % by default), g0 moved so
     that every row keeps its value at x0 -- the bounds (and the feasibility of x0) stay.  A larger noise spreads the
@@ -213,11 +316,13 @@ def from_qcqp(q) -> NlpTerms:
     return make_nlp_terms(q.n, q.m, q.num_linear, terms, g0=q.g0, f0=q.f0, xL=q.xL, xU=q.xU, gL=q.gL, gU=q.gU, x0=q.x0)
 
 
-def from_polar_acopf(net, lay) -> NlpTerms:
+def from_polar_acopf(net, lay, joint: bool = False) -> NlpTerms:
     """The polar model of acopf_layout(net) as terms, for a Context created with lay's own COO structures (duplicates
     included).  Flow k of a branch, F = A v_self^2 + v_f v_t (Bc cos(th_f - th_t) + Bs sin(th_f - th_t)), becomes
     A v_self^2 and four four-factor terms through cos(th_f - th_t) = cos th_f cos th_t + sin th_f sin th_t and
     sin(th_f - th_t) = sin th_f cos th_t - cos th_f sin th_t; the twelve coefficients per branch are net.branch_coeffs().
+    With joint = True the angle difference is the argument of one factor (affine form): two three-factor terms per flow,
+    -Bc v_f v_t cos(th_f - th_t) and -Bs v_f v_t sin(th_f - th_t).
     The structure depends on the topology only: contingency scenarios differ in their coefficients."""
     nb, ng, nl, ndc = net.nb, net.ng, net.nl, net.ndc
     VA, VM, PG = 1, nb + 1, 2 * nb + 1                     # 1-based first variables
@@ -260,6 +365,11 @@ def from_polar_acopf(net, lay) -> NlpTerms:
             row = O0 + 4 * l + k + 1
             terms.append((row, 1.0, lin(own[k] + l)))
             terms.append((row, -A, [(VM + (t if k >= 2 else f), POW, 2)]))
+            if joint:
+                dth = [(VA + f, 1.0), (VA + t, -1.0)]
+                terms.append((row, -Bc, [vf, vt, (dth, COS)]))
+                terms.append((row, -Bs, [vf, vt, (dth, SIN)]))
+                continue
             terms.append((row, -Bc, [vf, vt, cf, ct]))
             terms.append((row, -Bc, [vf, vt, sf, st]))
             terms.append((row, -Bs, [vf, vt, sf, ct]))
