@@ -47,6 +47,29 @@ int sqphip_mf_batch_test(sqphip_ctx *ctx, const int32_t *active, const double *J
                          const double *sigp, const double *hd, const int32_t *rtype, const double *hsc, const double *dw,
                          const double *dw_last, const int32_t *fac_attempt, const double *rhs, double *sol_fused,
                          double *sol_standalone, double *dinv0, double *dinv1, int32_t *decision, double *dw_out);
+/* The values launch of a sweep on its own (k_mf_values: the item-parallel kernel, or the one-thread-per-destination kernel
+ * under SQPHIP_MF_VALUES_SERIAL=1 / for a plan without blocks): instances and interior-point states as in
+ * sqphip_mf_batch_test.  vals0 / vals1 [B][nnzK]: the assembled values of the structural entries of both candidate shifts as
+ * the device holds them after the launch; every slot is preset to `sentinel`, which is what an idle instance -- and candidate
+ * 1 of an instance that does not speculate, or of a context without a second candidate -- comes back with.  *nnzK (may be
+ * null): entries per instance; with vals0 and vals1 both null nothing else happens.  Leaves every instance idle. */
+int sqphip_mf_values_test(sqphip_ctx *ctx, const int32_t *active, const double *Jval, const double *Hval, const double *Dd,
+                          const double *sigp, const double *hd, const int32_t *rtype, const double *hsc, const double *dw,
+                          const double *dw_last, const int32_t *fac_attempt, double sentinel, double *vals0, double *vals1,
+                          int64_t *nnzK);
+/* Host-only (no GPU): the blocks the item-parallel values kernel (k_mf_values) runs for the structure and condense option --
+ * blocks[cap_blocks][4] = (first destination, first item, destinations, items); *n_blocks = 0: the plan has none (a
+ * destination of more than 256 items) and the one-thread-per-destination kernel runs --, item_ptr[cap_dest + 1] (items of
+ * destination e: [item_ptr[e], item_ptr[e + 1]); written when cap_dest >= *n_dest), and two host replays of the values
+ * from the inputs of sqphip_mf_host_solve (vals_list / vals_block [*n_dest], written when not null and cap_dest >= *n_dest):
+ * every destination summed in list order, and -- as the kernel does it -- block by block through a staging array of the
+ * items' values, formed from the kernel's own item copy (vals_block is left alone when there are no blocks). */
+int sqphip_mf_values_blocks(int64_t n, int64_t m, int64_t nnzJ, const int64_t *jrow, const int64_t *jcol, int64_t nnzH,
+                            const int64_t *hrow, const int64_t *hcol, const double *gL, const double *gU, int32_t condense,
+                            const double *Jval, const double *Hval, const double *Dd, const double *sigp, const double *hd,
+                            const int32_t *rtype, double hsc, double dw, int32_t *blocks, int32_t cap_blocks,
+                            int32_t *n_blocks, int32_t *item_ptr, int64_t cap_dest, int64_t *n_dest, int64_t *n_items,
+                            double *vals_list, double *vals_block);
 /* Launch census of the multifrontal path: launches enqueued per kernel instantiation (factor, solve, inertia test) since the
  * context was created.  counts[cap]; names (may be null): cap x 64 characters; *n_kernels = number of instantiations. */
 int sqphip_mf_census(const sqphip_ctx *ctx, int64_t *counts, char *names, int32_t cap, int32_t *n_kernels);

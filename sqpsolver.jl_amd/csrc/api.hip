@@ -373,6 +373,8 @@ extern "C" int sqphip_create(sqphip_ctx **out, int64_t n, int64_t m, int64_t num
                 M.off = C.upload(P.off);
                 M.asm_ptr = C.upload(P.asm_ptr); M.dest_loc = C.upload(P.dest_loc); M.item_ptr = C.upload(P.item_ptr);
                 M.items = C.upload(P.items); M.sched = C.upload(P.sched);
+                M.nvblk = (int)P.vblk.size();
+                if (M.nvblk > 0) { M.vitems = C.upload(P.vitems); M.vblk = C.upload(P.vblk); }
                 auto nz = [](const std::vector<int> &v) { return v.empty() ? std::vector<int>(1, 0) : v; };
                 M.dest_rc = C.upload(P.dest_rc);
                 M.ea_ptr = C.upload(P.ea_ptr); M.ea_rc = C.upload(nz(P.ea_rc));
@@ -719,6 +721,52 @@ extern "C" int sqphip_mf_batch_test(sqphip_ctx *h, const int32_t *active, const 
         if (sol_standalone)
             for (int b = 0; b < B; ++b)
                 for (int u = 0; u < nu; ++u) sol_standalone[(size_t)b * nu + u] = out[(size_t)b * d.Fpad + S.pos[u]];
+        return SQPHIP_OK;
+    });
+}
+
+// The values launch of a sweep on its own (k_mf_values, whichever variant the switches select): instances and
+// interior-point states as in sqphip_mf_batch_test; vals0 / vals1 [B][nnzK] come back as the device holds them after the
+// launch, every slot preset to `sentinel` (vals1: where the context keeps a second candidate, else the sentinel throughout).
+// Null outputs: *nnzK only.  Leaves every instance idle.
+extern "C" int sqphip_mf_values_test(sqphip_ctx *h, const int32_t *active, const double *Jval, const double *Hval,
+                                     const double *Dd, const double *sigp, const double *hd, const int32_t *rtype,
+                                     const double *hsc, const double *dw, const double *dw_last, const int32_t *fac_attempt,
+                                     double sentinel, double *vals0, double *vals1, int64_t *nnzK)
+{
+    if (!h) return SQPHIP_EINVAL;
+    if (!h->c.d.sparse) { h->c.err = "sqphip_mf_values_test: the context does not use the sparse solver"; return SQPHIP_ESTATE; }
+    if (nnzK) *nnzK = h->c.d.mf.nnzK;
+    if (!vals0 && !vals1) return SQPHIP_OK;
+    if (!active || !Jval || !Dd || !sigp || !hd || !rtype || !hsc || !dw || !dw_last || !fac_attempt) return SQPHIP_EINVAL;
+    return guarded(h, [&](Ctx &C) {
+        DV &d = C.d;
+        const int B = d.B;
+        const size_t nv = (size_t)B * d.mf.nnzK;
+        for (int b = 0; b < B; ++b) {
+            const size_t on = (size_t)b * d.n, om = (size_t)b * d.m;
+            h2d(C, d.jcoo + (size_t)b * d.nnzj_coo, Jval + (size_t)b * d.nnzj_coo, d.nnzj_coo);
+            if (Hval) h2d(C, d.hcoo + (size_t)b * d.nnzh_coo, Hval + (size_t)b * d.nnzh_coo, d.nnzh_coo);
+            else SQPHIP_HIP_OK(hipMemsetAsync(d.hcoo + (size_t)b * d.nnzh_coo, 0, sizeof(double) * (size_t)d.nnzh_coo, C.stream));
+            h2d(C, d.Dd + om, Dd + om, d.m); h2d(C, d.sigp + on, sigp + on, d.n); h2d(C, d.hd + on, hd + on, d.n);
+            SQPHIP_HIP_OK(hipMemcpyAsync(d.rtype + om, rtype + om, sizeof(int) * (size_t)d.m, hipMemcpyHostToDevice, C.stream));
+            hipLaunchKernelGGL(k_mf_inst_set, dim3(1), dim3(64), 0, C.stream, d, b, active[b] ? 1 : 0, (int)PH_IDLE, 0.0, 0.0, 0.0, 0);
+        }
+        launch_qp_gather(C);                       // COO -> CSC values of the active instances (start flag set, stage 0)
+        for (int b = 0; b < B; ++b)
+            hipLaunchKernelGGL(k_mf_inst_set, dim3(1), dim3(64), 0, C.stream, d, b, 0, active[b] ? (int)PH_FACTOR : (int)PH_IDLE,
+                               hsc[b], dw[b], dw_last[b], (int)fac_attempt[b]);
+        std::vector<double> fill(nv, sentinel), out1(nv, sentinel);
+        h2d(C, d.mf.vals, fill.data(), nv);
+        if (d.mf.vals1) h2d(C, d.mf.vals1, fill.data(), nv);
+        mf_values(C, PH_FACTOR);
+        if (vals0) d2h(C, vals0, d.mf.vals, nv);
+        if (d.mf.vals1) d2h(C, out1.data(), d.mf.vals1, nv);
+        for (int b = 0; b < B; ++b)
+            hipLaunchKernelGGL(k_mf_inst_set, dim3(1), dim3(64), 0, C.stream, d, b, 0, (int)PH_IDLE, 0.0, 0.0, 0.0, 0);
+        SQPHIP_HIP_OK(hipStreamSynchronize(C.stream));
+        SQPHIP_HIP_OK(hipGetLastError());
+        if (vals1) std::copy(out1.begin(), out1.end(), vals1);
         return SQPHIP_OK;
     });
 }

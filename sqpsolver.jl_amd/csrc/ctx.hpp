@@ -90,6 +90,9 @@ struct MfDev {
     double *fronts1, *vals1;              // second candidate of a sweep (speculative next shift, k_inertia); null: off
     const int *asm_ptr, *dest_loc, *dest_rc, *item_ptr;
     const MfItem *items;
+    const MfItem *vitems;                 // items with every index loadable, and the blocks of k_mf_values (sparse.hpp MfValBlock;
+    const MfValBlock *vblk;               //  nvblk == 0: the one-thread-per-destination kernel runs)
+    int nvblk;
     const int *ea_ptr, *ea_rc, *ea_src_ptr, *ea_src;
     const int *ev_ptr, *ev_idx, *ev_src_ptr, *ev_src;
     const MfFrontDesc *desc;              // packed per-front records
@@ -322,6 +325,7 @@ void launch_qp_gather(Ctx &C);       // COO -> CSC for instances with start set 
 void comm_release(Ctx &C);
 // mfront.hip
 void mf_device_setup(Ctx &C);
+void mf_values(Ctx &C, int want);     // the values launch of mf_factor on its own (k_mf_values)
 void mf_factor(Ctx &C, int want, bool with_rhs, bool values_done = false);
 void mf_solve(Ctx &C, int want, bool skip_fwd, bool inertia = false, int also = -1);   // inertia: the streamed top kernel tests the inertia of PH_FACTOR instances first; also: a second phase in the same chain
 bool mf_solve_tests_inertia(const Ctx &C);     // ... which it can when the plan has a streamed top (k_mf_solve_top2)

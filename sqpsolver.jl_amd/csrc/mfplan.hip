@@ -83,6 +83,23 @@ MfPlan mf_build_plan(int n, int m, const std::vector<int> &kpos, int mk, const s
     P.item_ptr.push_back((int)P.items.size());
     for (int s = 0; s < S.ns; ++s) P.asm_ptr[s + 1] += P.asm_ptr[s];
     P.nnzK = (long)P.dest_loc.size();
+    // blocks of the item-parallel values kernel: whole destinations in order, greedily, at most MF_VBLK_ITEMS items each
+    {
+        int longest = 0;
+        for (long e = 0; e < P.nnzK; ++e) longest = std::max(longest, P.item_ptr[e + 1] - P.item_ptr[e]);
+        if (longest <= MF_VBLK_ITEMS && m > 0 && !jrslot.empty()) {
+            P.vitems = P.items;
+            // (only `row` is ever negative -- -1 on the items without a row --; the clamps of a and b are defensive)
+            for (MfItem &it : P.vitems) { if (it.row < 0) it.row = 0; if (it.a < 0) it.a = 0; if (it.b < 0) it.b = 0; }
+            MfValBlock blk{0, 0, 0, 0};
+            for (int e = 0; e < (int)P.nnzK; ++e) {
+                const int cnt = P.item_ptr[e + 1] - P.item_ptr[e];
+                if (blk.nitems + cnt > MF_VBLK_ITEMS) { P.vblk.push_back(blk); blk = MfValBlock{e, P.item_ptr[e], 0, 0}; }
+                blk.ndest++; blk.nitems += cnt;
+            }
+            if (blk.ndest > 0) P.vblk.push_back(blk);
+        }
+    }
     P.dest_rc.resize(P.dest_loc.size());
     for (int s = 0; s < S.ns; ++s) {
         const int ld = S.sn_nc[s] + S.sn_nr[s] + 1;
@@ -650,6 +667,62 @@ extern "C" int sqphip_mf_host_solve(int64_t n, int64_t m, int64_t nnzJ, const in
         if (d > 0.0 && std::isfinite(d)) ++np;
     }
     if (npos) *npos = np;
+    return SQPHIP_OK;
+}
+
+// C-ABI test hook (host only, no GPU): the blocks of the item-parallel values kernel and two replays of the values -- list
+// order per destination, and block by block through a staging array from the kernel's own item copy (MfPlan::vitems: every
+// operand fetched whatever the type, as the kernel does)
+extern "C" int sqphip_mf_values_blocks(int64_t n, int64_t m, int64_t nnzJ, const int64_t *jrow, const int64_t *jcol, int64_t nnzH,
+                                       const int64_t *hrow, const int64_t *hcol, const double *gL, const double *gU,
+                                       int32_t condense, const double *Jval, const double *Hval, const double *Dd,
+                                       const double *sigp, const double *hd, const int32_t *rtype, double hsc, double dw,
+                                       int32_t *blocks, int32_t cap_blocks, int32_t *n_blocks, int32_t *item_ptr,
+                                       int64_t cap_dest, int64_t *n_dest, int64_t *n_items, double *vals_list, double *vals_block)
+{
+    if (n <= 0 || m < 0 || cap_blocks < 0 || cap_dest < 0 || (cap_blocks > 0 && !blocks)) return SQPHIP_EINVAL;
+    using namespace sqphip;
+    std::vector<double> jv, hv;
+    const MfPlan P = host_plan(n, m, nnzJ, jrow, jcol, nnzH, hrow, hcol, gL, gU, condense, SymOptions(), Jval, Hval, jv, hv);
+    if (n_blocks) *n_blocks = (int32_t)P.vblk.size();
+    if (n_dest) *n_dest = P.nnzK;
+    if (n_items) *n_items = (int64_t)P.items.size();
+    for (int k = 0; k < (int)P.vblk.size() && k < cap_blocks; ++k) {
+        const MfValBlock &b = P.vblk[k];
+        blocks[4 * k] = b.dest0; blocks[4 * k + 1] = b.item0; blocks[4 * k + 2] = b.ndest; blocks[4 * k + 3] = b.nitems;
+    }
+    if (cap_dest < P.nnzK) return SQPHIP_OK;
+    if (item_ptr) std::copy(P.item_ptr.begin(), P.item_ptr.end(), item_ptr);
+    if (!vals_list && !vals_block) return SQPHIP_OK;
+    if (!Jval || !Dd || !sigp || !hd) return SQPHIP_EINVAL;
+    std::vector<int> rt(m > 0 ? m : 1, 1);
+    for (int64_t i = 0; i < m; ++i) rt[i] = rtype ? rtype[i] : 1;
+    const MfValues V{hv.data(), jv.data(), Dd, sigp, hd, rt.data(), hsc, dw};
+    if (vals_list)
+        for (long e = 0; e < P.nnzK; ++e) {
+            double a = 0.0;
+            for (int k = P.item_ptr[e]; k < P.item_ptr[e + 1]; ++k) a += item_value(P.items[k], V);
+            vals_list[e] = a;
+        }
+    if (vals_block)
+        for (const MfValBlock &b : P.vblk) {
+            double stage[MF_VBLK_ITEMS];
+            for (int t = 0; t < b.nitems; ++t) {
+                const MfItem it = P.vitems[b.item0 + t];
+                const double *p1 = it.type == MF_ITEM_H ? V.hv : (it.type == MF_ITEM_VDIAG ? V.hd : V.jv);
+                const double *p3 = it.type == MF_ITEM_VDIAG ? V.sigp + it.a : V.Dd + it.row;
+                const bool live = V.rtype[it.row] != 0;
+                const double x = p1[it.a], y = V.jv[it.b], z = *p3;
+                stage[t] = it.type == MF_ITEM_H ? hsc * x : it.type == MF_ITEM_JKEPT ? (live ? x : 0.0)
+                         : it.type == MF_ITEM_PAIR ? (live ? x * y / (z + 1e-8) : 0.0)
+                         : it.type == MF_ITEM_VDIAG ? x + z + dw + 1e-8 : (live ? -(z + 1e-8) : -1.0);
+            }
+            for (int t = 0; t < b.ndest; ++t) {
+                double a = 0.0;
+                for (int k = P.item_ptr[b.dest0 + t] - b.item0; k < P.item_ptr[b.dest0 + t + 1] - b.item0; ++k) a += stage[k];
+                vals_block[b.dest0 + t] = a;
+            }
+        }
     return SQPHIP_OK;
 }
 

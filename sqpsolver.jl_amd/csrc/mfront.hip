@@ -155,10 +155,14 @@ extern "C" int sqphip_mf_trace2_read(long long *out, int nfronts)
 #endif
 
 // ---------------------------------------------------------------------------------------------------------------
-// values of the structural entries of the Newton matrix: one thread per destination, the items of a destination
-// summed in list order.  Flat over the whole matrix and batch, so the latency-bound gather (item -> slot -> value)
-// runs at full occupancy and off the level-by-level critical path of the front kernels.
-__global__ __launch_bounds__(256) void k_mf_values(DV d, int want)
+// values of the structural entries of the Newton matrix, flat over the whole matrix and batch, off the level-by-level
+// critical path of the front kernels.
+//
+// k_mf_values_serial (the fallback of a plan without blocks, and the cross-check: SQPHIP_MF_VALUES_SERIAL=1): one thread
+// per destination, the items of a destination summed in list order.  Per item a chain of dependent loads (record ->
+// row type -> operands), the next record not requested before the sum: the longest destination of condensed IEEE-118 (16
+// items: a bus that many eliminated rows meet in) makes ~50 round trips one after the other, and the launch lasts as long.
+__global__ __launch_bounds__(256) void k_mf_values_serial(DV d, int want)
 {
     int inst, cand;
     if (!mf_candidate(d, want, inst, cand)) return;
@@ -173,6 +177,53 @@ __global__ __launch_bounds__(256) void k_mf_values(DV d, int want)
     double a = 0.0;
     for (int k = M.item_ptr[e]; k < M.item_ptr[e + 1]; ++k) a += mf_item_value(M.items[k], hv, jv, Dd, sigp, hd, rt, st.hsc, dw);
     mf_vals(d, inst, cand)[e] = a;
+}
+
+// k_mf_values: one workgroup per block of the plan (sparse.hpp MfValBlock: whole destinations, at most 256 items) and
+// instance.  Thread t takes item t of the block: its record is ONE 16-byte load (MfDev::vitems: every index valid whatever
+// the type), all its operands are requested together -- base pointers selected by type, no load behind a test on another
+// load's result --, its value is formed by the expressions of mf_item_value and parked in LDS; behind one barrier thread
+// t < (destinations of the block) sums its destination's values in list order from 0.0.  Product and sum were separate
+// instructions in the serial kernel too (no FMA across its switch): the same bits.  Two exposed round trips and a barrier
+// per workgroup.
+__global__ __launch_bounds__(MF_VBLK_ITEMS) void k_mf_values(DV d, int want)
+{
+    int inst, cand;
+    if (!mf_candidate(d, want, inst, cand)) return;
+    const MfDev &M = d.mf;
+    __shared__ double val[MF_VBLK_ITEMS];
+    const MfValBlock Bk = M.vblk[blockIdx.x];
+    const int t = threadIdx.x;
+    int k0 = 0, k1 = 0;
+    if (t < Bk.ndest) { k0 = M.item_ptr[Bk.dest0 + t]; k1 = M.item_ptr[Bk.dest0 + t + 1]; }
+    if (t < Bk.nitems) {
+        const IpmState &st = d.ist[inst];
+        const double hsc = st.hsc, dw = cand ? next_shift(st.dw, st.dw_last) : st.dw;
+        const int4 rec = reinterpret_cast<const int4 *>(M.vitems)[Bk.item0 + t];
+        const int type = rec.x, row = rec.y, a = rec.z, b = rec.w;
+        const double *jv = d.jv + (long)inst * d.nnzjc;
+        const double *p1 = type == MF_ITEM_H ? d.hv + (long)inst * d.nnzhc : (type == MF_ITEM_VDIAG ? d.hd + (long)inst * d.n : jv);
+        const double *p3 = type == MF_ITEM_VDIAG ? d.sigp + (long)inst * d.n + a : d.Dd + (long)inst * d.m + row;
+        int rtv = d.rtype[(long)inst * d.m + row];
+        double x = p1[a], y = jv[b], z = *p3;
+        asm volatile("" : "+v"(rtv), "+v"(x), "+v"(y), "+v"(z));      // all four in flight before the first use (no load sunk into a case below)
+        const bool live = rtv != ROW_FREE;
+        double v;
+        switch (type) {
+        case MF_ITEM_H: v = hsc * x; break;
+        case MF_ITEM_JKEPT: v = live ? x : 0.0; break;
+        case MF_ITEM_PAIR: v = live ? x * y / (z + MF_REG_D) : 0.0; break;
+        case MF_ITEM_VDIAG: v = x + z + dw + MF_REG_P; break;
+        default: v = live ? -(z + MF_REG_D) : -1.0; break;
+        }
+        val[t] = v;
+    }
+    __syncthreads();
+    if (t < Bk.ndest) {
+        double acc = 0.0;
+        for (int k = k0 - Bk.item0; k < k1 - Bk.item0; ++k) acc += val[k];
+        mf_vals(d, inst, cand)[Bk.dest0 + t] = acc;
+    }
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -243,9 +294,26 @@ __device__ __forceinline__ MfRows mf_rows3(double x, int l15)
 #endif
 }
 
-template <int NW, int MAXT, bool LDSIMG>
+// PACKED (LDS image only; SQPHIP_MF_F2_PACKED=0: the square R x R image): the image is the front's T (T + 1) / 2 lower-
+// triangular 16 x 16 tiles back to back -- nothing is assembled above the diagonal and only those tiles are loaded --, inside
+// a tile in the accumulator layout (a wave's tile load is 64 consecutive doubles per register), and the panel buffers, first
+// written behind the barrier that follows the tile loads, sit in its place: 6 KB instead of 10.6 per single-wave front.
+__device__ __forceinline__ int mf_pk(int row, int col)
+{
+    const int ti = row >> 4;
+    return 256 * ((ti * (ti + 1) >> 1) + (col >> 4)) + 16 * (col & 15) + (row & 15);
+}
+// doubles of dynamic LDS of a generic front kernel launch of T tile rows
+static constexpr size_t mf_factor2_lds_doubles(int T, bool img, bool packed)
+{
+    const size_t R = 16 * (size_t)T, pan = 9 * R + 16, tri = 128 * (size_t)T * (T + 1);
+    return !img ? pan : packed ? (tri > pan ? tri : pan) : R * R + pan;
+}
+
+template <int NW, int MAXT, bool LDSIMG, bool PACKED = false>
 __global__ __launch_bounds__(64 * NW) void k_mf_factor2(DV d, int sbegin, int want, int with_rhs, int Tl)
 {
+    static_assert(LDSIMG || !PACKED, "the packed layout is that of the LDS image");
     constexpr int NT = 64 * NW;
     int inst, cand;
     if (!mf_candidate(d, want, inst, cand)) return;
@@ -257,7 +325,7 @@ __global__ __launch_bounds__(64 * NW) void k_mf_factor2(DV d, int sbegin, int wa
     double *G = mf_arena(d, inst, cand) + Fd.off;
     extern __shared__ double mf_lds[];
     const int R = 16 * Tl;
-    double *Xp = mf_lds + (LDSIMG ? R * R : 0), *Lp = Xp + 4 * R, *blk = Lp + 4 * R, *dl = blk + 16;
+    double *Xp = mf_lds + (LDSIMG && !PACKED ? R * R : 0), *Lp = Xp + 4 * R, *blk = Lp + 4 * R, *dl = blk + 16;
     double *F = LDSIMG ? mf_lds : G;
     const int LD = LDSIMG ? R : ld;
     const int tid = threadIdx.x, lane = tid & 63, l15 = lane & 15, l4 = lane >> 4;
@@ -265,7 +333,8 @@ __global__ __launch_bounds__(64 * NW) void k_mf_factor2(DV d, int sbegin, int wa
     const int T = (ld + 15) >> 4;
     MF_TR(0)
     // 1. image
-    if (LDSIMG) {
+    if (PACKED) for (int e = tid; e < 128 * T * (T + 1); e += NT) F[e] = 0.0;
+    else if (LDSIMG) {
         // the 16 T x 16 T corner of the R x R image; R = 16 T for most fronts of a launch: one flat loop
         if (T == Tl) for (int e = tid; e < R * R; e += NT) F[e] = 0.0;
         else for (int e = tid; e < 256 * T * T; e += NT) F[(e / (16 * T)) * LD + e % (16 * T)] = 0.0;
@@ -276,11 +345,11 @@ __global__ __launch_bounds__(64 * NW) void k_mf_factor2(DV d, int sbegin, int wa
         const double *vals = mf_vals(d, inst, cand);
         for (int e = Fd.asm_begin + tid; e < Fd.asm_end; e += NT) {
             const int rc = M.dest_rc[e];
-            F[(rc >> 16) * LD + (rc & 0xffff)] = vals[e];
+            F[PACKED ? mf_pk(rc & 0xffff, rc >> 16) : (rc >> 16) * LD + (rc & 0xffff)] = vals[e];
         }
         if (with_rhs) {
             const double *b = d.xv + (long)inst * d.Fpad + f0;
-            for (int j = tid; j < nc; j += NT) F[j * LD + fs] = b[j];
+            for (int j = tid; j < nc; j += NT) F[PACKED ? mf_pk(fs, j) : j * LD + fs] = b[j];
         }
     }
     __syncthreads();
@@ -290,7 +359,7 @@ __global__ __launch_bounds__(64 * NW) void k_mf_factor2(DV d, int sbegin, int wa
         double a = arena[g.src0];
         for (int q = g.src_begin + 1; q < g.src_end; ++q) a += arena[M.ea_src[q]];
         const int rc = g.where;
-        F[(rc >> 16) * LD + (rc & 0xffff)] += a;
+        F[PACKED ? mf_pk(rc & 0xffff, rc >> 16) : (rc >> 16) * LD + (rc & 0xffff)] += a;
     }
     __syncthreads();
     MF_TR(3)
@@ -308,10 +377,10 @@ __global__ __launch_bounds__(64 * NW) void k_mf_factor2(DV d, int sbegin, int wa
         for (int rr = 0; rr < 4; ++rr) {
             const int col = 16 * tj + l4 + 4 * rr, row = 16 * ti + l15;
             const bool in = valid && (LDSIMG || (row <= fs && col < fs));
-            acc[q][rr] = in ? F[col * LD + row] : 0.0;
+            acc[q][rr] = in ? F[PACKED ? 256 * ((ti * (ti + 1) >> 1) + tj) + 64 * rr + lane : col * LD + row] : 0.0;
         }
     }
-    __syncthreads();
+    __syncthreads();      // (PACKED: the panel buffers below overwrite the image from here on)
     // 3. elimination, four columns at a time
     for (int tk = 0; 16 * tk < nc; ++tk) {
 #pragma unroll
@@ -2010,6 +2079,21 @@ void mf_device_setup(Ctx &C)
     C.mf_big_lds = ok;
 }
 
+// the values of the structural entries (both candidates where the sweep runs two): the item-parallel kernel over the plan's
+// blocks, or -- a plan without blocks, SQPHIP_MF_VALUES_SERIAL=1 -- the one-thread-per-destination kernel; one census
+// entry and one timing class for whichever runs
+void mf_values(Ctx &C, int want)
+{
+    const DV &d = C.d;
+    hipStream_t s = C.stream;
+    const int nb = d.mf.fronts1 && d.spec_mode != 0 ? 2 * d.B : d.B;
+    const bool serial = d.mf.nvblk == 0 || (getenv("SQPHIP_MF_VALUES_SERIAL") && atoi(getenv("SQPHIP_MF_VALUES_SERIAL")) != 0);     // (read per call: tests flip it)
+    C.tm.open(s); C.mf_census[MFK_VALUES]++;
+    if (serial) hipLaunchKernelGGL(k_mf_values_serial, dim3((d.mf.nnzK + 255) / 256, nb), dim3(256), 0, s, d, want);
+    else hipLaunchKernelGGL(k_mf_values, dim3(d.mf.nvblk, nb), dim3(MF_VBLK_ITEMS), 0, s, d, want);
+    C.tm.close(KC_VALUES, s);
+}
+
 void mf_factor(Ctx &C, int want, bool with_rhs, bool values_done)
 {
     const DV &d = C.d;
@@ -2018,9 +2102,10 @@ void mf_factor(Ctx &C, int want, bool with_rhs, bool values_done)
     const int wr = (int)with_rhs;
     const int nb = d.mf.fronts1 && d.spec_mode != 0 ? 2 * d.B : d.B;         // with the second candidate the factor side runs over 2 B "instances"
     // (values_done: the stage kernel that built the right-hand sides has assembled the values too: mf_values_block)
-    if (!v1 && !values_done) { C.tm.open(s); C.mf_census[MFK_VALUES]++; hipLaunchKernelGGL(k_mf_values, dim3((d.mf.nnzK + 255) / 256, nb), dim3(256), 0, s, d, want); C.tm.close(KC_VALUES, s); }
+    if (!v1 && !values_done) mf_values(C, want);
     // static front kernels (k_mf_front<T, NW, LDSIMG>) unless SQPHIP_MF_STATIC=0 asks for the generic ones (cross-check)
     const bool stat = !(getenv("SQPHIP_MF_STATIC") && atoi(getenv("SQPHIP_MF_STATIC")) == 0);     // (read per call: tests flip it)
+    const bool packed = !(getenv("SQPHIP_MF_F2_PACKED") && atoi(getenv("SQPHIP_MF_F2_PACKED")) == 0);   // (likewise) LDS image of the generic kernels as packed tiles
     // the levels below the spine as level launches, the spine (mfplan.hip: spine_level) by one workgroup per instance
     const bool spine = !v1 && d.mf.sp_n > 0 && C.mf_big_lds;
     int li = 0, cls_open = -1;        // (detail timers: one event pair around the launches below the narrow top, one around those of the top)
@@ -2029,10 +2114,13 @@ void mf_factor(Ctx &C, int want, bool with_rhs, bool values_done)
         const int cls = L.level >= C.mfp().narrow_level ? KC_FRONTS_TOP : KC_FRONTS_LOW;
         if (cls != cls_open) { if (cls_open >= 0) C.tm.close(cls_open, s); C.tm.open(s); cls_open = cls; }
         const dim3 grid(L.count, nb);
-        const int T = L.tiles, R = 16 * T;
+        const int T = L.tiles;
         if (v1 || T > 13) { C.mf_census[MFK_FACTOR_R1]++; hipLaunchKernelGGL((k_mf_factor<256, true>), grid, dim3(256), 0, s, d, L.begin, want, wr); continue; }
-        // generic kernels: dynamic LDS = [image (16 T)^2 when it lives in LDS][panel X and L: 2 x 4 x 16 T][4 x 4 block][1 / D: 16 T]
-#define MF_GENERIC(NW, MAXT, IMG) do { constexpr int kid_ = mf_factor2_kid(NW, MAXT, IMG); static_assert(kid_ >= 0, "census: no counter"); C.mf_census[kid_]++; hipLaunchKernelGGL((k_mf_factor2<NW, MAXT, IMG>), grid, dim3(64 * NW), 8 * (size_t)((IMG ? R * R : 0) + 9 * R + 16), s, d, L.begin, want, wr, T); } while (0)
+        // generic kernels: dynamic LDS = [image (16 T)^2 when it lives in LDS][panel X and L: 2 x 4 x 16 T][4 x 4 block][1 / D: 16 T];
+        // packed image (k_mf_factor2, PACKED): the larger of the T (T + 1) / 2 tiles and the panel buffers
+#define MF_GENERIC(NW, MAXT, IMG) do { constexpr int kid_ = mf_factor2_kid(NW, MAXT, IMG); static_assert(kid_ >= 0, "census: no counter"); C.mf_census[kid_]++; \
+        if (IMG && packed) hipLaunchKernelGGL((k_mf_factor2<NW, MAXT, IMG, IMG>), grid, dim3(64 * NW), 8 * mf_factor2_lds_doubles(T, IMG, true), s, d, L.begin, want, wr, T); \
+        else hipLaunchKernelGGL((k_mf_factor2<NW, MAXT, IMG, false>), grid, dim3(64 * NW), 8 * mf_factor2_lds_doubles(T, IMG, false), s, d, L.begin, want, wr, T); } while (0)
 #define MF_STATIC(TT, NW, IMG) do { constexpr int kid_ = mf_front_kid(TT, NW, IMG); static_assert(kid_ >= 0, "census: no counter"); C.mf_census[kid_]++; hipLaunchKernelGGL((k_mf_front<TT, NW, IMG>), grid, dim3(64 * NW), 8 * (size_t)mf_front_lds_doubles(TT, NW, IMG), s, d, L.begin, want, wr); } while (0)
         // ... from four tile rows on: below that the generic kernels are as fast per front and lighter (registers, code
         // size) where thousands of small fronts are in flight.  Measured (QP/s, static from T = 1 / from T = 4 / never):

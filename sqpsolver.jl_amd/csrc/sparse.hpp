@@ -94,6 +94,12 @@ enum { MF_ITEM_H = 0,        // hsc * hv[a]
        MF_ITEM_RDIAG = 4 };  // -(Dd[row] + reg_d), or -1 for a free row
 struct MfItem { int type, row, a, b; };
 
+// One workgroup of the item-parallel values kernel (k_mf_values, mfront.hip): whole, consecutive destinations
+// [dest0, dest0 + ndest) whose items [item0, item0 + nitems) number at most MF_VBLK_ITEMS -- one thread per item, then one
+// per destination for the sum in list order.
+constexpr int MF_VBLK_ITEMS = 256;
+struct MfValBlock { int dest0, item0, ndest, nitems; };
+
 // everything a kernel needs to know about a front, in one 48-byte record (three 16-byte loads instead of a chain of
 // dependent look-ups): columns, rows, first position, offsets into rows[] / the front arena, and its ranges in the
 // destination, extend-add and vector-gather lists
@@ -132,6 +138,11 @@ struct MfPlan {
     long stride = 0;                             // doubles per instance
     std::vector<int> asm_ptr, dest_loc, item_ptr; // per front: destinations [asm_ptr[s], asm_ptr[s+1]); per destination: items
     std::vector<MfItem> items;
+    // the same items for k_mf_values: every index valid for an unconditional load (row and unused operand slots 0), and the
+    // blocks of that kernel.  vblk empty: a destination has more than MF_VBLK_ITEMS items (or the structure has no row /
+    // no Jacobian entry to point the unused slots at) and the one-thread-per-destination kernel runs instead.
+    std::vector<MfItem> vitems;
+    std::vector<MfValBlock> vblk;
     // per front: (row | column << 16) of each destination, for kernels that keep the front in another leading dimension
     std::vector<int> dest_rc;
     // extend-add as a gather: per front the entries that receive contributions [ea_ptr[s], ea_ptr[s+1]), each with

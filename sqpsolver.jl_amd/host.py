@@ -138,6 +138,35 @@ def mf_plan_info(n, m, jrow, jcol, hrow, hcol, gL, gU, condense=1, batch=1):
     return fr, la, top.value, sp.value
 
 
+def mf_values_blocks(n, m, jrow, jcol, hrow, hcol, gL, gU, condense=1, values=None):
+    """Blocks of the item-parallel values kernel (`sqphip_mf_values_blocks`, host only): a dict with blocks ((nb, 4): first
+    destination, first item, destinations, items; nb = 0: the plan keeps the one-thread-per-destination kernel) and item_ptr;
+    with values = (jval, hval, Dd, sigp, hd, rtype, hsc, dw) also vals_list and vals_block, the two host replays (vals_block
+    is None when there are no blocks)."""
+    L = _lib.lib()
+    jr, jc, hr, hc = (np.ascontiguousarray(a, dtype=np.int64) for a in (jrow, jcol, hrow, hcol))
+    nb, nd, ni = C.c_int32(), C.c_int64(), C.c_int64()
+    head = (n, m, len(jr), _l(jr), _l(jc), len(hr), _l(hr), _l(hc), _d(_f(gL)), _d(_f(gU)), int(condense))
+    none = (None, None, None, None, None, None, 0.0, 0.0)
+    if L.sqphip_mf_values_blocks(*head, *none, None, 0, C.byref(nb), None, 0, C.byref(nd), C.byref(ni), None, None) != 0:
+        raise SqpHipError("sqphip_mf_values_blocks failed")
+    blocks = np.zeros((nb.value, 4), dtype=np.int32); ptr = np.zeros(nd.value + 1, dtype=np.int32)
+    out = {"blocks": blocks, "item_ptr": ptr, "n_items": ni.value, "vals_list": None, "vals_block": None}
+    vals = none; vl = vb = None
+    if values is not None:
+        jval, hval, Dd, sigp, hd, rtype, hsc, dw = values
+        rt = np.ascontiguousarray(rtype, dtype=np.int32)
+        vals = (_d(_f(jval)), _d(_f(hval)), _d(_f(Dd)), _d(_f(sigp)), _d(_f(hd)), _i(rt), float(hsc), float(dw))
+        vl = np.zeros(nd.value); vb = np.zeros(nd.value)
+    if L.sqphip_mf_values_blocks(*head, *vals, _i(blocks) if nb.value else None, nb.value, C.byref(nb), _i(ptr), nd.value,
+                                 C.byref(nd), C.byref(ni), _d(vl) if vl is not None else None,
+                                 _d(vb) if vb is not None else None) != 0:
+        raise SqpHipError("sqphip_mf_values_blocks failed")
+    if values is not None:
+        out["vals_list"] = vl; out["vals_block"] = vb if nb.value else None
+    return out
+
+
 class Context:
     """Owns a sqphip_ctx (one NLP structure, `batch` instances)."""
 
@@ -345,6 +374,19 @@ class Context:
                                              _i(dec), _d(dwo)))
         out["decision"] = dec; out["dw"] = dwo
         return out
+
+    def mf_values_test(self, active, jval, hval, Dd, sigp, hd, rtype, hsc, dw, dw_last, fac_attempt, sentinel=-7.5):
+        """The values launch of a sweep on its own (`sqphip_mf_values_test`); inputs stacked as for `mf_batch_test`.  Returns
+        (vals0, vals1), each [B, nnzK]: the assembled values of both candidate shifts, `sentinel` where nothing was written."""
+        nk = C.c_int64()
+        self._ck(self.L.sqphip_mf_values_test(self.h, *([None] * 11), 0.0, None, None, C.byref(nk)))
+        i32 = lambda a: np.ascontiguousarray(a, dtype=np.int32)
+        act, rt, fa = i32(active), i32(rtype), i32(fac_attempt)
+        v0 = np.zeros((len(act), nk.value)); v1 = np.zeros_like(v0)
+        self._ck(self.L.sqphip_mf_values_test(self.h, _i(act), _d(_f(jval)), _d(_f(hval)), _d(_f(Dd)), _d(_f(sigp)), _d(_f(hd)),
+                                              _i(rt), _d(_f(hsc)), _d(_f(dw)), _d(_f(dw_last)), _i(fa), float(sentinel),
+                                              _d(v0), _d(v1), C.byref(nk)))
+        return v0, v1
 
     def mf_census(self):
         """Launch census of the multifrontal path (`sqphip_mf_census`): {kernel instantiation: launches enqueued}."""
