@@ -85,6 +85,12 @@ int sqphip_mf_plan_info(int64_t n, int64_t m, int64_t nnzJ, const int64_t *jrow,
                         const int64_t *hrow, const int64_t *hcol, const double *gL, const double *gU, int32_t condense,
                         int32_t batch, int32_t *fronts, int32_t cap_fronts, int32_t *n_fronts, int32_t *launches,
                         int32_t cap_launches, int32_t *n_launches, int64_t *top2_lds_bytes, int32_t *spine_fronts);
+/* Host-only (no GPU): where the deferral pass of the plan (SQPHIP_MF_DEFER) put the fronts of the same plan --
+ * fronts[cap_fronts][3] = (factor launch the front runs in: a row of `launches` above, its launch in the schedule before the
+ * pass, numbered in that schedule -- the rows of `launches` under SQPHIP_MF_DEFER=0 --, parent front or -1 for a root). */
+int sqphip_mf_front_launches(int64_t n, int64_t m, int64_t nnzJ, const int64_t *jrow, const int64_t *jcol, int64_t nnzH,
+                             const int64_t *hrow, const int64_t *hcol, const double *gL, const double *gU, int32_t condense,
+                             int32_t batch, int32_t *fronts, int32_t cap_fronts, int32_t *n_fronts);
 /* ---- kernel-level entry points (parity tests, micro-benchmarks) -------------------------------
  * Batched dense LDL^T without pivoting of `batch` symmetric N x N matrices given as full
  * column-major host arrays A[batch][N*N] (lower triangle read).  On return L (unit lower) is in the

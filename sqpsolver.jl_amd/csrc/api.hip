@@ -2032,7 +2032,7 @@ extern "C" int sqphip_get_counters(sqphip_ctx *h, sqphip_counters *c)
             c->cb_doubles = cb;
             long lt = 0, kt = 0, nct = 0;
             for (int q = 0; q < Y.ns; ++q)
-                if (Y.sn_level[q] >= C.mfp().narrow_level) {
+                if (C.mfp().fac[C.mfp().launch_of[q]].level >= C.mfp().narrow_level) {      // (by the launch the front runs in: the timers open per launch level)
                     const long nc = Y.sn_nc[q], nr = Y.sn_nr[q];
                     lt += nc * (nc - 1) / 2 + nc * nr; kt += C.mfp().asm_ptr[q + 1] - C.mfp().asm_ptr[q]; nct += nc;
                 }

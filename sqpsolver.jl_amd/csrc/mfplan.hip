@@ -226,6 +226,7 @@ MfPlan mf_build_plan(int n, int m, const std::vector<int> &kpos, int mk, const s
             if (!L.count) continue;
             if (!merge && c == 1) L.tiles = 2;        // the kernel of the class (a front of fewer tiles runs in it with empty tiles)
             if (!merge && c == 7) L.tiles = 8;
+            L.small = L.count <= 8;                   // what mf_factor's choices go by: fixed here, before the deferral pass below
             P.fac.push_back(L);                       // threads and LDS are the kernel's business (mf_factor)
         }
     }
@@ -432,6 +433,78 @@ MfPlan mf_build_plan(int n, int m, const std::vector<int> &kpos, int mk, const s
         if (getenv("SQPHIP_SYM_DUMP"))
             fprintf(stderr, "spine (factorisation): %d fronts from level %d, tallest %d tiles, %zu arena gather entries, LDS %ld bytes\n",
                     (int)P.sp_fr.size(), P.spine_level, P.spine_T, P.sp_ent.size(), P.spine_lds_bytes);
+    }
+    // ---- deferral: a launch dissolves when every front of it can ride in a later launch of the same kernel that still runs
+    // before the front's parent does.  The levels above give every front the earliest possible launch, 1 + max(children),
+    // whether or not anybody waits for it; a front whose parent sits two or more levels up has slack, and where a whole
+    // launch consists of such fronts (a single leaf one row over a class boundary, two side branches of the upper tree) the
+    // launch costs the chain its full latency for work that a later, equally shaped launch takes along almost free.
+    // Nothing a front computes depends on the launch it is in: its kernel is the same (mf_same_selection: the rules live
+    // next to mf_factor), its children's blocks are complete, its arena slot is its own.  Launches keep level, tiles and class;
+    // sn_level, the solve launches and the gather lists are untouched.  SQPHIP_MF_DEFER=0: the schedule as built above;
+    // 1 (default): the latest launch allowed; 2: the destination whose own tallest front has the most columns -- a proxy for
+    // the longest launch, behind which the guest hides --, ties to the latest (measured, 512 x IEEE-118, QP/s medians of five:
+    // 10 279 without / 10 490 latest / 10 416 widest: DESIGN.md section 0d).  Not with a spine: fac_below cuts the launch
+    // list by level.
+    {
+        const int defer = getenv("SQPHIP_MF_DEFER") ? atoi(getenv("SQPHIP_MF_DEFER")) : 1;
+        const int nl = (int)P.fac.size();
+        std::vector<std::vector<int>> mem(nl);           // fronts per launch, guests behind the launch's own
+        P.launch_of0.assign(S.ns, -1);
+        for (int k = 0; k < nl; ++k)
+            for (int q = P.fac[k].begin; q < P.fac[k].begin + P.fac[k].count; ++q) { mem[k].push_back(P.sched[q]); P.launch_of0[P.sched[q]] = k; }
+        std::vector<char> alive(nl, 1);
+        if (defer != 0 && P.sp_fr.empty()) {
+            std::vector<int> width(nl, 0);               // columns of the launch's own tallest front
+            for (int k = 0; k < nl; ++k) {
+                int fs = -1;
+                for (int s : mem[k]) {
+                    const int h = S.sn_nc[s] + S.sn_nr[s];
+                    if (h > fs || (h == fs && S.sn_nc[s] > width[k])) { fs = h; width[k] = S.sn_nc[s]; }
+                }
+            }
+            std::vector<int> dest;
+            for (int a = 0; a < nl; ++a) {
+                const MfLaunch &A = P.fac[a];
+                dest.clear();
+                for (int s : mem[a]) {
+                    const int p = S.sn_parent[s], bound = p >= 0 ? S.sn_level[p] : S.nlevels;
+                    int best = -1;
+                    for (int b = a + 1; b < nl && P.fac[b].level < bound; ++b) {
+                        const MfLaunch &B = P.fac[b];
+                        if (!alive[b] || B.level <= A.level || !mf_same_selection(A, B, P.narrow_level)) continue;
+                        if (best < 0 || defer != 2 || width[b] >= width[best]) best = b;
+                    }
+                    if (best < 0) break;
+                    dest.push_back(best);
+                }
+                if (dest.size() != mem[a].size()) continue;       // a launch that would keep a front saves nothing: left alone
+                for (size_t t = 0; t < dest.size(); ++t) mem[dest[t]].push_back(mem[a][t]);
+                mem[a].clear(); alive[a] = 0;
+            }
+            std::vector<MfLaunch> fac;
+            P.sched.clear();
+            for (int k = 0; k < nl; ++k) {
+                if (!alive[k]) continue;
+                MfLaunch L = P.fac[k];
+                L.begin = (int)P.sched.size(); L.count = (int)mem[k].size();
+                P.sched.insert(P.sched.end(), mem[k].begin(), mem[k].end());
+                fac.push_back(L);
+            }
+            P.fac.swap(fac);
+            P.fac_below = (int)P.fac.size();
+        }
+        P.launch_of.assign(S.ns, -1);
+        for (int k = 0; k < (int)P.fac.size(); ++k)
+            for (int q = P.fac[k].begin; q < P.fac[k].begin + P.fac[k].count; ++q) P.launch_of[P.sched[q]] = k;
+        if (getenv("SQPHIP_SYM_DUMP")) {
+            for (int s = 0; s < S.ns; ++s)
+                if (alive[P.launch_of0[s]] == 0)
+                    fprintf(stderr, "  deferred: front %d (%d x %d, level %d, parent's level %d) from launch %d to launch %d (level %d)\n", s, S.sn_nc[s],
+                            S.sn_nr[s], S.sn_level[s], S.sn_parent[s] >= 0 ? S.sn_level[S.sn_parent[s]] : -1, P.launch_of0[s], P.launch_of[s],
+                            P.fac[P.launch_of[s]].level);
+            fprintf(stderr, "factor launches: %d (%d before deferral)\n", (int)P.fac.size(), nl);
+        }
     }
     return P;
 }
@@ -759,5 +832,23 @@ extern "C" int sqphip_mf_plan_info(int64_t n, int64_t m, int64_t nnzJ, const int
     if (n_launches) *n_launches = (int32_t)P.fac.size();
     if (top2_lds_bytes) *top2_lds_bytes = P.top2_lds_bytes;
     if (spine_fronts) *spine_fronts = (int32_t)P.sp_fr.size();
+    return SQPHIP_OK;
+}
+
+// C-ABI test hook (host only, no GPU): where the deferral pass of mf_build_plan put every front of the plan sqphip_create
+// builds for the structure, condense option and batch -- per front (factor launch it runs in, its launch in the schedule
+// before the pass, numbered in that schedule, parent front or -1 for a root); cap_fronts 0 asks for the count only.
+extern "C" int sqphip_mf_front_launches(int64_t n, int64_t m, int64_t nnzJ, const int64_t *jrow, const int64_t *jcol, int64_t nnzH,
+                                        const int64_t *hrow, const int64_t *hcol, const double *gL, const double *gU,
+                                        int32_t condense, int32_t batch, int32_t *fronts, int32_t cap_fronts, int32_t *n_fronts)
+{
+    if (n <= 0 || m < 0 || batch <= 0 || cap_fronts < 0 || (cap_fronts > 0 && !fronts)) return SQPHIP_EINVAL;
+    using namespace sqphip;
+    const SymOptions so = mf_sym_options(batch);
+    std::vector<double> jv, hv;
+    const MfPlan P = host_plan(n, m, nnzJ, jrow, jcol, nnzH, hrow, hcol, gL, gU, condense, so, nullptr, nullptr, jv, hv);
+    const SparseSym &S = P.S;
+    for (int f = 0; f < S.ns && f < cap_fronts; ++f) { fronts[3 * f] = P.launch_of[f]; fronts[3 * f + 1] = P.launch_of0[f]; fronts[3 * f + 2] = S.sn_parent[f]; }
+    if (n_fronts) *n_fronts = S.ns;
     return SQPHIP_OK;
 }

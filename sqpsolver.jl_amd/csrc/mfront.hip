@@ -2094,6 +2094,19 @@ void mf_values(Ctx &C, int want)
     C.tm.close(KC_VALUES, s);
 }
 
+// What mf_factor's choice of instantiation takes from the launch itself, besides the switches it reads per call: the tiles of
+// its kernel, whether it was a launch of at most eight fronts when the schedule was built (MfLaunch::small: stat_min, nw4, the
+// LDS image of six to eight tiles) and whether its level belongs to the narrow top of the tree (stat_min).  The last one
+// decides nothing from four tiles on: stat_min is then 1 or 4 by default, and a SQPHIP_MF_STATIC_MIN holds for every launch
+// alike.  The deferral pass of mf_build_plan moves a front only between launches this function calls equal, so no front
+// changes kernel; whoever adds an input to the choice below adds it here.
+static inline bool mf_launch_narrow(const MfLaunch &L, int narrow_level) { return L.level >= narrow_level; }
+bool mf_same_selection(const MfLaunch &a, const MfLaunch &b, int narrow_level)
+{
+    return a.tiles == b.tiles && a.small == b.small &&
+           (a.tiles >= 4 || mf_launch_narrow(a, narrow_level) == mf_launch_narrow(b, narrow_level));
+}
+
 void mf_factor(Ctx &C, int want, bool with_rhs, bool values_done)
 {
     const DV &d = C.d;
@@ -2111,7 +2124,7 @@ void mf_factor(Ctx &C, int want, bool with_rhs, bool values_done)
     int li = 0, cls_open = -1;        // (detail timers: one event pair around the launches below the narrow top, one around those of the top)
     for (const MfLaunch &L : C.mfp().fac) {
         if (spine && li++ >= C.mfp().fac_below) break;
-        const int cls = L.level >= C.mfp().narrow_level ? KC_FRONTS_TOP : KC_FRONTS_LOW;
+        const int cls = mf_launch_narrow(L, C.mfp().narrow_level) ? KC_FRONTS_TOP : KC_FRONTS_LOW;
         if (cls != cls_open) { if (cls_open >= 0) C.tm.close(cls_open, s); C.tm.open(s); cls_open = cls; }
         const dim3 grid(L.count, nb);
         const int T = L.tiles;
@@ -2128,13 +2141,13 @@ void mf_factor(Ctx &C, int want, bool with_rhs, bool values_done)
         // 55.4 k / 53.9 k.  SQPHIP_MF_STATIC_MIN moves the threshold (tests run it at 1 to cover every instantiation).
         // (round 4: on a narrow level -- a handful of fronts, i.e. the levels the spine kernel takes over -- the static
         //  kernels run every front: the level-launch build, SQPHIP_MF_SPINE=0, then gives the bits of the spine kernel)
-        const int stat_min = getenv("SQPHIP_MF_STATIC_MIN") ? atoi(getenv("SQPHIP_MF_STATIC_MIN")) : (L.count <= 8 && L.level >= C.mfp().narrow_level ? 1 : 4);
+        const int stat_min = getenv("SQPHIP_MF_STATIC_MIN") ? atoi(getenv("SQPHIP_MF_STATIC_MIN")) : (L.small && mf_launch_narrow(L, C.mfp().narrow_level) ? 1 : 4);
         // four waves instead of two for fronts of four (bit 0) / five (bit 1) tile rows on the levels near the top of the
         // tree (a handful of fronts: latency, not occupancy, is what counts there): 512 x IEEE-118 7 100 -> 7 154 / 7 297 / 7 326
         // QP/s with bit 0 / bit 1 / both, same bits (SQPHIP_MF_NW4=0: two waves everywhere)
         // ... and eight instead of four for six to eight tile rows there: 7 323 -> 7 403 QP/s, same bits (SQPHIP_MF_NW8=0: four)
         const bool nw8 = !(getenv("SQPHIP_MF_NW8") && atoi(getenv("SQPHIP_MF_NW8")) == 0);
-        const int nw4 = L.count <= 8 ? (getenv("SQPHIP_MF_NW4") ? atoi(getenv("SQPHIP_MF_NW4")) : 3) : 0;
+        const int nw4 = L.small ? (getenv("SQPHIP_MF_NW4") ? atoi(getenv("SQPHIP_MF_NW4")) : 3) : 0;
         const bool big_img = C.mf_big_lds && !(getenv("SQPHIP_MF_BIG_LDSIMG") && atoi(getenv("SQPHIP_MF_BIG_LDSIMG")) == 0);     // (read per call: tests flip it)
         // (round 4: nine to twelve tile rows too -- the fronts of 129 .. 192 rows of the 1354- and 9241-bus shapes --, eight waves,
         //  image in the arena: 1354 buses 549 -> 557 QP/s, 9241 buses 28.5 -> 29.2; SQPHIP_MF_STATIC_MAX = 8 gives them back to the
@@ -2157,9 +2170,9 @@ void mf_factor(Ctx &C, int want, bool with_rhs, bool values_done)
         // (six to eight tile rows: the image fits the 160 KB of LDS of gfx950 too -- 74 / 100 / 131 KB -- once more than
         //  64 KB of dynamic LDS has been asked for; only for the handful of fronts of a level near the top of the tree, where
         //  one workgroup per CU is all there is anyway: +0.3 % on 512 x IEEE-118; SQPHIP_MF_BIG_LDSIMG=0: image in the arena)
-        case 6: if (big_img && L.count <= 8) { if (nw8) MF_STATIC(6, 8, true); else MF_STATIC(6, 4, true); } else MF_STATIC(6, 4, false); break;
-        case 7: if (big_img && L.count <= 8) { if (nw8) MF_STATIC(7, 8, true); else MF_STATIC(7, 4, true); } else MF_STATIC(7, 4, false); break;
-        case 8: if (big_img && L.count <= 8) { if (nw8) MF_STATIC(8, 8, true); else MF_STATIC(8, 4, true); } else MF_STATIC(8, 4, false); break;
+        case 6: if (big_img && L.small) { if (nw8) MF_STATIC(6, 8, true); else MF_STATIC(6, 4, true); } else MF_STATIC(6, 4, false); break;
+        case 7: if (big_img && L.small) { if (nw8) MF_STATIC(7, 8, true); else MF_STATIC(7, 4, true); } else MF_STATIC(7, 4, false); break;
+        case 8: if (big_img && L.small) { if (nw8) MF_STATIC(8, 8, true); else MF_STATIC(8, 4, true); } else MF_STATIC(8, 4, false); break;
         case 9: MF_STATIC(9, 8, false); break;
         case 10: MF_STATIC(10, 8, false); break;
         case 11: MF_STATIC(11, 8, false); break;

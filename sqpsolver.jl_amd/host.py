@@ -138,6 +138,22 @@ def mf_plan_info(n, m, jrow, jcol, hrow, hcol, gL, gU, condense=1, batch=1):
     return fr, la, top.value, sp.value
 
 
+def mf_front_launches(n, m, jrow, jcol, hrow, hcol, gL, gU, condense=1, batch=1):
+    """Where the deferral pass of the plan put its fronts (`sqphip_mf_front_launches`, host only): an (ns, 3) array of (factor
+    launch the front runs in, its launch in the schedule before the pass -- the rows of `mf_plan_info` under
+    SQPHIP_MF_DEFER=0 --, parent front or -1 for a root)."""
+    L = _lib.lib()
+    jr, jc, hr, hc = (np.ascontiguousarray(a, dtype=np.int64) for a in (jrow, jcol, hrow, hcol))
+    nf = C.c_int32()
+    args = (n, m, len(jr), _l(jr), _l(jc), len(hr), _l(hr), _l(hc), _d(_f(gL)), _d(_f(gU)), int(condense), int(batch))
+    if L.sqphip_mf_front_launches(*args, None, 0, C.byref(nf)) != 0:
+        raise SqpHipError("sqphip_mf_front_launches failed")
+    fr = np.zeros((nf.value, 3), dtype=np.int32)
+    if L.sqphip_mf_front_launches(*args, _i(fr), nf.value, C.byref(nf)) != 0:
+        raise SqpHipError("sqphip_mf_front_launches failed")
+    return fr
+
+
 def mf_values_blocks(n, m, jrow, jcol, hrow, hcol, gL, gU, condense=1, values=None):
     """Blocks of the item-parallel values kernel (`sqphip_mf_values_blocks`, host only): a dict with blocks ((nb, 4): first
     destination, first item, destinations, items; nb = 0: the plan keeps the one-thread-per-destination kernel) and item_ptr;
