@@ -676,7 +676,10 @@ static __device__ __forceinline__ void b_build_rhs(const DV &d)
 // Sparse path: the sweep has factorised the shift st.dw AND -- for the instances mf_speculates() names -- the next shift
 // of the schedule.  The bookkeeping below is that of a run that factorises one shift per sweep (same counters, same
 // decisions as the oracle); the second candidate only saves the sweep a failed first shift would have cost.
-__global__ __launch_bounds__(TPB, SQPHIP_VEC_WAVES_PER_EU) void k_inertia(DV d)
+// serial: the former counting loop (SQPHIP_INERTIA_SERIAL=1).  Chunks of eight elements per thread: 8 192 positions per chunk
+// (the 1354-bus shape in a handful of chunks), 8 x 5 registers of loaded values per lane out of the 128 of a 1 024-thread
+// workgroup at four waves per SIMD.
+__global__ __launch_bounds__(TPB, SQPHIP_VEC_WAVES_PER_EU) void k_inertia(DV d, int serial)
 {
     const int inst = blockIdx.x;
     if (d.phase[inst] != PH_FACTOR) return;
@@ -684,7 +687,8 @@ __global__ __launch_bounds__(TPB, SQPHIP_VEC_WAVES_PER_EU) void k_inertia(DV d)
     const bool spec = mf_speculates(d, st);
     const double *dinv = d.dinv + (long)inst * d.Fpad, *dinv1 = spec ? d.dinv1 + (long)inst * d.Fpad : nullptr;
     double np = 0, bad = 0, np1 = 0, bad1 = 0;
-    inertia_count(d, dinv, dinv1, TPB, np, bad, np1, bad1);
+    if (serial) inertia_count_serial(d, dinv, dinv1, TPB, np, bad, np1, bad1);
+    else inertia_count<8>(d, dinv, dinv1, TPB, np, bad, np1, bad1);
     np = block_reduce<OpSum>(np); bad = block_reduce<OpSum>(bad);
     if (spec) { np1 = block_reduce<OpSum>(np1); bad1 = block_reduce<OpSum>(bad1); }
     if (threadIdx.x == 0) inertia_decide(d, inst, st, spec, np, bad, np1, bad1);
@@ -1285,7 +1289,8 @@ __global__ __launch_bounds__(TPB, SQPHIP_VEC_WAVES_PER_EU) void k_ipm_prepare(DV
 void launch_inertia(Ctx &C)
 {
     C.mf_census[MFK_INERTIA]++;
-    hipLaunchKernelGGL(k_inertia, dim3(C.d.B), dim3(TPB), 0, C.stream, C.d);
+    const char *e = getenv("SQPHIP_INERTIA_SERIAL");      // (read per call: tests flip it)
+    hipLaunchKernelGGL(k_inertia, dim3(C.d.B), dim3(TPB), 0, C.stream, C.d, e && atoi(e) ? 1 : 0);
 }
 
 void launch_qp_gather(Ctx &C)

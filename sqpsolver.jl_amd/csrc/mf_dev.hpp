@@ -70,16 +70,63 @@ static __device__ __forceinline__ void mf_values_block(const DV &d, int inst, in
 // kernels per instance) and the streamed solve kernel, which does the test of its instance in its own prologue
 // (k_mf_solve_top2, mfront.hip: a launch less per sweep).  The counts are small integers: any summation order gives the
 // same doubles.
-static __device__ __forceinline__ void inertia_count(const DV &d, const double *dinv, const double *dinv1, int nthreads,
-                                                     double &np, double &bad, double &np1, double &bad1)
+//
+// one pivot into its two counters, without a branch (live: a real position, not padding)
+static __device__ __forceinline__ void inertia_classify(double v, bool live, double &np, double &bad)
+{
+    const bool b = !isfinite(v) || v == 0.0;
+    bad += (live && b) ? 1.0 : 0.0;
+    np += (live && !b && v > 0) ? 1.0 : 0.0;
+}
+// The former loop (SQPHIP_INERTIA_SERIAL=1: cross-check and A/B): one element per thread and iteration, the pivot loaded
+// behind the test of its position -- two dependent round trips per iteration, ceil(Fpad / nthreads) iterations.  Its loads
+// and their order are the former ones; its counters are the predicated adds of the chunked count (as `if ... bad += 1; else
+// np += 1` the compiler addresses the counters through a selected pointer and keeps all four in scratch, in every caller).
+static __device__ __forceinline__ void inertia_count_serial(const DV &d, const double *dinv, const double *dinv1, int nthreads,
+                                                            double &np, double &bad, double &np1, double &bad1)
 {
     for (int i = threadIdx.x; i < d.Fpad; i += nthreads) {
         if (d.uinv[i] < 0) continue;             // identity padding
-        const double v = dinv[i];
-        if (!isfinite(v) || v == 0.0) bad += 1; else if (v > 0) np += 1;
+        inertia_classify(dinv[i], true, np, bad);
+        if (dinv1) inertia_classify(dinv1[i], true, np1, bad1);
+    }
+}
+// CH elements per thread and chunk, every load of a chunk requested before the first is tested: one exposed round trip per
+// chunk instead of two or three per element.  Indices are clamped to Fpad - 1 (uinv, dinv and dinv1 are Fpad long: every
+// clamped load is valid); a position beyond Fpad counts as padding.  Same classification as the serial loop, by predicated
+// adds into four named scalars (an array of counters indexed at run time goes through scratch).
+template <int CH>
+static __device__ __forceinline__ void inertia_count(const DV &d, const double *dinv, const double *dinv1, int nthreads,
+                                                     double &np, double &bad, double &np1, double &bad1)
+{
+    const int F = d.Fpad;
+    for (int base = threadIdx.x; base < F; base += CH * nthreads) {
+        int u[CH];
+        double v[CH], w[CH];
+#pragma unroll
+        for (int q = 0; q < CH; ++q) {
+            const int i = base + q * nthreads, ii = i < F ? i : F - 1;
+            u[q] = d.uinv[ii];
+            v[q] = dinv[ii];
+        }
+        if (dinv1) {                                                    // (uniform over the workgroup)
+#pragma unroll
+            for (int q = 0; q < CH; ++q) {
+                const int i = base + q * nthreads, ii = i < F ? i : F - 1;
+                w[q] = dinv1[ii];
+            }
+        }
+#pragma unroll
+        for (int q = 0; q < CH; ++q) {
+            const bool live = base + q * nthreads < F && u[q] >= 0;     // (uinv < 0: identity padding)
+            inertia_classify(v[q], live, np, bad);
+        }
         if (dinv1) {
-            const double w = dinv1[i];
-            if (!isfinite(w) || w == 0.0) bad1 += 1; else if (w > 0) np1 += 1;
+#pragma unroll
+            for (int q = 0; q < CH; ++q) {
+                const bool live = base + q * nthreads < F && u[q] >= 0;
+                inertia_classify(w[q], live, np1, bad1);
+            }
         }
     }
 }

@@ -1787,45 +1787,91 @@ __device__ __forceinline__ void mf_top_bwd(const MfTopFront &F, const double *Bf
 // and backward -- the refinement solves (PH_RESOLVE) riding in the sweep's solve chain (ipm_sweep).  The direction is a
 // per-instance decision taken from the phase as it stands behind the inertia block; one workgroup serves one instance, so it
 // stays uniform and lives in a scalar register.
+// inertia: 1 = the inertia test of the PH_FACTOR instances in the prologue (round 4: k_inertia's job, a launch less per
+// sweep); 2 = the same with the former counting loop and the former order (SQPHIP_INERTIA_SERIAL=1).  With 1, the pivots are
+// counted a chunk at a time (inertia_count<12>, mf_dev.hpp: the condensed IEEE-118 structure is one chunk of 256 x 12), an
+// instance that does not speculate -- it can only be accepted with sel = 0, into PH_SOLVE -- requests the record of the first
+// front of its solve beside the pivots, and everybody reads the decision (phase, sel) from LDS instead of global memory.
+// (Requesting the whole first front -- image, vectors, records -- ahead of the decision was built in three arrangements;
+// each took the kernel from 248 registers to 256 and 3 - 18 spilled to AGPRs, for the ~3 us of one cold round trip: left out.)
+// LDS: [buf0][buf1][slack][updates][x][D^-1 L^-1 b][records] as the plan lays them out (mfplan.hip), and behind the records
+// the count's exchange (sixteen doubles) and the published decision (two ints: phase, sel) -- apart from everything the
+// prologue's commit writes, so a wave may commit while another still reads the decision.
 __global__ __launch_bounds__(256) void k_mf_solve_top2(DV d, int want, int do_fwd_want, int inertia, int also)
 {
     const int inst = blockIdx.x;
-    if (inertia && d.phase[inst] == PH_FACTOR) {
-        // the inertia test of this instance's factorisation (round 4: k_inertia's job, a launch less per sweep): pivot signs
-        // counted by the four waves, decision by thread 0, published to the workgroup by the barrier
-        IpmState &st = d.ist[inst];
-        const bool spec = mf_speculates(d, st);
-        double c[4] = {0.0, 0.0, 0.0, 0.0};
-        inertia_count(d, d.dinv + (long)inst * d.Fpad, spec ? d.dinv1 + (long)inst * d.Fpad : nullptr, 256, c[0], c[1], c[2], c[3]);
-        extern __shared__ double mf_lds[];
-        double (*ish)[4] = reinterpret_cast<double (*)[4]>(mf_lds);      // (sixteen doubles of the dynamic LDS, free until the solve starts)
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) c[q] += __shfl_xor(c[q], o);
-            if ((threadIdx.x & 63) == 0) ish[q][threadIdx.x >> 6] = c[q];
-        }
-        __syncthreads();
-        if (threadIdx.x == 0)
-            inertia_decide(d, inst, st, spec, (ish[0][0] + ish[0][1]) + (ish[0][2] + ish[0][3]), (ish[1][0] + ish[1][1]) + (ish[1][2] + ish[1][3]),
-                           (ish[2][0] + ish[2][1]) + (ish[2][2] + ish[2][3]), (ish[3][0] + ish[3][1]) + (ish[3][2] + ish[3][3]));
-        __syncthreads();
-    }
-    const int ph = __builtin_amdgcn_readfirstlane(d.phase[inst]);
-    if (ph != want && ph != also) return;
-    const int do_fwd = ph == want ? do_fwd_want : 1;
     const MfDev &M = d.mf;
     extern __shared__ double mf_lds[];
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int cand = d.ist[inst].sel;
-    const double *arena = mf_arena(d, inst, cand);
-    const double *dinv = mf_dinv(d, inst, cand);
-    double *vv = mf_vv(d, inst, cand);
-    double *xg = d.xv + (long)inst * d.Fpad;
     const int n = M.top_n, next = M.top_next;
     double *buf0 = mf_lds, *buf1 = buf0 + M.top_buf0, *uvec = buf1 + M.top_buf1 + 128, *xtop = uvec + next + M.top_utotal,
            *ytop = xtop + M.top_xtotal;
     int *recs = reinterpret_cast<int *>(ytop + M.top_xtotal);       // the front records, staged once: [n][16]
+    double *ish = reinterpret_cast<double *>(recs + 16 * n);        // the count's exchange: [4 counters][4 waves]
+    int *pub = reinterpret_cast<int *>(ish + 16);                   // the decision as thread 0 publishes it: phase, sel
+    double *xg = d.xv + (long)inst * d.Fpad;
+    const int *Tg = reinterpret_cast<const int *>(M.top_fr);
+    // the first front of the solve, in two halves: request (first_request: its record; first_issue: everything the record
+    // names, the staging of the records, the sources of the updates from below the top) and commit to LDS (below)
+    MfTopStage St;
+    MfTopFront F;
+    int fw[13], xs[4] = {0, 0, 0, 0}, rr[2] = {0, 0};
+    auto first_request = [&](int fwd) __attribute__((always_inline)) {
+        const int k0 = fwd ? 0 : n - 1;
+#pragma unroll
+        for (int q = 0; q < 13; ++q) fw[q] = Tg[16 * k0 + q];
+    };
+    auto first_issue = [&](int fwd, int cd) __attribute__((always_inline)) {
+        int *w = reinterpret_cast<int *>(&F);
+#pragma unroll
+        for (int q = 0; q < 13; ++q) w[q] = __builtin_amdgcn_readfirstlane(fw[q]);
+        if (fwd) {
+#pragma unroll
+            for (int q = 0; q < 4; ++q) if (tid + 256 * q < next) xs[q] = M.top_ext[tid + 256 * q];
+        }
+        mf_top_issue<4>(M, F, mf_arena(d, inst, cd), mf_dinv(d, inst, cd), fwd ? xg : mf_vv(d, inst, cd), wave, lane, St);
+#pragma unroll
+        for (int q = 0; q < 2; ++q) if (tid + 256 * q < 16 * n) rr[q] = Tg[tid + 256 * q];
+    };
+    // what the phase of an instance that passes the inertia test becomes, and the direction it is then served with (-1: not by
+    // this launch)
+    const int pass_fwd = PH_SOLVE == want ? do_fwd_want : (PH_SOLVE == also ? 1 : -1);
+    int ph = __builtin_amdgcn_readfirstlane(d.phase[inst]);
+    int cand = -1;                                                  // (-1: sel still to be read from global memory)
+    const bool test = inertia && ph == PH_FACTOR;
+    IpmState &st = d.ist[inst];
+    const bool spec = test && __builtin_amdgcn_readfirstlane(mf_speculates(d, st) ? 1 : 0) != 0;
+    // ahead: the record of the first front is requested beside the pivots -- for an instance that does not speculate, which can
+    // only be accepted with sel = 0 and into PH_SOLVE, so its direction is known at entry (not in the former order)
+    const bool ahead = test && inertia != 2 && !spec && pass_fwd >= 0;
+    if (test) {
+        // pivot signs counted by the four waves, decision by thread 0, published to the workgroup through LDS
+        const double *dv0 = d.dinv + (long)inst * d.Fpad, *dv1 = spec ? d.dinv1 + (long)inst * d.Fpad : nullptr;
+        double np = 0.0, bad = 0.0, np1 = 0.0, bad1 = 0.0;
+        if (ahead) first_request(pass_fwd);
+        if (inertia == 2) inertia_count_serial(d, dv0, dv1, 256, np, bad, np1, bad1);
+        else inertia_count<12>(d, dv0, dv1, 256, np, bad, np1, bad1);
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            np += __shfl_xor(np, o); bad += __shfl_xor(bad, o); np1 += __shfl_xor(np1, o); bad1 += __shfl_xor(bad1, o);
+        }
+        if (lane == 0) { ish[wave] = np; ish[4 + wave] = bad; ish[8 + wave] = np1; ish[12 + wave] = bad1; }
+        __syncthreads();
+        if (tid == 0) {
+            inertia_decide(d, inst, st, spec, (ish[0] + ish[1]) + (ish[2] + ish[3]), (ish[4] + ish[5]) + (ish[6] + ish[7]),
+                           (ish[8] + ish[9]) + (ish[10] + ish[11]), (ish[12] + ish[13]) + (ish[14] + ish[15]));
+            pub[0] = d.phase[inst]; pub[1] = st.sel;
+        }
+        __syncthreads();
+        if (inertia == 2) ph = __builtin_amdgcn_readfirstlane(d.phase[inst]);      // (the former order: both from global memory)
+        else { ph = __builtin_amdgcn_readfirstlane(pub[0]); cand = __builtin_amdgcn_readfirstlane(pub[1]); }
+    }
+    if (ph != want && ph != also) return;
+    if (cand < 0) cand = d.ist[inst].sel;
+    const int do_fwd = ph == want ? do_fwd_want : 1;
+    const double *arena = mf_arena(d, inst, cand);
+    const double *dinv = mf_dinv(d, inst, cand);
+    double *vv = mf_vv(d, inst, cand);
     // steps: forward over fronts 0 .. n-1, then backward n-1 .. 0 (the root does both in its step); or backward only
     const int nsteps = do_fwd ? 2 * n - 1 : n;
 #define MF_TOP_FRONT_OF(j) (do_fwd ? ((j) < n ? (j) : 2 * n - 2 - (j)) : n - 1 - (j))
@@ -1839,18 +1885,13 @@ __global__ __launch_bounds__(256) void k_mf_solve_top2(DV d, int want, int do_fw
     };
     // prologue, one round trip deep: the first front straight from its global record (all four waves fetch), the records
     // and the updates from below the top alongside
-    MfTopStage St;
-    MfTopFront F;
+    if (!(ahead && ph == PH_SOLVE)) first_request(do_fwd);
+    first_issue(do_fwd, cand);
     {
         const int k0 = MF_TOP_FRONT_OF(0);
-        const int *Tg = reinterpret_cast<const int *>(M.top_fr);
-        int *w = reinterpret_cast<int *>(&F);
 #pragma unroll
-        for (int q = 0; q < 13; ++q) w[q] = __builtin_amdgcn_readfirstlane(Tg[16 * k0 + q]);
-        int xs[4] = {0, 0, 0, 0};
-        if (do_fwd) for (int t = tid, q = 0; t < next && q < 4; t += 256, ++q) xs[q] = M.top_ext[t];
-        mf_top_issue<4>(M, F, arena, dinv, do_fwd ? xg : vv, wave, lane, St);
-        for (int t = tid; t < 16 * n; t += 256) recs[t] = Tg[t];
+        for (int q = 0; q < 2; ++q) if (tid + 256 * q < 16 * n) recs[tid + 256 * q] = rr[q];
+        for (int t = tid + 512; t < 16 * n; t += 256) recs[t] = Tg[t];
         if (do_fwd) {
 #pragma unroll
             for (int q = 0; q < 4; ++q) if (tid + 256 * q < next) uvec[tid + 256 * q] = arena[xs[q]];
@@ -2232,7 +2273,8 @@ void mf_solve(Ctx &C, int want, bool skip_fwd, bool inertia, int also)
     if (d.mf.top_n > 0 && !generic) {
         const size_t lds = (size_t)C.mfp().top2_lds_bytes;
         C.mf_census[MFK_SOLVE_TOP2]++;
-        hipLaunchKernelGGL(k_mf_solve_top2, dim3(d.B), dim3(256), lds, s, d, want, skip_fwd ? 0 : 1, inertia ? 1 : 0, also);
+        const char *ser = getenv("SQPHIP_INERTIA_SERIAL");      // (read per call: tests flip it) the former counting loop and order
+        hipLaunchKernelGGL(k_mf_solve_top2, dim3(d.B), dim3(256), lds, s, d, want, skip_fwd ? 0 : 1, inertia ? (ser && atoi(ser) ? 2 : 1) : 0, also);
     } else if (const MfLaunch &T = C.mfp().top; T.count > 0) {
         C.mf_census[MFK_SOLVE_TOP]++;
         hipLaunchKernelGGL(k_mf_solve_top, dim3(d.B), dim3(256), T.lds_bytes, s, d, T.begin, T.count, want, skip_fwd ? 0 : 1, generic,
