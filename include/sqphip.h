@@ -423,6 +423,35 @@ int sqphip_nlp_attach_affine(sqphip_ctx *ctx, int64_t nterms, const int64_t *tro
                              const int64_t *avar /* [nargs] 1-based */, const double *acoef /* [nargs] or NULL: ones */,
                              const int32_t *fkind, const int32_t *fexp, const double *fshift /* [nfac] or NULL: zeros */,
                              const double *g0 /* [m] or NULL */, double f0);
+/* The same model once more, with two restrictions lifted.
+ * (1) A variable may occur in several factors of one term: x log x (a POW and a LOG factor on x), x exp(-x), x / (1 + x),
+ * (x + y)(x - y), sin x cos x, any product of affine forms with overlapping supports.  Twice inside one factor stays
+ * refused (add the coefficients).  With F(v) the (factor, argument) couples of a term on variable v the device files
+ *     d/dx_v       = c sum_{(a,j) in F(v)} a_j kappa'_a prod_{k != a} kappa_k
+ *     d2/dx_v dx_w = c sum_{(a,j) in F(v)} sum_{(b,l) in F(w)} a_j a_l [a = b ? kappa''_a prod_{k != a} kappa_k
+ *                                                                            : kappa'_a kappa'_b prod_{k != a, b} kappa_k],
+ * every summand one plan entry: two different arguments on the same variable enter the slot (v, v) twice, once per order.
+ * The context must have been created with a Jacobian COO that holds (i, v) for every argument of a term of row i and --
+ * unless nnzH = 0 -- a Hessian COO that holds the lower entry (v, w) for every two arguments of a term that lie in
+ * different factors, or in the same factor when it is not plain linear (POW, e = 1), and (v, v) for every argument of a
+ * factor that is not plain linear and for every variable that sits in two factors of a term, plain linear or not.
+ * (2) The menu goes on after LOG: 5 SQRT, 6 TANH, 7 ATAN, 8 SIGMOID 1 / (1 + e^-u), 9 SOFTPLUS log(1 + e^u), 10 POWR u^p with
+ * the real exponent p = fpar[k], finite and not 0 (fpar is read for POWR only and may be NULL when there is none; a POWR
+ * factor is never plain linear, p = 1 included).  SIGMOID and SOFTPLUS are evaluated through e = exp(-|u|) (e / (1 + e)
+ * or 1 / (1 + e); max(u, 0) + log1p(e)) and stay finite with their derivatives for every finite u.  SQRT and POWR need
+ * u > 0 at every point the solver visits: the caller's business, as for LOG.
+ * Everything else is sqphip_nlp_attach_affine: the limits (8 factors, 8 arguments), the order of the sums, the rule for
+ * rows 1..num_linear, the refusals and their 1-based messages (plus: POWR without fpar, a real exponent that is 0 or not
+ * finite), SQPHIP_ESTATE on a context attached before, the block f0 | g0 | c of an instance, and the result is an NLP
+ * context to every other entry point.  A model that sqphip_nlp_attach or sqphip_nlp_attach_affine takes files the same
+ * bits through this call. */
+int sqphip_nlp_attach_general(sqphip_ctx *ctx, int64_t nterms, const int64_t *trow, const double *tcoef,
+                              const int64_t *tptr /* [nterms + 1] factors of a term */,
+                              const int64_t *aptr /* [nfac + 1] arguments of a factor */,
+                              const int64_t *avar /* [nargs] 1-based */, const double *acoef /* [nargs] or NULL: ones */,
+                              const int32_t *fkind, const int32_t *fexp,
+                              const double *fpar /* [nfac] or NULL: real exponent, read for POWR only */,
+                              const double *fshift /* [nfac] or NULL: zeros */, const double *g0 /* [m] or NULL */, double f0);
 /* Per-instance values (f0 one value, g0 [m], tcoef [nterms] in the term order of the attach) and the start x0 [n];
  * any pointer may be NULL: keep.  Bounds go through sqphip_set_bounds. */
 int sqphip_nlp_set_instance(sqphip_ctx *ctx, int32_t inst, const double *f0, const double *g0,

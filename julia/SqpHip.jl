@@ -245,6 +245,16 @@ hip_nlp_attach_affine(ctx::Ptr{Cvoid}, trow::Vector{Int64}, tcoef::Vector{Float6
                       (Ptr{Cvoid}, Int64, Ptr{Int64}, Ptr{Cdouble}, Ptr{Int64}, Ptr{Int64}, Ptr{Int64}, Ptr{Cdouble}, Ptr{Int32},
                        Ptr{Int32}, Ptr{Cdouble}, Ptr{Cdouble}, Cdouble),
                       ctx, length(trow), trow, tcoef, tptr, aptr, avar, acoef, fkind, fexp, fshift, g0, f0))
+# ... with variables shared by the factors of a term (x log x: a POW and a LOG factor on x; never twice inside one factor) and
+# the wider menu (sqphip_nlp_attach_general): 5 sqrt, 6 tanh, 7 atan, 8 1 / (1 + e^-u), 9 log(1 + e^u), 10 u^p with the real
+# exponent p = fpar[k] (finite, not 0; fpar = nothing when no factor is of kind 10).  Everything else as hip_nlp_attach_affine.
+hip_nlp_attach_general(ctx::Ptr{Cvoid}, trow::Vector{Int64}, tcoef::Vector{Float64}, tptr::Vector{Int64}, aptr::Vector{Int64},
+                       avar::Vector{Int64}, acoef::Vector{Float64}, fkind::Vector{Int32}, fexp::Vector{Int32},
+                       fpar::Union{Nothing, Vector{Float64}}, fshift::Vector{Float64}, g0::Vector{Float64}, f0::Real) =
+    _check(ctx, ccall((:sqphip_nlp_attach_general, LIBSQPHIP), Cint,
+                      (Ptr{Cvoid}, Int64, Ptr{Int64}, Ptr{Cdouble}, Ptr{Int64}, Ptr{Int64}, Ptr{Int64}, Ptr{Cdouble}, Ptr{Int32},
+                       Ptr{Int32}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Cdouble),
+                      ctx, length(trow), trow, tcoef, tptr, aptr, avar, acoef, fkind, fexp, _vals(fpar), fshift, g0, f0))
 hip_nlp_set_instance(ctx::Ptr{Cvoid}, inst::Integer; f0 = nothing, g0 = nothing, tcoef = nothing, x0 = nothing) =
     _check(ctx, ccall((:sqphip_nlp_set_instance, LIBSQPHIP), Cint,
                       (Ptr{Cvoid}, Int32, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}),

@@ -1702,13 +1702,16 @@ static void plan_order(int owners, const std::vector<int> &own, std::vector<int>
     for (size_t e = 0; e < own.size(); ++e) ord[fill[own[e]]++] = (int)e;
 }
 
-// Both entry points.  !affine: sqphip_nlp_attach, aptr is null and factor k has the one argument avar[k] with coefficient acoef[k].
+// The three entry points.  !affine: sqphip_nlp_attach, aptr is null and factor k has the one argument avar[k] with coefficient acoef[k].
 // A one-argument factor keeps its coefficient in pass 1 (fab, chain factors folded into phi', phi'') and weight 1.0 in the
 // plans; a factor of several arguments stores kappa', kappa'' and its arguments weigh a_v (nlp_dev.hpp).
-static int nlp_attach_impl(sqphip_ctx *h, const char *who, bool affine, int64_t nterms, const int64_t *trow, const double *tcoef, const int64_t *tptr,
-                           const int64_t *aptr, const int64_t *avar, const double *acoef, const int32_t *fkind, const int32_t *fexp,
-                           const double *fshift, const double *g0, double f0)
+// general: sqphip_nlp_attach_general -- the menu up to POWR (fpar: its real exponents) and variables shared by the factors of
+// a term; the two older calls are this one with the menu check at LOG and the distinct-variables check switched on.
+static int nlp_attach_impl(sqphip_ctx *h, const char *who, bool affine, bool general, int64_t nterms, const int64_t *trow, const double *tcoef,
+                           const int64_t *tptr, const int64_t *aptr, const int64_t *avar, const double *acoef, const int32_t *fkind,
+                           const int32_t *fexp, const double *fpar, const double *fshift, const double *g0, double f0)
 {
+    const int last_kind = general ? NLP_POWR : NLP_LOG;
     if (!h) return SQPHIP_EINVAL;
     Ctx &C0 = h->c;
     if (C0.acopf_attached) {
@@ -1754,7 +1757,7 @@ static int nlp_attach_impl(sqphip_ctx *h, const char *who, bool affine, int64_t 
     std::vector<int> fke((size_t)std::max<int64_t>(nfac, 1), 0), fv(fke.size(), 0);
     std::vector<double2> fab(fke.size(), double2{1.0, 0.0});
     std::vector<int> ap((size_t)nfac + 1, 0), av((size_t)std::max<int64_t>(nargs, 1), 0);
-    std::vector<double> ac(av.size(), 1.0), aw(av.size(), 1.0);
+    std::vector<double> ac(av.size(), 1.0), aw(av.size(), 1.0), fpw(fke.size(), 0.0);
     bool multi = false;
     for (int64_t t = 0; t < nterms; ++t) {
         const int64_t i = trow[t], k0 = tptr[t], k1 = tptr[t + 1];
@@ -1767,13 +1770,19 @@ static int nlp_attach_impl(sqphip_ctx *h, const char *who, bool affine, int64_t 
             const double b = fshift ? fshift[k] : 0.0;
             for (int64_t j = j0; j < j1; ++j)
                 if (avar[j] < 1 || avar[j] > n) return nlp_fail(h, who, t, kf, "variable " + std::to_string(avar[j]) + " out of range");
-            if (fkind[k] < NLP_POW || fkind[k] > NLP_LOG) return nlp_fail(h, who, t, kf, "unknown kind " + std::to_string(fkind[k]));
+            if (fkind[k] < NLP_POW || fkind[k] > last_kind) return nlp_fail(h, who, t, kf, "unknown kind " + std::to_string(fkind[k]));
+            if (fkind[k] == NLP_POWR) {
+                if (!fpar) return nlp_fail(h, who, t, kf, "a POWR factor needs its real exponent: fpar is null");
+                if (!std::isfinite(fpar[k]) || fpar[k] == 0.0)
+                    return nlp_fail(h, who, t, kf, "real exponent " + std::to_string(fpar[k]) + " (finite and not 0)");
+                fpw[k] = fpar[k];
+            }
             const int e = fkind[k] == NLP_POW ? fexp[k] : 1;
             if (e == 0 || e > 32 || e < -32) return nlp_fail(h, who, t, kf, "exponent " + std::to_string(e) + " (1 <= |e| <= 32)");
             for (int64_t j = j0; j < j1; ++j) {
                 for (int64_t j2 = j0; j2 < j; ++j2)
                     if (avar[j2] == avar[j]) return nlp_fail(h, who, t, kf, "variable " + std::to_string(avar[j]) + " twice in one factor (add the coefficients)");
-                for (int64_t j2 = a0(k0); j2 < j0; ++j2)
+                for (int64_t j2 = a0(k0); !general && j2 < j0; ++j2)
                     if (avar[j2] == avar[j]) return nlp_fail(h, who, t, kf, "variable " + std::to_string(avar[j]) + " twice in one term (write x^2)");
             }
             plain[kf] = fkind[k] == NLP_POW && e == 1;
@@ -1784,7 +1793,7 @@ static int nlp_attach_impl(sqphip_ctx *h, const char *who, bool affine, int64_t 
                 return nlp_fail(h, who, t, kf, "row " + std::to_string(i) + " is one of the num_linear = " + std::to_string(nlin) +
                                           (affine ? " linear rows: a single POW factor with e = 1, one argument with coefficient 1, shift 0 only"
                                                   : " linear rows: a single POW factor with e = 1, a = 1, b = 0 only"));
-            fv[k] = one ? (int)avar[j0] - 1 : -1; fke[k] = fkind[k] + 8 * (e + 32); fab[k] = double2{a, b};
+            fv[k] = one ? (int)avar[j0] - 1 : -1; fke[k] = fkind[k] + (e + 32) * (1 << NLP_KIND_BITS); fab[k] = double2{a, b};
             ap[k] = (int)j0; ap[k + 1] = (int)j1;
             for (int64_t j = j0; j < j1; ++j) {
                 av[j] = (int)avar[j] - 1; ac[j] = acoef ? acoef[j] : 1.0; aw[j] = one ? 1.0 : ac[j];
@@ -1810,7 +1819,10 @@ static int nlp_attach_impl(sqphip_ctx *h, const char *who, bool affine, int64_t 
                             const int hs = hfind(av[j], av[j2]);
                             if (hs < 0) return nlp_fail(h, who, t, k - k0, "needs the Hessian entry (" + std::to_string(std::max(avar[j], avar[j2])) + ", " +
                                                                       std::to_string(std::min(avar[j], avar[j2])) + ") that the structure of sqphip_create lacks");
-                            h_own.push_back(hs); h_e.push_back(int4{(int)t, ent(k2, j2), ent(k, j), (int)i - 1});
+                            // two arguments on one variable (general only: different factors): both ordered pairs count
+                            for (int c = (j2 != j && av[j2] == av[j]) ? 2 : 1; c > 0; --c) {
+                                h_own.push_back(hs); h_e.push_back(int4{(int)t, ent(k2, j2), ent(k, j), (int)i - 1});
+                            }
                         }
                     }
     }
@@ -1850,6 +1862,7 @@ static int nlp_attach_impl(sqphip_ctx *h, const char *who, bool affine, int64_t 
         P.ptr = C.upload(ptr); P.tptr = C.upload(tp); P.fvar = C.upload(fv); P.fke = C.upload(fke); P.fab = C.upload(fab);
         P.ot = C.upload(ot); P.ge = C.upload(ge); P.fe = C.upload(fe); P.je = C.upload(je); P.he = C.upload(he);
         P.aptr = C.upload(ap); P.avar = C.upload(av); P.acoef = C.upload(ac); P.aw = C.upload(aw); P.multi = multi ? 1 : 0;
+        P.fpar = C.upload(fpw);
         NlpDev *pd = (NlpDev *)C.dalloc<char>(sizeof(NlpDev));
         SQPHIP_HIP_OK(hipMemcpyAsync(pd, &P, sizeof(NlpDev), hipMemcpyHostToDevice, C.stream));
         std::vector<double> all((size_t)d.B * nv);
@@ -1870,14 +1883,21 @@ extern "C" int sqphip_nlp_attach(sqphip_ctx *h, int64_t nterms, const int64_t *t
                                  const int64_t *fvar, const int32_t *fkind, const int32_t *fexp, const double *fscale,
                                  const double *fshift, const double *g0, double f0)
 {
-    return nlp_attach_impl(h, "sqphip_nlp_attach", false, nterms, trow, tcoef, tptr, nullptr, fvar, fscale, fkind, fexp, fshift, g0, f0);
+    return nlp_attach_impl(h, "sqphip_nlp_attach", false, false, nterms, trow, tcoef, tptr, nullptr, fvar, fscale, fkind, fexp, nullptr, fshift, g0, f0);
 }
 
 extern "C" int sqphip_nlp_attach_affine(sqphip_ctx *h, int64_t nterms, const int64_t *trow, const double *tcoef, const int64_t *tptr,
                                         const int64_t *aptr, const int64_t *avar, const double *acoef, const int32_t *fkind,
                                         const int32_t *fexp, const double *fshift, const double *g0, double f0)
 {
-    return nlp_attach_impl(h, "sqphip_nlp_attach_affine", true, nterms, trow, tcoef, tptr, aptr, avar, acoef, fkind, fexp, fshift, g0, f0);
+    return nlp_attach_impl(h, "sqphip_nlp_attach_affine", true, false, nterms, trow, tcoef, tptr, aptr, avar, acoef, fkind, fexp, nullptr, fshift, g0, f0);
+}
+
+extern "C" int sqphip_nlp_attach_general(sqphip_ctx *h, int64_t nterms, const int64_t *trow, const double *tcoef, const int64_t *tptr,
+                                         const int64_t *aptr, const int64_t *avar, const double *acoef, const int32_t *fkind,
+                                         const int32_t *fexp, const double *fpar, const double *fshift, const double *g0, double f0)
+{
+    return nlp_attach_impl(h, "sqphip_nlp_attach_general", true, true, nterms, trow, tcoef, tptr, aptr, avar, acoef, fkind, fexp, fpar, fshift, g0, f0);
 }
 
 extern "C" int sqphip_nlp_set_instance(sqphip_ctx *h, int32_t inst, const double *f0, const double *g0, const double *tcoef,

@@ -21,6 +21,12 @@
 // c (prod 1.0) rounds as c prod does, so both entry points file the same bits for the same one-argument model.  A context
 // without any multi-argument factor (NlpDev::multi = 0, uniform over the launch) skips the weight loads: the same bits, since
 // the weights it skips are 1.0.
+// sqphip_nlp_attach_general: a variable may sit in several factors of one term (x log x, (x + y)(x - y)), and the menu grows
+// by sqrt, tanh, atan, the logistic pair 1 / (1 + e^-u), log(1 + e^u) in their overflow-free forms and u^p with a real p.
+// Shared variables are the host's business alone: the plans file one entry per ordered pair of (factor, argument) couples
+// and the sums above do the rest.  The six kinds sit behind one out-of-line function of scalars and the factor's place in
+// the workspace (nlp_kappa_wide, one call site per nlp_eval): inlined, tanh / atan / log1p / pow cost the kernels that
+// inline nlp_eval 120 - 130 B of scratch per lane each.
 #pragma once
 #include "ctx.hpp"
 #include "dev_util.hpp"
@@ -28,7 +34,9 @@
 
 namespace sqphip {
 
-enum { NLP_POW = 0, NLP_SIN = 1, NLP_COS = 2, NLP_EXP = 3, NLP_LOG = 4 };
+enum { NLP_POW = 0, NLP_SIN = 1, NLP_COS = 2, NLP_EXP = 3, NLP_LOG = 4,
+       NLP_SQRT = 5, NLP_TANH = 6, NLP_ATAN = 7, NLP_SIGMOID = 8, NLP_SOFTPLUS = 9, NLP_POWR = 10 };
+enum { NLP_KIND_BITS = 4, NLP_KIND_MASK = (1 << NLP_KIND_BITS) - 1 };     // fke = kind + 16 * (exponent + 32)
 enum { NLP_NONE = -(1 << 30), NLP_ARG = (1 << 28) - 1 };     // no factor of a term; the argument bits of a plan entry (nargs <= 2^28)
 
 struct NlpDev {
@@ -37,7 +45,7 @@ struct NlpDev {
     const int *ptr;                       // the four CSR row pointers back to back: rows [m + 1], variables [n + 1], slots
     const int *tptr;                      // [nterms + 1] factors of a term
     const int *fvar;                      // [nfac] variable of a one-argument factor (0-based); -1: the arguments aptr[k] .. aptr[k + 1] - 1
-    const int *fke;                       // [nfac] kind + 8 * (exponent + 32)
+    const int *fke;                       // [nfac] kind + 16 * (exponent + 32)
     const double2 *fab;                   // [nfac] (a, b)
     const int *ot;                        // [nobj] the objective's terms
     const int *ge;                        // row i: g0_i + sum over terms t
@@ -50,7 +58,38 @@ struct NlpDev {
     const double *acoef;                  // [nargs] its coefficient (pass 1)
     const double *aw;                     // [nargs] its weight in the derivative plans: the coefficient, 1.0 in a one-argument factor
     int multi;                            // some factor has several arguments; 0: every weight is 1.0 and the plans do not load aw
+    const double *fpar;                   // [nfac] real exponent of a POWR factor (loaded for that kind only)
 };
+
+// pass 1 of a factor of the kinds SQRT .. POWR at u: kappa, a kappa', a^2 kappa'' to w[0], w[nf], w[2 nf] (nd: how many
+// derivatives).  Out of line on purpose and never handed DV: scalars and the factor's workspace pointer only.
+struct NlpK3 { double k0, k1, k2; };
+static __device__ __noinline__ void nlp_kappa_wide(int kind, double a, double u, double pw, int nd, double *__restrict__ w, int nf)
+{
+    NlpK3 r;
+    if (kind == NLP_SQRT) {
+        const double s = sqrt(u);
+        r.k0 = s; r.k1 = 0.5 / s; r.k2 = -0.25 / (u * s);
+    } else if (kind == NLP_TANH) {
+        const double t = tanh(u), d = 1.0 - t * t;
+        r.k0 = t; r.k1 = d; r.k2 = -2.0 * t * d;
+    } else if (kind == NLP_ATAN) {
+        const double q = 1.0 / (1.0 + u * u);
+        r.k0 = atan(u); r.k1 = q; r.k2 = -2.0 * u * (q * q);
+    } else if (kind == NLP_POWR) {
+        const double v = pow(u, pw);
+        r.k0 = v; r.k1 = pw * v / u; r.k2 = pw * (pw - 1.0) * v / (u * u);
+    } else {
+        // e = exp(-|u|) <= 1 never overflows; s and 1 - s both from e, none by cancellation
+        const double e = exp(-fabs(u)), den = 1.0 / (1.0 + e);
+        const double s = u < 0.0 ? e * den : den, sc = u < 0.0 ? den : e * den;
+        if (kind == NLP_SIGMOID) { r.k0 = s; r.k1 = s * sc; r.k2 = s * sc * (sc - s); }
+        else { r.k0 = fmax(u, 0.0) + log1p(e); r.k1 = s; r.k2 = s * sc; }
+    }
+    w[0] = r.k0;
+    if (nd >= 1) w[nf] = a * r.k1;
+    if (nd >= 2) w[2 * nf] = a * a * r.k2;
+}
 
 // c-free product of term t with its factors a and b (counted within the term) differentiated (a == b: twice;
 // NLP_NONE: not at all), in factor order
@@ -65,13 +104,16 @@ static __device__ __forceinline__ double nlp_prod(const int *__restrict__ tptr, 
     return p;
 }
 
-// pass 1 for factor k at u = a x + b
-static __device__ __forceinline__ void nlp_factor(int ke, double a, double u, bool d1, bool d2, double *__restrict__ w, int nf, int k)
+// pass 1 for factor k at u = a x + b (pw: the exponent of a POWR factor)
+static __device__ __forceinline__ void nlp_factor(int ke, double a, double u, double pw, bool d1, bool d2, double *__restrict__ w, int nf, int k)
 {
-    const int kind = ke & 7;
+    const int kind = ke & NLP_KIND_MASK;
     double p0, p1 = 0.0, p2 = 0.0;
-    if (kind == NLP_POW) {
-        const int e = (ke >> 3) - 32, ae = e < 0 ? -e : e;
+    if (kind >= NLP_SQRT) {
+        nlp_kappa_wide(kind, a, u, pw, (int)d1 + (int)d2, w + k, nf);
+        return;
+    } else if (kind == NLP_POW) {
+        const int e = (ke >> NLP_KIND_BITS) - 32, ae = e < 0 ? -e : e;
         const double q = e < 0 ? 1.0 / u : u;
         // lo = q^(ae - 2) (e >= 2) or 1; then u^(e-2), u^(e-1), u^e upwards (e > 0) or q^ae, q^(ae+1), q^(ae+2) (e < 0)
         double lo = 1.0;
@@ -118,12 +160,17 @@ static __device__ __forceinline__ void nlp_eval(const DV &d, int inst, const dou
     #pragma unroll 1
     for (int k = threadIdx.x; k < nf; k += TPB) {
         const double2 ab = q.fab[k];
-        const int v = q.fvar[k];
-        if (v >= 0) { nlp_factor(q.fke[k], ab.x, ab.x * x[v] + ab.y, d1, d2, w, nf, k); continue; }
-        double u = 0.0;
-        #pragma unroll 1
-        for (int j = q.aptr[k]; j < q.aptr[k + 1]; ++j) u += q.acoef[j] * x[q.avar[j]];
-        nlp_factor(q.fke[k], 1.0, u + ab.y, d1, d2, w, nf, k);
+        const int v = q.fvar[k], ke = q.fke[k];
+        const double pw = (ke & NLP_KIND_MASK) == NLP_POWR ? q.fpar[k] : 0.0;
+        double a = 1.0, u;
+        if (v >= 0) { a = ab.x; u = ab.x * x[v] + ab.y; }
+        else {
+            u = 0.0;
+            #pragma unroll 1
+            for (int j = q.aptr[k]; j < q.aptr[k + 1]; ++j) u += q.acoef[j] * x[q.avar[j]];
+            u += ab.y;
+        }
+        nlp_factor(ke, a, u, pw, d1, d2, w, nf, k);
     }
     __syncthreads();
     if (f_out) {

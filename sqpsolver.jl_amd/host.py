@@ -528,9 +528,27 @@ class Context:
         self._ck(self.L.sqphip_qcqp_set_instance(self.h, inst, *[_d(a) for a in arr], _d(_f(x0))))
 
     # ---- a sparse factorable NLP (nlp_terms.py; csrc/nlp_dev.hpp nlp_eval)
-    def nlp_attach(self, p):
+    def nlp_attach(self, p, general=None):
         """Structure of the batch and the values every instance starts with; p: nlp_terms.NlpTerms.  A p with argument arrays
-        (affine multi-variable factors) goes through sqphip_nlp_attach_affine, any other through sqphip_nlp_attach."""
+        (affine multi-variable factors) goes through sqphip_nlp_attach_affine, any other through sqphip_nlp_attach; a p
+        made for more -- p.general, which make_nlp_terms sets for a variable shared by two factors of a term, a kind above
+        LOG or a real exponent (nlp_terms.needs_general); fpar set -- through sqphip_nlp_attach_general.  A model of the
+        older calls stays on them, so they refuse what they always refused.  general = True / False overrides the choice
+        (a model of the old class files the same bits through the new call)."""
+        from .nlp_terms import nlp_terms_args
+        if general is None:
+            general = bool(getattr(p, "general", False)) or getattr(p, "fpar", None) is not None
+        if general:
+            if not hasattr(self.L, "sqphip_nlp_attach_general"):
+                raise SqpHipError("libsqphip.so lacks sqphip_nlp_attach_general: rebuild it")
+            aptr, avar, acoef = nlp_terms_args(p)
+            t = [np.ascontiguousarray(a, dtype=np.int64) for a in (p.trow, p.tptr, aptr, avar)]
+            k = [np.ascontiguousarray(a, dtype=np.int32) for a in (p.fkind, p.fexp)]
+            v = [_f(a) for a in (p.tcoef, acoef, p.fshift, p.g0)]
+            par = None if getattr(p, "fpar", None) is None else _f(p.fpar)
+            self._ck(self.L.sqphip_nlp_attach_general(self.h, len(t[0]), _l(t[0]), _d(v[0]), _l(t[1]), _l(t[2]), _l(t[3]), _d(v[1]),
+                                                      _i(k[0]), _i(k[1]), _d(par), _d(v[2]), _d(v[3]), float(p.f0)))
+            return
         if getattr(p, "aptr", None) is not None:
             t = [np.ascontiguousarray(a, dtype=np.int64) for a in (p.trow, p.tptr, p.aptr, p.avar)]
             k = [np.ascontiguousarray(a, dtype=np.int32) for a in (p.fkind, p.fexp)]

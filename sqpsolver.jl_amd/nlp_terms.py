@@ -14,6 +14,11 @@ arguments, the variables of a term distinct across all arguments of all its fact
 arrays aptr / avar / acoef (None in the one-argument form above, where fvar / fscale say it all); in it fvar / fscale hold
 the first argument of every factor.
 
+A variable may also sit in several factors of one term and the menu may go beyond LOG (sqphip_nlp_attach_general): SQRT,
+TANH, ATAN, SIGMOID 1 / (1 + e^-u), SOFTPLUS log(1 + e^u) and POWR u^p with a real exponent p (finite, not 0; fpar holds
+it, and a float in the exponent's place of a POWR factor sets it).  x log x is [(i, POW), (i, LOG)], (x + y)(x - y) two
+plain affine factors.  Twice inside one factor stays an error.  SQRT and POWR need a positive argument, as LOG does.
+
     NlpTerms             the data (terms, factors, values, bounds, start)
     make_nlp_terms       ... from a list of (row, coefficient, [(variable, kind, e, a, b), ...]); a factor may be
                          ([(variable, coefficient), ...], kind, e, b) instead
@@ -22,6 +27,10 @@ the first argument of every factor.
     nlp_terms_rows       g(x) in numpy
     nlp_terms_synth      a seeded test problem over the whole menu with a start that satisfies every row
     nlp_affine_synth     the same with affine arguments and least-squares residuals in the objective
+    nlp_general_synth    the same with variables shared between the factors of a term and every kind up to POWR
+    entropy_model, cobb_douglas_model, logistic_model     three small models with known answers
+    needs_general        whether a problem is outside what sqphip_nlp_attach / _affine take (make_nlp_terms records it in
+                         NlpTerms.general, and Context.nlp_attach goes by that record)
     nlp_terms_scenario   scenario s of a problem: the same structure, other coefficients, the same feasible start
     from_qcqp            a Qcqp (qcqp.py) restated as terms
     from_polar_acopf     the polar ACOPF of acopf_layout restated as terms, on that layout's COO structures
@@ -34,6 +43,7 @@ import dataclasses
 import numpy as np
 
 POW, SIN, COS, EXP, LOG = 0, 1, 2, 3, 4
+SQRT, TANH, ATAN, SIGMOID, SOFTPLUS, POWR = 5, 6, 7, 8, 9, 10
 MAX_FACTORS = 8
 MAX_ARGS = 8
 
@@ -61,6 +71,9 @@ class NlpTerms:
     aptr: np.ndarray | None = None     # [nfac + 1] offsets into the argument arrays; None: one argument per factor (fvar, fscale)
     avar: np.ndarray | None = None     # [nargs] variable (1-based)
     acoef: np.ndarray | None = None    # [nargs] coefficient
+    fpar: np.ndarray | None = None     # [nfac] real exponent of a POWR factor (0 elsewhere); None: no POWR factor
+    general: bool = False              # written for sqphip_nlp_attach_general (make_nlp_terms: needs_general); False: a model
+                                       # of the older calls, which keep refusing what they refuse
 
     @property
     def affine(self) -> bool:
@@ -102,10 +115,11 @@ def _f64(a):
 def make_nlp_terms(n, m, num_linear, terms, g0=None, f0=0.0, xL=None, xU=None, gL=None, gU=None, x0=None) -> NlpTerms:
     """terms: (row, coefficient, factors) with row 0 for the objective and factors (variable, kind[, e[, a[, b]]]), 1-based
     variables; a factor may be (args, kind[, e[, b]]) with args a list of (variable, coefficient) pairs, and one such factor
-    makes the problem an affine one (aptr / avar / acoef set).  Missing vectors are zeros, missing bounds infinite."""
+    makes the problem an affine one (aptr / avar / acoef set).  The e of a POWR factor is its real exponent (fpar set).
+    Variables may repeat across the factors of a term.  Missing vectors are zeros, missing bounds infinite."""
     inf = np.inf
     full = lambda v, k, d: _f64(np.full(k, d) if v is None else v)
-    trow, tcoef, tptr, fv, fk, fe, fa, fb = [], [], [0], [], [], [], [], []
+    trow, tcoef, tptr, fv, fk, fe, fa, fb, fp = [], [], [0], [], [], [], [], [], []
     aptr, avar, acoef, affine = [0], [], [], False
     for row, coef, factors in terms:
         trow.append(int(row)); tcoef.append(float(coef))
@@ -118,13 +132,17 @@ def make_nlp_terms(n, m, num_linear, terms, g0=None, f0=0.0, xL=None, xU=None, g
                 var, kind, e, a, b = (tuple(fac) + (1, 1.0, 0.0)[len(fac) - 2:])[:5]
                 args = [(int(var), float(a))]
             fv.append(args[0][0] if args else 0); fa.append(args[0][1] if args else 1.0)
-            fk.append(int(kind)); fe.append(int(e)); fb.append(float(b))
+            real = int(kind) == POWR
+            fk.append(int(kind)); fe.append(1 if real else int(e)); fp.append(float(e) if real else 0.0); fb.append(float(b))
             avar += [v for v, _ in args]; acoef += [c for _, c in args]; aptr.append(len(avar))
         tptr.append(len(fv))
-    extra = (_i64(aptr), _i64(avar), _f64(acoef)) if affine else ()
-    return NlpTerms(n, m, num_linear, _i64(trow), _f64(tcoef), _i64(tptr), _i64(fv), np.ascontiguousarray(fk, dtype=np.int32),
-                    np.ascontiguousarray(fe, dtype=np.int32), _f64(fa), _f64(fb), full(g0, m, 0.0), float(f0),
-                    full(xL, n, -inf), full(xU, n, inf), full(gL, m, -inf), full(gU, m, inf), full(x0, n, 0.0), *extra)
+    extra = (_i64(aptr), _i64(avar), _f64(acoef)) if affine else (None, None, None)
+    extra += (_f64(fp) if POWR in fk else None,)
+    p = NlpTerms(n, m, num_linear, _i64(trow), _f64(tcoef), _i64(tptr), _i64(fv), np.ascontiguousarray(fk, dtype=np.int32),
+                 np.ascontiguousarray(fe, dtype=np.int32), _f64(fa), _f64(fb), full(g0, m, 0.0), float(f0),
+                 full(xL, n, -inf), full(xU, n, inf), full(gL, m, -inf), full(gU, m, inf), full(x0, n, 0.0), *extra)
+    p.general = needs_general(p)
+    return p
 
 
 def _term_of_factor(p: NlpTerms) -> np.ndarray:
@@ -173,7 +191,29 @@ def factor_values(p: NlpTerms, x) -> np.ndarray:
             out[k] = fn(u[k])
         k = p.fkind == POW
         out[k] = u[k] ** p.fexp[k].astype(np.float64)
+        for kind, fn in ((SQRT, np.sqrt), (TANH, np.tanh), (ATAN, np.arctan)):
+            k = p.fkind == kind
+            out[k] = fn(u[k])
+        # the logistic pair without overflow: e = exp(-|u|) <= 1
+        k = p.fkind == SIGMOID
+        e = np.exp(-np.abs(u[k]))
+        out[k] = np.where(u[k] < 0, e / (1.0 + e), 1.0 / (1.0 + e))
+        k = p.fkind == SOFTPLUS
+        out[k] = np.maximum(u[k], 0.0) + np.log1p(np.exp(-np.abs(u[k])))
+        k = p.fkind == POWR
+        if k.any():
+            out[k] = u[k] ** p.fpar[k]
     return out
+
+
+def needs_general(p: NlpTerms) -> bool:
+    """A variable shared by two factors of a term, a kind above LOG or fpar set: sqphip_nlp_attach_general's class."""
+    if getattr(p, "fpar", None) is not None or (len(p.fkind) and int(np.max(p.fkind)) > LOG):
+        return True
+    aptr, avar, _ = nlp_terms_args(p)
+    term = _term_of_factor(p)[np.repeat(np.arange(len(p.fkind), dtype=np.int64), np.diff(aptr))]
+    key = term * (p.n + 1) + avar
+    return len(np.unique(key)) < len(key)
 
 
 def _term_values(p: NlpTerms, x) -> np.ndarray:
@@ -291,6 +331,107 @@ def nlp_affine_synth(n: int = 24, m: int = 14, seed: int = 1, terms_per_row: int
         else:
             p.gL[i], p.gU[i] = g[i] - s, g[i] + s
     return p
+
+
+_POSITIVE = (LOG, SQRT, POWR)
+
+
+def nlp_general_synth(n: int = 24, m: int = 14, seed: int = 1, terms_per_row: int = 3, max_args: int = 3) -> NlpTerms:
+    """Seeded problem of sqphip_nlp_attach_general's class: the objective sum w_j (x_j - a_j)^2 with a = x0 +- 0.3, four
+    entropy terms x log x (two factors on one variable), four softplus residuals of three variables and two products
+    (x_i + x_j)(x_i - x_j) of plain affine factors; two leading linear rows; then rows of terms_per_row terms of 1-3 factors,
+    each with 1-max_args arguments drawn from a pool smaller than the argument count, so that factors of a term share
+    variables (never twice inside a factor); the kinds cycle through the new ones first and are uniform over all eleven
+    after.  LOG, SQRT, POWR and negative integer powers take positive coefficients (0.5, 1, 2) and shift 0 or 0.3, so their
+    argument stays above 0.1 on the whole box [0.2, 3]; the others take 1, -1, 0.5, 2, halved for EXP.  Real exponents come
+    from 0.5, 1.5, -0.7, 1.852.  g0 and the row bounds are placed as nlp_terms_synth places them: every row holds at x0."""
+    assert n >= 3 * max_args and 1 <= max_args <= MAX_ARGS
+    rng = np.random.default_rng(seed)
+    nlin = 2
+    x0 = rng.uniform(0.6, 1.4, n)
+    terms = []
+    a = x0 + 0.3 * rng.choice([-1.0, 1.0], n)
+    w = rng.uniform(0.5, 2.0, n)
+    for j in range(n):
+        terms.append((0, w[j], [(j + 1, POW, 2, 1.0, -a[j])]))
+    for j in rng.choice(n, 4, replace=False) + 1:
+        terms.append((0, 0.5, [(int(j), POW), (int(j), LOG)]))
+    for _ in range(4):
+        js = rng.choice(n, 3, replace=False)
+        c = rng.choice([1.0, -1.0, 0.5, 2.0], 3)
+        terms.append((0, 1.0, [([(int(j) + 1, float(cj)) for j, cj in zip(js, c)], SOFTPLUS, 1, -float(c @ x0[js]))]))
+    for _ in range(2):
+        i, j = (int(v) + 1 for v in rng.choice(n, 2, replace=False))
+        terms.append((0, 0.1, [([(i, 1.0), (j, 1.0)], POW, 1, 0.0), ([(i, 1.0), (j, -1.0)], POW, 1, 0.0)]))
+    kinds, made = [], 0
+    for i in range(1, m + 1):
+        if i <= nlin:
+            for j in rng.choice(n, terms_per_row, replace=False) + 1:
+                terms.append((i, rng.uniform(-1, 1), [(int(j), POW, 1, 1.0, 0.0)]))
+            kinds.append("eq" if i % 2 else "range")
+            continue
+        for _ in range(terms_per_row):
+            nargs = [int(rng.integers(1, max_args + 1)) for _ in range(int(rng.integers(1, 4)))]
+            pool = rng.choice(n, max(max(nargs), sum(nargs) - int(rng.integers(0, 3))), replace=False) + 1
+            facs = []
+            for na in nargs:
+                kind = SQRT + made % 6 if made < 12 else int(rng.integers(0, POWR + 1))
+                made += 1
+                e = int(rng.choice([-2, -1, 1, 2, 3])) if kind == POW else 1
+                if kind == POWR:
+                    e = float(rng.choice([0.5, 1.5, -0.7, 1.852]))
+                positive = kind in _POSITIVE or (kind == POW and e < 0)
+                c = rng.choice([0.5, 1.0, 2.0] if positive else [1.0, -1.0, 0.5, 2.0], na)
+                if kind == EXP:
+                    c = 0.5 * c
+                sh = float(rng.choice([0.0, 0.3]))
+                facs.append(([(int(j), float(cj)) for j, cj in zip(rng.choice(pool, na, replace=False), c)], kind, e, sh))
+            terms.append((i, rng.uniform(-1, 1), facs))
+        kinds.append(("eq", "upper", "range")[(i - nlin - 1) % 3])
+    p = make_nlp_terms(n, m, nlin, terms, g0=rng.uniform(-0.2, 0.2, m), f0=float(rng.standard_normal()),
+                       xL=np.full(n, 0.2), xU=np.full(n, 3.0), x0=x0)
+    g = nlp_terms_rows(p, x0)
+    for i, kind in enumerate(kinds):
+        s = rng.uniform(0.2, 1.0)
+        if kind == "eq":
+            p.gL[i] = p.gU[i] = g[i]
+        elif kind == "upper":
+            p.gL[i], p.gU[i] = -np.inf, g[i] + s
+        else:
+            p.gL[i], p.gU[i] = g[i] - s, g[i] + s
+    return p
+
+
+def entropy_model(c) -> NlpTerms:
+    """min sum_i x_i log x_i + c'x  s.t.  sum_i x_i = 1 (a linear row), 1e-6 <= x <= 1, from the uniform point.  Optimum
+    x_i = exp(-c_i) / sum_j exp(-c_j).  x log x is two factors on one variable."""
+    c = _f64(c)
+    n = len(c)
+    terms = [(0, 1.0, [(j + 1, POW), (j + 1, LOG)]) for j in range(n)] + [(0, c[j], [(j + 1, POW)]) for j in range(n)]
+    terms += [(1, 1.0, [(j + 1, POW)]) for j in range(n)]
+    return make_nlp_terms(n, 1, 1, terms, xL=np.full(n, 1e-6), xU=np.ones(n), gL=[1.0], gU=[1.0], x0=np.full(n, 1.0 / n))
+
+
+def cobb_douglas_model(alpha, prices, wealth) -> NlpTerms:
+    """min -prod_i x_i^alpha_i  s.t.  prices'x <= wealth (a linear row), x >= 1e-3, from an equal split of half the wealth.
+    With sum alpha <= 1 the utility is concave; optimum x_i = alpha_i wealth / (prices_i sum alpha)."""
+    alpha, prices = _f64(alpha), _f64(prices)
+    n = len(alpha)
+    terms = [(0, -1.0, [(j + 1, POWR, float(alpha[j])) for j in range(n)])]
+    terms += [(1, prices[j], [(j + 1, POW)]) for j in range(n)]
+    return make_nlp_terms(n, 1, 1, terms, xL=np.full(n, 1e-3), xU=np.full(n, wealth / prices.min()), gL=[-np.inf], gU=[float(wealth)],
+                          x0=0.5 * wealth / (n * prices))
+
+
+def logistic_model(X, y, reg) -> NlpTerms:
+    """Ridge-regularised logistic regression, labels y in {0, 1}: min sum_i [softplus(X_i'w) - y_i X_i'w] + reg / 2 |w|^2
+    over -50 <= w <= 50, no rows, from w = 0.  One SOFTPLUS factor of an affine form per point."""
+    X, y = np.atleast_2d(_f64(X)), _f64(y)
+    N, n = X.shape
+    terms = [(0, 1.0, [([(j + 1, X[i, j]) for j in range(n)], SOFTPLUS, 1, 0.0)]) for i in range(N)]
+    terms += [(0, -float(y @ X[:, j]), [(j + 1, POW)]) for j in range(n)]
+    terms += [(0, 0.5 * float(reg), [(j + 1, POW, 2)]) for j in range(n)]
+    return make_nlp_terms(n, 0, 0, terms, xL=np.full(n, -50.0), xU=np.full(n, 50.0), x0=np.zeros(n))
 
 
 def nlp_terms_scenario(p: NlpTerms, s: int, seed: int = 1, noise: float = 0.05) -> NlpTerms:
