@@ -408,7 +408,8 @@ int sqphip_nlp_attach(sqphip_ctx *ctx, int64_t nterms, const int64_t *trow /* 0:
  *     d2/dx_v dx_w = c a_v a_w kappa''_a prod_{k != a} kappa_k  (a = b, v = w included),
  * products in factor order, one thread per output entry summing in term order, no atomics (bit-reproducible,
  * independent of the slot).  A model with one argument per factor files the bits it files through sqphip_nlp_attach.
- * The structure, acoef included, is shared by the batch; an instance's values are f0 | g0 | c as above, so
+ * The structure, acoef included, is shared by the batch (sqphip_nlp_attach_data below hands shifts, coefficients and real
+ * exponents to the instance); an instance's values are f0 | g0 | c as above, so
  * sqphip_nlp_set_instance, sqphip_nlp_stream_begin / _set, sqphip_sqp_stream_* and everything sqphip_nlp_attach lists
  * work on such a context unchanged (it is an NLP context to every other entry point).
  * Domain is the caller's business, as above: LOG and negative powers need u > 0 at every point the solver visits.
@@ -452,6 +453,41 @@ int sqphip_nlp_attach_general(sqphip_ctx *ctx, int64_t nterms, const int64_t *tr
                               const int32_t *fkind, const int32_t *fexp,
                               const double *fpar /* [nfac] or NULL: real exponent, read for POWR only */,
                               const double *fshift /* [nfac] or NULL: zeros */, const double *g0 /* [m] or NULL */, double f0);
+/* The same model once more, with the data of the factors owned by the instance: shifts, coefficients and real exponents may
+ * differ between the instances of a batch and between the scenarios of a queue -- one dataset per instance of
+ * logistic_model-like fits (cross-validation folds, bootstrap resamples), measurements b_s in (a'x - b_s)^2 or
+ * exp(a'x - b_s), one vector of elasticities per consumer, a phase-shifter angle per contingency.  The arguments, the class
+ * of models, the checks, the messages and SQPHIP_ESTATE on a context attached before are those of sqphip_nlp_attach_general,
+ * and the result is an NLP context to every other entry point.  What stays shared is the structure proper: rows, terms,
+ * factors, arguments and their variables, kinds, integer exponents.
+ * An instance's block of doubles becomes
+ *     f0 | g0 [m] | c [nterms] | b [nfac] | a [nargs] | p [nfac]       (padded to an even count)
+ * with b = fshift, a = acoef in argument order and p = fpar; the p segment exists only when the model has a POWR factor.
+ * The call fills the data segments of every instance with the arrays given here (NULL acoef: ones, NULL fshift: zeros).
+ * sqphip_nlp_set_instance keeps writing f0 | g0 | c and leaves the data alone; sqphip_nlp_stream_set writes a whole block,
+ * the data of this call included.  The device reads b, a, p from the instance's block in pass 1 and the weights a_v of the
+ * derivative plans from its a segment (a one-argument factor keeps a folded into phi', phi'' and the weight 1.0); orders
+ * of summation, the absence of atomics and the factor workspace are unchanged.
+ * Bit rule: a context attached through this call whose instances all carry the data of the attach files, in all five
+ * callbacks and in sqphip_sqp_get, the bits of the same model attached through sqphip_nlp_attach_general, with equal work
+ * counters.  Contexts of the three other calls are untouched by the switch. */
+int sqphip_nlp_attach_data(sqphip_ctx *ctx, int64_t nterms, const int64_t *trow, const double *tcoef,
+                           const int64_t *tptr /* [nterms + 1] factors of a term */,
+                           const int64_t *aptr /* [nfac + 1] arguments of a factor */,
+                           const int64_t *avar /* [nargs] 1-based */, const double *acoef /* [nargs] or NULL: ones */,
+                           const int32_t *fkind, const int32_t *fexp,
+                           const double *fpar /* [nfac] or NULL: real exponent, read for POWR only */,
+                           const double *fshift /* [nfac] or NULL: zeros */, const double *g0 /* [m] or NULL */, double f0);
+/* The data of one instance of such a context: fshift [nfac], acoef [nargs], fpar [nfac] in the order of the attach; any
+ * pointer may be NULL: keep.  SQPHIP_EINVAL with a message in sqphip_last_error on a context without
+ * sqphip_nlp_attach_data (the message names that call), inst out of range, fpar on a model without a POWR factor, a real
+ * exponent of a POWR factor that is 0 or not finite (1-based term and factor named) and data that would leave the single
+ * factor of a term of rows 1..num_linear with a coefficient other than 1 or a shift other than 0 (term named).  A zero
+ * coefficient is allowed anywhere else: the structure, and with it every plan entry, stays.  Only the real exponents are
+ * checked for finiteness: a NaN or infinite coefficient or shift is taken as given, as the attach calls take it.  Domain
+ * stays the caller's business. */
+int sqphip_nlp_set_instance_data(sqphip_ctx *ctx, int32_t inst, const double *fshift, const double *acoef,
+                                 const double *fpar);
 /* Per-instance values (f0 one value, g0 [m], tcoef [nterms] in the term order of the attach) and the start x0 [n];
  * any pointer may be NULL: keep.  Bounds go through sqphip_set_bounds. */
 int sqphip_nlp_set_instance(sqphip_ctx *ctx, int32_t inst, const double *f0, const double *g0,
@@ -503,7 +539,7 @@ int sqphip_qcqp_stream_set(sqphip_ctx *ctx, int32_t scenario, const double *xL, 
                            const double *av, const double *qv, const double *x0);
 /* The queue of a factorable-NLP context (sqphip_nlp_attach): the same, for any sparse factorable NLP.  _run, _run_some,
  * _assign, _append, _release and _get above work on it unchanged; a slot loads a scenario by one streaming copy of its
- * block of values (f0 | g0 | c, padded to an even count: the layout of sqphip_nlp_set_instance) into the slot's own.
+ * block of values (f0 | g0 | c, after sqphip_nlp_attach_data | b | a | p, padded to an even count) into the slot's own.
  * tables for n_scenarios on an NLP context; keep_multipliers = 1 also allocates result tables for g, mult_g, mult_x_L,
  * mult_x_U.  SQPHIP_EINVAL on a context without sqphip_nlp_attach (unattached, ACOPF, dense, QCQP) and for
  * n_scenarios <= 0. */
@@ -516,6 +552,14 @@ int sqphip_nlp_stream_begin(sqphip_ctx *ctx, int32_t n_scenarios, int32_t keep_m
  * sqphip_nlp_stream_begin the call is refused too. */
 int sqphip_nlp_stream_set(sqphip_ctx *ctx, int32_t scenario, const double *xL, const double *xU, const double *gL,
                           const double *gU, const double *f0, const double *g0, const double *tcoef, const double *x0);
+/* The data of one scenario of the queue of a context of sqphip_nlp_attach_data: overlays the b | a | p segments of the
+ * scenario's block in the tables (the blocks there have the layout of that attach; every queue call works on the longer
+ * block unchanged).  sqphip_nlp_stream_set writes the whole block, data of the attach included, so the order is
+ * sqphip_nlp_stream_set, then this call; a later sqphip_nlp_stream_set restores the attach's data.  NULL: keep.  Refused
+ * with SQPHIP_EINVAL and a message on a context without sqphip_nlp_attach_data, before sqphip_nlp_stream_begin, for a
+ * scenario outside the queue and for the values sqphip_nlp_set_instance_data refuses. */
+int sqphip_nlp_stream_set_data(sqphip_ctx *ctx, int32_t scenario, const double *fshift, const double *acoef,
+                               const double *fpar);
 /* everything sqphip_sqp_get returns, for a scenario of a queue begun with keep_multipliers = 1 (same signs as
  * sqphip_sqp_get: mult_g = -lambda, mult_x_U negated; any pointer may be NULL): the slot files them with the final
  * point before it draws its next scenario.  SQPHIP_ESTATE when the tables were not asked for (sqphip_qcqp_stream_begin

@@ -255,6 +255,24 @@ hip_nlp_attach_general(ctx::Ptr{Cvoid}, trow::Vector{Int64}, tcoef::Vector{Float
                       (Ptr{Cvoid}, Int64, Ptr{Int64}, Ptr{Cdouble}, Ptr{Int64}, Ptr{Int64}, Ptr{Int64}, Ptr{Cdouble}, Ptr{Int32},
                        Ptr{Int32}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Cdouble),
                       ctx, length(trow), trow, tcoef, tptr, aptr, avar, acoef, fkind, fexp, _vals(fpar), fshift, g0, f0))
+# ... with shifts, coefficients and real exponents owned by the instance (sqphip_nlp_attach_data): the arguments of
+# hip_nlp_attach_general; they start every instance, hip_nlp_set_instance_data replaces those of one instance (`nothing`:
+# keep) and hip_nlp_stream_set_data, after hip_nlp_stream_set, those of one scenario of the queue (inst and s are 0-based)
+hip_nlp_attach_data(ctx::Ptr{Cvoid}, trow::Vector{Int64}, tcoef::Vector{Float64}, tptr::Vector{Int64}, aptr::Vector{Int64},
+                    avar::Vector{Int64}, acoef::Vector{Float64}, fkind::Vector{Int32}, fexp::Vector{Int32},
+                    fpar::Union{Nothing, Vector{Float64}}, fshift::Vector{Float64}, g0::Vector{Float64}, f0::Real) =
+    _check(ctx, ccall((:sqphip_nlp_attach_data, LIBSQPHIP), Cint,
+                      (Ptr{Cvoid}, Int64, Ptr{Int64}, Ptr{Cdouble}, Ptr{Int64}, Ptr{Int64}, Ptr{Int64}, Ptr{Cdouble}, Ptr{Int32},
+                       Ptr{Int32}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Cdouble),
+                      ctx, length(trow), trow, tcoef, tptr, aptr, avar, acoef, fkind, fexp, _vals(fpar), fshift, g0, f0))
+hip_nlp_set_instance_data(ctx::Ptr{Cvoid}, inst::Integer; fshift = nothing, acoef = nothing, fpar = nothing) =
+    _check(ctx, ccall((:sqphip_nlp_set_instance_data, LIBSQPHIP), Cint,
+                      (Ptr{Cvoid}, Int32, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}),
+                      ctx, inst, _vals(fshift), _vals(acoef), _vals(fpar)))
+hip_nlp_stream_set_data(ctx::Ptr{Cvoid}, s::Integer; fshift = nothing, acoef = nothing, fpar = nothing) =
+    _check(ctx, ccall((:sqphip_nlp_stream_set_data, LIBSQPHIP), Cint,
+                      (Ptr{Cvoid}, Int32, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}),
+                      ctx, s, _vals(fshift), _vals(acoef), _vals(fpar)))
 hip_nlp_set_instance(ctx::Ptr{Cvoid}, inst::Integer; f0 = nothing, g0 = nothing, tcoef = nothing, x0 = nothing) =
     _check(ctx, ccall((:sqphip_nlp_set_instance, LIBSQPHIP), Cint,
                       (Ptr{Cvoid}, Int32, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}),

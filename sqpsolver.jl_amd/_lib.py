@@ -202,6 +202,10 @@ def lib():
                 L.sqphip_nlp_attach_affine.argtypes = [vp, C.c_int64, lp, dp, lp, lp, lp, dp, ip, ip, dp, dp, C.c_double]
             if not os.environ.get("SQPHIP_SO") or hasattr(L, "sqphip_nlp_attach_general"):   # (an older build given through SQPHIP_SO lacks shared variables and the wider menu)
                 L.sqphip_nlp_attach_general.argtypes = [vp, C.c_int64, lp, dp, lp, lp, lp, dp, ip, ip, dp, dp, dp, C.c_double]
+            if not os.environ.get("SQPHIP_SO") or hasattr(L, "sqphip_nlp_attach_data"):   # (an older build given through SQPHIP_SO lacks per-instance data)
+                L.sqphip_nlp_attach_data.argtypes = [vp, C.c_int64, lp, dp, lp, lp, lp, dp, ip, ip, dp, dp, dp, C.c_double]
+                L.sqphip_nlp_set_instance_data.argtypes = [vp, C.c_int32, dp, dp, dp]
+                L.sqphip_nlp_stream_set_data.argtypes = [vp, C.c_int32, dp, dp, dp]
             L.sqphip_acopf_set_shunts.argtypes = [vp, C.c_int32, ip, dp, dp]
             L.sqphip_acopf_set_dclines.argtypes = [vp, C.c_int32, dp]
             L.sqphip_kkt_order.argtypes = [C.c_int64, C.c_int64, C.c_int64, lp, lp, C.c_int64, lp, lp, dp, dp, C.c_int32,
@@ -270,9 +274,9 @@ EXPORTS = [
     "sqphip_kt_residuals", "sqphip_norm_complementarity", "sqphip_compute_phi",
     "sqphip_compute_qmodel", "sqphip_compute_derivative", "sqphip_compute_derivative_full", "sqphip_compute_mu_rule_dev",
     "sqphip_acopf_armijo", "sqphip_tr_update",
-    "sqphip_kkt_order", "sqphip_kkt_symbolic", "sqphip_mf_host_solve", "sqphip_mf_host_top2_err", "sqphip_mf_host_spine_err", "sqphip_mf_solve_test", "sqphip_mf_batch_test", "sqphip_mf_values_test", "sqphip_mf_values_blocks", "sqphip_mf_census", "sqphip_trans_inline_groups", "sqphip_mf_plan_info", "sqphip_mf_front_launches", "sqphip_acopf_attach", "sqphip_acopf_attach_acr", "sqphip_acopf_attach_acwr", "sqphip_acopf_set_shunts", "sqphip_acopf_set_dclines", "sqphip_acopf_set_instance", "sqphip_dense_attach", "sqphip_dense_set_instance", "sqphip_qcqp_attach", "sqphip_qcqp_set_instance", "sqphip_nlp_attach", "sqphip_nlp_attach_affine", "sqphip_nlp_attach_general", "sqphip_nlp_set_instance", "sqphip_acopf_eval", "sqphip_sqp_reset",
+    "sqphip_kkt_order", "sqphip_kkt_symbolic", "sqphip_mf_host_solve", "sqphip_mf_host_top2_err", "sqphip_mf_host_spine_err", "sqphip_mf_solve_test", "sqphip_mf_batch_test", "sqphip_mf_values_test", "sqphip_mf_values_blocks", "sqphip_mf_census", "sqphip_trans_inline_groups", "sqphip_mf_plan_info", "sqphip_mf_front_launches", "sqphip_acopf_attach", "sqphip_acopf_attach_acr", "sqphip_acopf_attach_acwr", "sqphip_acopf_set_shunts", "sqphip_acopf_set_dclines", "sqphip_acopf_set_instance", "sqphip_dense_attach", "sqphip_dense_set_instance", "sqphip_qcqp_attach", "sqphip_qcqp_set_instance", "sqphip_nlp_attach", "sqphip_nlp_attach_affine", "sqphip_nlp_attach_general", "sqphip_nlp_attach_data", "sqphip_nlp_set_instance", "sqphip_nlp_set_instance_data", "sqphip_acopf_eval", "sqphip_sqp_reset",
     "sqphip_sqp_run", "sqphip_sqp_get", "sqphip_sqp_status", "sqphip_sqp_trace",
     "sqphip_comm_available", "sqphip_comm_unique_id", "sqphip_comm_init", "sqphip_gather_status", "sqphip_comm_destroy",
-    "sqphip_get_counters", "sqphip_get_mode_counters", "sqphip_sqp_work", "sqphip_sqp_stream_begin", "sqphip_sqp_stream_set", "sqphip_sqp_stream_run", "sqphip_sqp_stream_get", "sqphip_sqp_stream_assign", "sqphip_sqp_stream_append", "sqphip_sqp_stream_release", "sqphip_sqp_stream_run_some", "sqphip_qcqp_stream_begin", "sqphip_qcqp_stream_set", "sqphip_nlp_stream_begin", "sqphip_nlp_stream_set", "sqphip_sqp_stream_get_full", "sqphip_sqp_last_request", "sqphip_sqp_qp_log", "sqphip_reset_counters", "sqphip_set_timing", "sqphip_get_kernel_times", "sqphip_ldlt_factor_host",
+    "sqphip_get_counters", "sqphip_get_mode_counters", "sqphip_sqp_work", "sqphip_sqp_stream_begin", "sqphip_sqp_stream_set", "sqphip_sqp_stream_run", "sqphip_sqp_stream_get", "sqphip_sqp_stream_assign", "sqphip_sqp_stream_append", "sqphip_sqp_stream_release", "sqphip_sqp_stream_run_some", "sqphip_qcqp_stream_begin", "sqphip_qcqp_stream_set", "sqphip_nlp_stream_begin", "sqphip_nlp_stream_set", "sqphip_nlp_stream_set_data", "sqphip_sqp_stream_get_full", "sqphip_sqp_last_request", "sqphip_sqp_qp_log", "sqphip_reset_counters", "sqphip_set_timing", "sqphip_get_kernel_times", "sqphip_ldlt_factor_host",
     "sqphip_ldlt_solve_host", "sqphip_ldlt_bench", "sqphip_ldlt_stress", "sqphip_ldlt_tile_masks", "sqphip_ldlt_case_test", "sqphip_mfma_f64_peak", "sqphip_armijo_alpha", "sqphip_compute_mu_rule",
 ]

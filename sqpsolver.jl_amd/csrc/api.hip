@@ -1707,7 +1707,8 @@ static void plan_order(int owners, const std::vector<int> &own, std::vector<int>
 // plans; a factor of several arguments stores kappa', kappa'' and its arguments weigh a_v (nlp_dev.hpp).
 // general: sqphip_nlp_attach_general -- the menu up to POWR (fpar: its real exponents) and variables shared by the factors of
 // a term; the two older calls are this one with the menu check at LOG and the distinct-variables check switched on.
-static int nlp_attach_impl(sqphip_ctx *h, const char *who, bool affine, bool general, int64_t nterms, const int64_t *trow, const double *tcoef,
+// data: sqphip_nlp_attach_data -- the general call with b | a | p appended to every instance's block (nlp_dev.hpp NlpDev::data).
+static int nlp_attach_impl(sqphip_ctx *h, const char *who, bool affine, bool general, bool data, int64_t nterms, const int64_t *trow, const double *tcoef,
                            const int64_t *tptr, const int64_t *aptr, const int64_t *avar, const double *acoef, const int32_t *fkind,
                            const int32_t *fexp, const double *fpar, const double *fshift, const double *g0, double f0)
 {
@@ -1758,7 +1759,8 @@ static int nlp_attach_impl(sqphip_ctx *h, const char *who, bool affine, bool gen
     std::vector<double2> fab(fke.size(), double2{1.0, 0.0});
     std::vector<int> ap((size_t)nfac + 1, 0), av((size_t)std::max<int64_t>(nargs, 1), 0);
     std::vector<double> ac(av.size(), 1.0), aw(av.size(), 1.0), fpw(fke.size(), 0.0);
-    bool multi = false;
+    bool multi = false, powr = false;
+    std::vector<int> lin_terms;
     for (int64_t t = 0; t < nterms; ++t) {
         const int64_t i = trow[t], k0 = tptr[t], k1 = tptr[t + 1];
         if (i < 0 || i > m) return nlp_fail(h, who, t, -1, "row " + std::to_string(i) + " out of range (0: objective, 1.." + std::to_string(m) + ")");
@@ -1776,6 +1778,7 @@ static int nlp_attach_impl(sqphip_ctx *h, const char *who, bool affine, bool gen
                 if (!std::isfinite(fpar[k]) || fpar[k] == 0.0)
                     return nlp_fail(h, who, t, kf, "real exponent " + std::to_string(fpar[k]) + " (finite and not 0)");
                 fpw[k] = fpar[k];
+                powr = true;
             }
             const int e = fkind[k] == NLP_POW ? fexp[k] : 1;
             if (e == 0 || e > 32 || e < -32) return nlp_fail(h, who, t, kf, "exponent " + std::to_string(e) + " (1 <= |e| <= 32)");
@@ -1799,6 +1802,7 @@ static int nlp_attach_impl(sqphip_ctx *h, const char *who, bool affine, bool gen
                 av[j] = (int)avar[j] - 1; ac[j] = acoef ? acoef[j] : 1.0; aw[j] = one ? 1.0 : ac[j];
             }
         }
+        if (i >= 1 && i <= nlin) lin_terms.push_back((int)t);
         if (i == 0) ot.push_back((int)t); else { g_own.push_back((int)i - 1); g_t.push_back((int)t); }
         // a plan entry names an argument and, in the bits above 2^28, its factor within the term
         auto ent = [&](int64_t k, int64_t j) { return (int)(j | ((k - k0) << 28)); };
@@ -1846,12 +1850,20 @@ static int nlp_attach_impl(sqphip_ctx *h, const char *who, bool affine, bool gen
     const int hp = (int)ptr.size(); ptr.insert(ptr.end(), h_ptr.begin(), h_ptr.end());
     std::vector<int> tp((size_t)nterms + 1);
     for (int64_t t = 0; t <= nterms; ++t) tp[t] = (int)tptr[t];
-    // values of an instance: f0 | g0 | c, the stride padded to even: every block is 16-byte aligned, as the QCQP blocks are
-    const long nvals = 1 + (long)m + nterms, nv = (nvals + 1) & ~1L;
+    // values of an instance: f0 | g0 | c, the stride padded to even: every block is 16-byte aligned, as the QCQP blocks are;
+    // data: f0 | g0 | c | b [nfac] | a [nargs] | p [nfac, with a POWR factor only]
+    const long ob = 1 + (long)m + nterms, oa = ob + nfac, op = powr ? oa + nargs : -1;
+    const long nvals = data ? oa + nargs + (powr ? nfac : 0) : ob, nv = (nvals + 1) & ~1L;
+    if (nv > INT32_MAX) return fail("too many values per instance");
     std::vector<double> val0(nv, 0.0);
     val0[0] = f0;
     if (g0) std::copy(g0, g0 + m, val0.begin() + 1);
     if (nterms) std::copy(tcoef, tcoef + nterms, val0.begin() + 1 + m);
+    if (data) {
+        for (int64_t k = 0; k < nfac; ++k) val0[ob + k] = fab[k].y;
+        std::copy(ac.begin(), ac.begin() + nargs, val0.begin() + oa);
+        if (powr) std::copy(fpw.begin(), fpw.begin() + nfac, val0.begin() + op);
+    }
     const int nobj = (int)ot.size();
     if (ot.empty()) ot.push_back(0);
     return guarded(h, [&](Ctx &C) {
@@ -1863,6 +1875,7 @@ static int nlp_attach_impl(sqphip_ctx *h, const char *who, bool affine, bool gen
         P.ot = C.upload(ot); P.ge = C.upload(ge); P.fe = C.upload(fe); P.je = C.upload(je); P.he = C.upload(he);
         P.aptr = C.upload(ap); P.avar = C.upload(av); P.acoef = C.upload(ac); P.aw = C.upload(aw); P.multi = multi ? 1 : 0;
         P.fpar = C.upload(fpw);
+        P.data = data ? 1 : 0; P.ob = (int)ob; P.oa = (int)oa; P.op = (int)op;
         NlpDev *pd = (NlpDev *)C.dalloc<char>(sizeof(NlpDev));
         SQPHIP_HIP_OK(hipMemcpyAsync(pd, &P, sizeof(NlpDev), hipMemcpyHostToDevice, C.stream));
         std::vector<double> all((size_t)d.B * nv);
@@ -1872,6 +1885,8 @@ static int nlp_attach_impl(sqphip_ctx *h, const char *who, bool affine, bool gen
         d.nlp = pd;
         C.nl_nv = nv; C.nl_nfac = nfac; C.nl_nterms = nterms;
         C.h_nl_base = val0;                // (the instances' blocks are overwritten by sqphip_nlp_set_instance)
+        C.nl_data = data; C.nl_ob = ob; C.nl_oa = oa; C.nl_op = op; C.nl_nargs = nargs;
+        if (data) { C.h_nl_tptr = tp; C.h_nl_aptr = ap; C.h_nl_kind.assign(fkind, fkind + nfac); C.h_nl_lin = lin_terms; }
         SQPHIP_HIP_OK(hipStreamSynchronize(C.stream));
         C.acopf_attached = true;           // (the batched run! has its device callbacks)
         make_lanes(C);
@@ -1883,21 +1898,76 @@ extern "C" int sqphip_nlp_attach(sqphip_ctx *h, int64_t nterms, const int64_t *t
                                  const int64_t *fvar, const int32_t *fkind, const int32_t *fexp, const double *fscale,
                                  const double *fshift, const double *g0, double f0)
 {
-    return nlp_attach_impl(h, "sqphip_nlp_attach", false, false, nterms, trow, tcoef, tptr, nullptr, fvar, fscale, fkind, fexp, nullptr, fshift, g0, f0);
+    return nlp_attach_impl(h, "sqphip_nlp_attach", false, false, false, nterms, trow, tcoef, tptr, nullptr, fvar, fscale, fkind, fexp, nullptr, fshift, g0, f0);
 }
 
 extern "C" int sqphip_nlp_attach_affine(sqphip_ctx *h, int64_t nterms, const int64_t *trow, const double *tcoef, const int64_t *tptr,
                                         const int64_t *aptr, const int64_t *avar, const double *acoef, const int32_t *fkind,
                                         const int32_t *fexp, const double *fshift, const double *g0, double f0)
 {
-    return nlp_attach_impl(h, "sqphip_nlp_attach_affine", true, false, nterms, trow, tcoef, tptr, aptr, avar, acoef, fkind, fexp, nullptr, fshift, g0, f0);
+    return nlp_attach_impl(h, "sqphip_nlp_attach_affine", true, false, false, nterms, trow, tcoef, tptr, aptr, avar, acoef, fkind, fexp, nullptr, fshift, g0, f0);
 }
 
 extern "C" int sqphip_nlp_attach_general(sqphip_ctx *h, int64_t nterms, const int64_t *trow, const double *tcoef, const int64_t *tptr,
                                          const int64_t *aptr, const int64_t *avar, const double *acoef, const int32_t *fkind,
                                          const int32_t *fexp, const double *fpar, const double *fshift, const double *g0, double f0)
 {
-    return nlp_attach_impl(h, "sqphip_nlp_attach_general", true, true, nterms, trow, tcoef, tptr, aptr, avar, acoef, fkind, fexp, fpar, fshift, g0, f0);
+    return nlp_attach_impl(h, "sqphip_nlp_attach_general", true, true, false, nterms, trow, tcoef, tptr, aptr, avar, acoef, fkind, fexp, fpar, fshift, g0, f0);
+}
+
+extern "C" int sqphip_nlp_attach_data(sqphip_ctx *h, int64_t nterms, const int64_t *trow, const double *tcoef, const int64_t *tptr,
+                                      const int64_t *aptr, const int64_t *avar, const double *acoef, const int32_t *fkind,
+                                      const int32_t *fexp, const double *fpar, const double *fshift, const double *g0, double f0)
+{
+    return nlp_attach_impl(h, "sqphip_nlp_attach_data", true, true, true, nterms, trow, tcoef, tptr, aptr, avar, acoef, fkind, fexp, fpar, fshift, g0, f0);
+}
+
+// what sqphip_nlp_set_instance_data and sqphip_nlp_stream_set_data refuse of the data of one instance (NULL: kept, unchecked:
+// what an instance holds has passed these checks)
+static int nlp_data_check(sqphip_ctx *h, const char *who, const double *fshift, const double *acoef, const double *fpar)
+{
+    Ctx &C = h->c;
+    if (!C.d.nlp || !C.nl_data) {
+        C.err = std::string(who) + ": the data of this context is shared by the batch (attach with sqphip_nlp_attach_data)";
+        return SQPHIP_EINVAL;
+    }
+    if (fpar && C.nl_op < 0) { C.err = std::string(who) + ": fpar given, but the model has no POWR factor"; return SQPHIP_EINVAL; }
+    if (fpar)
+        for (long t = 0; t < C.nl_nterms; ++t)
+            for (int k = C.h_nl_tptr[t]; k < C.h_nl_tptr[t + 1]; ++k)
+                if (C.h_nl_kind[k] == NLP_POWR && (!std::isfinite(fpar[k]) || fpar[k] == 0.0))
+                    return nlp_fail(h, who, t, k - C.h_nl_tptr[t], "real exponent " + std::to_string(fpar[k]) + " (finite and not 0)");
+    for (int t : C.h_nl_lin) {
+        const int k = C.h_nl_tptr[t];              // (the attach made sure: one factor, one argument)
+        if ((acoef && acoef[C.h_nl_aptr[k]] != 1.0) || (fshift && fshift[k] != 0.0))
+            return nlp_fail(h, who, t, 0, "the term is in one of the num_linear = " + std::to_string(C.d.nlin) +
+                                          " linear rows: coefficient 1 and shift 0 only");
+    }
+    return SQPHIP_OK;
+}
+
+// ... and the upload of the parts given into the block v (of an instance or of a scenario of the queue)
+static void nlp_data_upload(Ctx &C, double *v, const double *fshift, const double *acoef, const double *fpar)
+{
+    h2d(C, v + C.nl_ob, fshift, (size_t)C.nl_nfac); h2d(C, v + C.nl_oa, acoef, (size_t)C.nl_nargs);
+    if (C.nl_op >= 0) h2d(C, v + C.nl_op, fpar, (size_t)C.nl_nfac);
+}
+
+extern "C" int sqphip_nlp_set_instance_data(sqphip_ctx *h, int32_t inst, const double *fshift, const double *acoef, const double *fpar)
+{
+    const char *who = "sqphip_nlp_set_instance_data";
+    if (!h) return SQPHIP_EINVAL;
+    if (int rc = nlp_data_check(h, who, nullptr, nullptr, nullptr)) return rc;
+    if (inst < 0 || inst >= h->c.d.B) {
+        h->c.err = std::string(who) + ": instance " + std::to_string(inst) + " is outside the batch of " + std::to_string(h->c.d.B);
+        return SQPHIP_EINVAL;
+    }
+    if (int rc = nlp_data_check(h, who, fshift, acoef, fpar)) return rc;
+    return guarded(h, [&](Ctx &C) {
+        nlp_data_upload(C, C.d.nlv + (size_t)inst * C.nl_nv, fshift, acoef, fpar);
+        SQPHIP_HIP_OK(hipStreamSynchronize(C.stream));
+        return SQPHIP_OK;
+    });
 }
 
 extern "C" int sqphip_nlp_set_instance(sqphip_ctx *h, int32_t inst, const double *f0, const double *g0, const double *tcoef,
@@ -2466,7 +2536,8 @@ extern "C" int sqphip_qcqp_stream_set(sqphip_ctx *h, int32_t scen, const double 
     return value_stream_upload(h, scen, xL, xU, gL, gU, x0, v);
 }
 
-// ---- the queue on a factorable-NLP context: the same tables, the block in the layout of DV::nlv (f0 | g0 | c, padded to even)
+// ---- the queue on a factorable-NLP context: the same tables, the block in the layout of DV::nlv (f0 | g0 | c, on a context
+// of sqphip_nlp_attach_data | b | a | p; padded to even)
 extern "C" int sqphip_nlp_stream_begin(sqphip_ctx *h, int32_t n_scenarios, int32_t keep_multipliers)
 {
     if (!h) return SQPHIP_EINVAL;
@@ -2489,6 +2560,24 @@ extern "C" int sqphip_nlp_stream_set(sqphip_ctx *h, int32_t scen, const double *
     if (g0) std::copy(g0, g0 + m, v.begin() + 1);
     if (tcoef) std::copy(tcoef, tcoef + h->c.nl_nterms, v.begin() + 1 + m);
     return value_stream_upload(h, scen, xL, xU, gL, gU, x0, v);
+}
+
+extern "C" int sqphip_nlp_stream_set_data(sqphip_ctx *h, int32_t scen, const double *fshift, const double *acoef, const double *fpar)
+{
+    const char *who = "sqphip_nlp_stream_set_data";
+    if (!h) return SQPHIP_EINVAL;
+    if (int rc = nlp_data_check(h, who, nullptr, nullptr, nullptr)) return rc;
+    if (!h->c.d.stream.val) { h->c.err = std::string(who) + ": no NLP queue (sqphip_nlp_stream_begin)"; return SQPHIP_EINVAL; }
+    if (scen < 0 || scen >= h->c.d.stream.M) {
+        h->c.err = std::string(who) + ": scenario " + std::to_string(scen) + " is outside the " + std::to_string(h->c.d.stream.M) + " of the queue";
+        return SQPHIP_EINVAL;
+    }
+    if (int rc = nlp_data_check(h, who, fshift, acoef, fpar)) return rc;
+    return guarded(h, [&](Ctx &C) {
+        nlp_data_upload(C, const_cast<double *>(C.d.stream.val) + (size_t)scen * C.nl_nv, fshift, acoef, fpar);
+        SQPHIP_HIP_OK(hipStreamSynchronize(C.stream));
+        return SQPHIP_OK;
+    });
 }
 
 extern "C" int sqphip_sqp_stream_get_full(sqphip_ctx *h, int32_t scen, double *x, double *g, double *mult_g, double *mult_x_L,

@@ -280,6 +280,12 @@ struct Ctx {
     std::vector<double> h_qc_base;              // ... the values given to sqphip_qcqp_attach (NULL parts of a queue scenario)
     long nl_nv = 0, nl_nfac = 0, nl_nterms = 0; // doubles per instance of an attached factorable NLP (DV::nlv: f0 | g0 | c, padded to even), its factors and terms
     std::vector<double> h_nl_base;              // ... the values given to sqphip_nlp_attach (NULL parts of a queue scenario)
+    // sqphip_nlp_attach_data: the block goes on with b [nfac] | a [nargs] | p [nfac, with a POWR factor only] at nl_ob, nl_oa,
+    // nl_op (-1: no p); what the value checks of sqphip_nlp_set_instance_data / _stream_set_data need of the structure
+    bool nl_data = false;
+    long nl_ob = 0, nl_oa = 0, nl_op = -1, nl_nargs = 0;
+    std::vector<int> h_nl_tptr, h_nl_aptr, h_nl_kind;   // [nterms + 1], [nfac + 1], [nfac]
+    std::vector<int> h_nl_lin;                          // the terms of rows 1..num_linear
     std::vector<double> h_xL, h_xU, h_gL, h_gU; // the bounds given to sqphip_create (NULL bounds of a queue scenario)
     bool acopf_attached = false;
     bool mf_big_lds = false;        // the multifrontal kernels were granted 160 KB of dynamic LDS on this context's device (mf_device_setup)

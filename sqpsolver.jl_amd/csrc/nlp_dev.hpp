@@ -27,6 +27,12 @@
 // and the sums above do the rest.  The six kinds sit behind one out-of-line function of scalars and the factor's place in
 // the workspace (nlp_kappa_wide, one call site per nlp_eval): inlined, tanh / atan / log1p / pow cost the kernels that
 // inline nlp_eval 120 - 130 B of scratch per lane each.
+// sqphip_nlp_attach_data: shifts, coefficients and real exponents belong to the instance.  Its block goes on after c with
+// b [nfac] | a [nargs] | p [nfac, only with a POWR factor] (NlpDev::ob, oa, op), and one switch, NlpDev::data, uniform over the
+// launch as multi is, makes pass 1 read them there instead of fab / acoef / fpar.  Pass 2 takes its weights from a as well:
+// the coefficient of an argument of a multi-argument factor, 1.0 for the argument of a one-argument factor (fvar >= 0),
+// whose a is folded into phi', phi'' as above.  The arithmetic is the same expression on other operands, so a data context
+// whose instances carry the attach's arrays files the bits of sqphip_nlp_attach_general; with the switch off no load moves.
 #pragma once
 #include "ctx.hpp"
 #include "dev_util.hpp"
@@ -59,6 +65,8 @@ struct NlpDev {
     const double *aw;                     // [nargs] its weight in the derivative plans: the coefficient, 1.0 in a one-argument factor
     int multi;                            // some factor has several arguments; 0: every weight is 1.0 and the plans do not load aw
     const double *fpar;                   // [nfac] real exponent of a POWR factor (loaded for that kind only)
+    int data;                             // sqphip_nlp_attach_data: b, a, p are the instance's, in its block of DV::nlv at ...
+    int ob, oa, op;                       // ... ob [nfac], oa [nargs], op [nfac] (op: with a POWR factor only); fab, acoef, aw, fpar unread
 };
 
 // pass 1 of a factor of the kinds SQRT .. POWR at u: kappa, a kappa', a^2 kappa'' to w[0], w[nf], w[2 nf] (nd: how many
@@ -102,6 +110,14 @@ static __device__ __forceinline__ double nlp_prod(const int *__restrict__ tptr, 
     #pragma unroll 1
     for (int k = k0; k < tptr[t + 1]; ++k) p *= w[((k == a) + (k == b)) * nf + k];
     return p;
+}
+
+// the weight of the argument named by the plan entry ey (argument + 2^28 its factor within term t); aw: NlpDev::aw, or the
+// a segment of the instance's block on a data context, where a one-argument factor keeps its weight 1.0
+static __device__ __forceinline__ double nlp_weight(const NlpDev &q, const double *__restrict__ aw, bool data, int t, int ey)
+{
+    if (data && q.fvar[q.tptr[t] + (ey >> 28)] >= 0) return 1.0;
+    return aw[ey & NLP_ARG];
 }
 
 // pass 1 for factor k at u = a x + b (pw: the exponent of a POWR factor)
@@ -154,20 +170,28 @@ static __device__ __forceinline__ void nlp_eval(const DV &d, int inst, const dou
     const double *__restrict__ cf = val + 1 + q.m;
     const int *__restrict__ tptr = q.tptr;
     const bool d1 = grad || jv || hv, d2 = hv != nullptr;     // phi'' is read by the Hessian plan only
-    const bool multi = q.multi != 0;
-    const double *__restrict__ aw = q.aw;
+    const bool multi = q.multi != 0, data = q.data != 0;
+    const double *__restrict__ aw = data ? val + q.oa : q.aw;
     __syncthreads();                        // x is complete; nobody still reads the workspace of an earlier evaluation
     #pragma unroll 1
     for (int k = threadIdx.x; k < nf; k += TPB) {
-        const double2 ab = q.fab[k];
         const int v = q.fvar[k], ke = q.fke[k];
-        const double pw = (ke & NLP_KIND_MASK) == NLP_POWR ? q.fpar[k] : 0.0;
+        double2 ab;
+        double pw = 0.0;
+        if (data) {
+            ab = double2{v >= 0 ? aw[q.aptr[k]] : 1.0, val[q.ob + k]};
+            if ((ke & NLP_KIND_MASK) == NLP_POWR) pw = val[q.op + k];
+        } else {
+            ab = q.fab[k];
+            if ((ke & NLP_KIND_MASK) == NLP_POWR) pw = q.fpar[k];
+        }
+        const double *__restrict__ ac = data ? aw : q.acoef;
         double a = 1.0, u;
         if (v >= 0) { a = ab.x; u = ab.x * x[v] + ab.y; }
         else {
             u = 0.0;
             #pragma unroll 1
-            for (int j = q.aptr[k]; j < q.aptr[k + 1]; ++j) u += q.acoef[j] * x[q.avar[j]];
+            for (int j = q.aptr[k]; j < q.aptr[k + 1]; ++j) u += ac[j] * x[q.avar[j]];
             u += ab.y;
         }
         nlp_factor(ke, a, u, pw, d1, d2, w, nf, k);
@@ -188,7 +212,7 @@ static __device__ __forceinline__ void nlp_eval(const DV &d, int inst, const dou
             #pragma unroll 1
             for (int k = ptr[j]; k < ptr[j + 1]; ++k) {
                 const int2 e = q.fe[k];
-                s += cf[e.x] * (nlp_prod(tptr, w, nf, e.x, e.y >> 28, NLP_NONE) * (multi ? aw[e.y & NLP_ARG] : 1.0));
+                s += cf[e.x] * (nlp_prod(tptr, w, nf, e.x, e.y >> 28, NLP_NONE) * (multi ? nlp_weight(q, aw, data, e.x, e.y) : 1.0));
             }
             grad[j] = s;
         }
@@ -209,7 +233,7 @@ static __device__ __forceinline__ void nlp_eval(const DV &d, int inst, const dou
             #pragma unroll 1
             for (int k = ptr[s_]; k < ptr[s_ + 1]; ++k) {
                 const int2 e = q.je[k];
-                s += cf[e.x] * (nlp_prod(tptr, w, nf, e.x, e.y >> 28, NLP_NONE) * (multi ? aw[e.y & NLP_ARG] : 1.0));
+                s += cf[e.x] * (nlp_prod(tptr, w, nf, e.x, e.y >> 28, NLP_NONE) * (multi ? nlp_weight(q, aw, data, e.x, e.y) : 1.0));
             }
             jv[s_] = s;
         }
@@ -222,7 +246,7 @@ static __device__ __forceinline__ void nlp_eval(const DV &d, int inst, const dou
             #pragma unroll 1
             for (int k = ptr[s_]; k < ptr[s_ + 1]; ++k) {
                 const int4 e = q.he[k];
-                s += cf[e.x] * (nlp_prod(tptr, w, nf, e.x, e.y >> 28, e.z >> 28) * (multi ? aw[e.y & NLP_ARG] * aw[e.z & NLP_ARG] : 1.0)) *
+                s += cf[e.x] * (nlp_prod(tptr, w, nf, e.x, e.y >> 28, e.z >> 28) * (multi ? nlp_weight(q, aw, data, e.x, e.y) * nlp_weight(q, aw, data, e.x, e.z) : 1.0)) *
                      (e.w < 0 ? sigma : lam[e.w]);
             }
             hv[s_] = s;

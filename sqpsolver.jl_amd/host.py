@@ -528,14 +528,22 @@ class Context:
         self._ck(self.L.sqphip_qcqp_set_instance(self.h, inst, *[_d(a) for a in arr], _d(_f(x0))))
 
     # ---- a sparse factorable NLP (nlp_terms.py; csrc/nlp_dev.hpp nlp_eval)
-    def nlp_attach(self, p, general=None):
+    def nlp_attach(self, p, general=None, instance_data=False):
         """Structure of the batch and the values every instance starts with; p: nlp_terms.NlpTerms.  A p with argument arrays
         (affine multi-variable factors) goes through sqphip_nlp_attach_affine, any other through sqphip_nlp_attach; a p
         made for more -- p.general, which make_nlp_terms sets for a variable shared by two factors of a term, a kind above
         LOG or a real exponent (nlp_terms.needs_general); fpar set -- through sqphip_nlp_attach_general.  A model of the
         older calls stays on them, so they refuse what they always refused.  general = True / False overrides the choice
-        (a model of the old class files the same bits through the new call)."""
+        (a model of the old class files the same bits through the new call).
+        instance_data = True goes through sqphip_nlp_attach_data: the class of the general call, with shifts, coefficients
+        and real exponents owned by the instance (the block f0 | g0 | c | b | a | p).  p's data starts every instance;
+        nlp_set_instance(inst, q) and nlp_stream_set(scen, q) then also send q's fshift, acoef and fpar, and q must have
+        p's structure."""
         from .nlp_terms import nlp_terms_args
+        if instance_data:
+            if not hasattr(self.L, "sqphip_nlp_attach_data"):
+                raise SqpHipError("libsqphip.so lacks sqphip_nlp_attach_data: rebuild it")
+            general = True
         if general is None:
             general = bool(getattr(p, "general", False)) or getattr(p, "fpar", None) is not None
         if general:
@@ -546,8 +554,11 @@ class Context:
             k = [np.ascontiguousarray(a, dtype=np.int32) for a in (p.fkind, p.fexp)]
             v = [_f(a) for a in (p.tcoef, acoef, p.fshift, p.g0)]
             par = None if getattr(p, "fpar", None) is None else _f(p.fpar)
-            self._ck(self.L.sqphip_nlp_attach_general(self.h, len(t[0]), _l(t[0]), _d(v[0]), _l(t[1]), _l(t[2]), _l(t[3]), _d(v[1]),
-                                                      _i(k[0]), _i(k[1]), _d(par), _d(v[2]), _d(v[3]), float(p.f0)))
+            fn = self.L.sqphip_nlp_attach_data if instance_data else self.L.sqphip_nlp_attach_general
+            self._ck(fn(self.h, len(t[0]), _l(t[0]), _d(v[0]), _l(t[1]), _l(t[2]), _l(t[3]), _d(v[1]),
+                        _i(k[0]), _i(k[1]), _d(par), _d(v[2]), _d(v[3]), float(p.f0)))
+            if instance_data:
+                self._nlp_structure = self._nlp_structure_of(p)
             return
         if getattr(p, "aptr", None) is not None:
             t = [np.ascontiguousarray(a, dtype=np.int64) for a in (p.trow, p.tptr, p.aptr, p.avar)]
@@ -562,9 +573,39 @@ class Context:
         self._ck(self.L.sqphip_nlp_attach(self.h, len(t[0]), _l(t[0]), _d(v[0]), _l(t[1]), _l(t[2]), _i(k[0]), _i(k[1]),
                                           _d(v[1]), _d(v[2]), _d(v[3]), float(p.f0)))
 
+    _NLP_DATA = ("fshift", "acoef", "fpar")
+
+    @staticmethod
+    def _nlp_structure_of(p):
+        """what the instances of a context of nlp_attach(instance_data=True) share: trow, tptr, aptr, avar, fkind, fexp"""
+        from .nlp_terms import nlp_terms_args
+        aptr, avar, _ = nlp_terms_args(p)
+        return [np.asarray(a).astype(np.int64) for a in (p.trow, p.tptr, aptr, avar, p.fkind, p.fexp)]
+
+    def _nlp_data_of(self, who, p, values):
+        """(values without the data keywords, [fshift, acoef, fpar] or None): the data parts of p and of the keywords on a
+        context of nlp_attach(instance_data=True); the keywords are refused on any other context."""
+        from .nlp_terms import nlp_terms_args
+        struct = getattr(self, "_nlp_structure", None)
+        data = {k: values.pop(k) for k in self._NLP_DATA if k in values}
+        if struct is None:
+            if data:
+                raise TypeError(f"{who}: {sorted(data)} need a context of nlp_attach(instance_data=True)")
+            return values, None
+        if p is not None:
+            mine = self._nlp_structure_of(p)
+            for name, a, b in zip(("trow", "tptr", "aptr", "avar", "fkind", "fexp"), struct, mine):
+                if a.shape != b.shape or not np.array_equal(a, b):
+                    raise SqpHipError(f"{who}: the structure of the model ({name}) differs from the attached one")
+            data = {"fshift": p.fshift, "acoef": nlp_terms_args(p)[2], "fpar": getattr(p, "fpar", None), **data}
+        return values, [None if data.get(k) is None else _f(np.atleast_1d(data[k])) for k in self._NLP_DATA]
+
     def nlp_set_instance(self, inst, p=None, x0=None, **values):
         """Per-instance values (sqphip_nlp_set_instance).  With an NlpTerms p: its bounds, every value and its start; keywords
-        f0, g0, tcoef override single parts, and what is given neither way is kept."""
+        f0, g0, tcoef override single parts, and what is given neither way is kept.  On a context of
+        nlp_attach(instance_data=True) p's fshift, acoef and fpar go along (sqphip_nlp_set_instance_data; p must have the
+        attached structure) and the keywords fshift, acoef, fpar override single parts."""
+        values, data = self._nlp_data_of("nlp_set_instance", p, dict(values))
         if p is not None:
             self.set_bounds(inst, p)
             values = {**{k: getattr(p, k) for k in ("f0", "g0", "tcoef")}, **values}
@@ -574,6 +615,8 @@ class Context:
             raise TypeError(f"nlp_set_instance: unknown values {sorted(bad)}")
         arr = [None if values.get(k) is None else _f(np.atleast_1d(values[k])) for k in ("f0", "g0", "tcoef")]
         self._ck(self.L.sqphip_nlp_set_instance(self.h, inst, *[_d(a) for a in arr], _d(_f(x0))))
+        if data is not None and any(a is not None for a in data):
+            self._ck(self.L.sqphip_nlp_set_instance_data(self.h, inst, *[_d(a) for a in data]))
 
     def acopf_eval(self, inst, x, sigma=1.0, lam=None):
         f = C.c_double(); grad = np.zeros(self.n); g = np.zeros(self.m)
@@ -752,8 +795,12 @@ class Context:
     def nlp_stream_set(self, scen, p=None, x0=None, **values):
         """One scenario (sqphip_nlp_stream_set), with the conventions of qcqp_stream_set.  With an NlpTerms p: its bounds, every
         value and its start; keywords f0, g0, tcoef override single parts and xL, xU, gL, gU single bounds.  A value given
-        neither way is the one of nlp_attach, a bound given neither way the one the context was created with."""
+        neither way is the one of nlp_attach, a bound given neither way the one the context was created with.  On a context of
+        nlp_attach(instance_data=True) p's fshift, acoef and fpar follow through sqphip_nlp_stream_set_data (p must have the
+        attached structure); the keywords fshift, acoef, fpar override single parts, and a part given neither way is the
+        attach's."""
         names, bnames = ("f0", "g0", "tcoef"), ("xL", "xU", "gL", "gU")
+        values, data = self._nlp_data_of("nlp_stream_set", p, dict(values))
         if p is not None:
             values = {**{k: getattr(p, k) for k in names + bnames}, **values}
             x0 = p.x0 if x0 is None else x0
@@ -762,6 +809,8 @@ class Context:
             raise TypeError(f"nlp_stream_set: unknown values {sorted(bad)}")
         arr = [None if values.get(k) is None else _f(np.atleast_1d(values[k])) for k in bnames + names]
         self._ck(self.L.sqphip_nlp_stream_set(self.h, int(scen), *[_d(a) for a in arr], _d(_f(x0))))
+        if data is not None and any(a is not None for a in data):
+            self._ck(self.L.sqphip_nlp_stream_set_data(self.h, int(scen), *[_d(a) for a in data]))
 
     def stream_get_full(self, scen):
         """The dict of sqp_get for a scenario of a queue begun with keep_multipliers (sqphip_sqp_stream_get_full)."""

@@ -32,6 +32,9 @@ plain affine factors.  Twice inside one factor stays an error.  SQRT and POWR ne
     needs_general        whether a problem is outside what sqphip_nlp_attach / _affine take (make_nlp_terms records it in
                          NlpTerms.general, and Context.nlp_attach goes by that record)
     nlp_terms_scenario   scenario s of a problem: the same structure, other coefficients, the same feasible start
+    nlp_data_scenario    ... other shifts, argument coefficients and real exponents (sqphip_nlp_attach_data: the data of the
+                         factors belongs to the instance), the same feasible start
+    logistic_folds       the k training folds of a dataset as k logistic models of one structure
     from_qcqp            a Qcqp (qcqp.py) restated as terms
     from_polar_acopf     the polar ACOPF of acopf_layout restated as terms, on that layout's COO structures
 
@@ -414,7 +417,9 @@ def entropy_model(c) -> NlpTerms:
 
 def cobb_douglas_model(alpha, prices, wealth) -> NlpTerms:
     """min -prod_i x_i^alpha_i  s.t.  prices'x <= wealth (a linear row), x >= 1e-3, from an equal split of half the wealth.
-    With sum alpha <= 1 the utility is concave; optimum x_i = alpha_i wealth / (prices_i sum alpha)."""
+    With sum alpha <= 1 the utility is concave; optimum x_i = alpha_i wealth / (prices_i sum alpha).
+    The structure depends on len(alpha) only -- alpha sits in fpar, the prices in tcoef, the wealth in gU --, so consumers
+    with different elasticities are instances of one context of Context.nlp_attach(p, instance_data=True)."""
     alpha, prices = _f64(alpha), _f64(prices)
     n = len(alpha)
     terms = [(0, -1.0, [(j + 1, POWR, float(alpha[j])) for j in range(n)])]
@@ -442,6 +447,75 @@ def nlp_terms_scenario(p: NlpTerms, s: int, seed: int = 1, noise: float = 0.05) 
         return p
     rng = np.random.default_rng(seed * 1000 + s)
     out = dataclasses.replace(p, tcoef=p.tcoef * (1.0 + noise * rng.standard_normal(len(p.tcoef))), f0=p.f0 + 0.1 * s)
+    out.g0 = p.g0 + (nlp_terms_rows(p, p.x0) - nlp_terms_rows(out, p.x0))
+    return out
+
+
+def logistic_fold_indices(N: int, k: int):
+    """[(training rows, validation rows)] of the k folds of N points: fold f validates on rows f * (N // k) .. and trains on
+    the other (k - 1) * (N // k) of the first k * (N // k) rows; the remainder N % k is dropped."""
+    sz = int(N) // int(k)
+    assert k >= 2 and sz >= 1
+    used = np.arange(k * sz)
+    return [(np.concatenate([used[:f * sz], used[(f + 1) * sz:]]), used[f * sz:(f + 1) * sz]) for f in range(k)]
+
+
+def logistic_folds(X, y, reg, k: int) -> list:
+    """logistic_model on each of the k training folds of (X, y) (logistic_fold_indices: equal sizes, the remainder dropped).
+    The k models have one structure -- a fold differs in acoef (its rows of X) and in the coefficients of its linear terms
+    -- so they are the instances of one context of Context.nlp_attach(folds[0], instance_data=True)."""
+    X, y = np.atleast_2d(_f64(X)), _f64(y)
+    return [logistic_model(X[tr], y[tr], reg) for tr, _ in logistic_fold_indices(len(y), k)]
+
+
+def _needs_positive(p: NlpTerms) -> np.ndarray:
+    return np.isin(p.fkind, _POSITIVE) | ((p.fkind == POW) & (p.fexp < 0))
+
+
+def nlp_data_scenario(p: NlpTerms, s: int, seed: int = 1, noise: float = 0.05) -> NlpTerms:
+    """Scenario s of p (s = 0: p itself) in the data of its factors: every argument coefficient scaled by 1 + noise z, every
+    shift moved by noise z, every real exponent scaled by max(1 + noise z, 0.1), z standard normal cut at +-2; the terms'
+    coefficients stay (nlp_terms_scenario moves those).  The single factors of the terms of rows 1..num_linear stay as
+    they are.  g0 moves so that every row keeps its value at x0: the bounds and the feasibility of x0 stay.
+    A factor that needs a positive argument (LOG, SQRT, POWR, a negative power) gets its perturbation shrunk, coefficients
+    and shift together, until the argument at x0 -- and its minimum over the box [xL, xU] where that was positive in p --
+    keeps at least half of what it was in p.  The structure (trow, tptr, aptr, avar, fkind, fexp) is p's."""
+    if s == 0:
+        return p
+    rng = np.random.default_rng([int(seed), int(s), 77])
+    aptr, avar, acoef = nlp_terms_args(p)
+    nfac = len(p.fkind)
+    fa = np.repeat(np.arange(nfac, dtype=np.int64), np.diff(aptr))          # factor of an argument
+    z = lambda k: np.clip(rng.standard_normal(k), -2.0, 2.0)
+    da, db = acoef * noise * z(len(acoef)), noise * z(nfac)
+    fixed = np.isin(p.trow[_term_of_factor(p)], np.arange(1, p.num_linear + 1))
+    da[fixed[fa]] = 0.0; db[fixed] = 0.0
+
+    def at(x, a, b):
+        return np.bincount(fa, a * x[avar - 1], nfac) + b
+
+    def box_min(a, b):
+        with np.errstate(invalid="ignore"):
+            lo = np.where(a >= 0, a * p.xL[avar - 1], a * p.xU[avar - 1])
+        return np.bincount(fa, np.where(a == 0, 0.0, lo), nfac) + b
+
+    theta = np.ones(nfac)
+    pos = _needs_positive(p)
+    for u0, u1 in ((at(p.x0, acoef, p.fshift), at(p.x0, acoef + da, p.fshift + db)),
+                   (box_min(acoef, p.fshift), box_min(acoef + da, p.fshift + db))):
+        # the margin is concave in theta: at theta it keeps at least (1 - theta) u0 + theta u1
+        k = pos & np.isfinite(u0) & (u0 > 0) & ~(u1 >= 0.5 * u0)
+        with np.errstate(all="ignore"):
+            theta[k] = np.minimum(theta[k], np.where(np.isfinite(u1[k]), 0.5 * u0[k] / (u0[k] - u1[k]), 0.0))
+    a1, b1 = acoef + theta[fa] * da, p.fshift + theta * db
+    out = dataclasses.replace(p, fshift=b1)
+    if p.aptr is None:
+        out.fscale = a1
+    else:
+        out.acoef = a1
+        out.fscale = np.where(np.diff(aptr) > 0, a1[np.minimum(aptr[:-1], len(a1) - 1)], p.fscale) if len(a1) else p.fscale.copy()
+    if p.fpar is not None:
+        out.fpar = np.where(p.fkind == POWR, p.fpar * np.maximum(1.0 + noise * z(nfac), 0.1), p.fpar)
     out.g0 = p.g0 + (nlp_terms_rows(p, p.x0) - nlp_terms_rows(out, p.x0))
     return out
 
