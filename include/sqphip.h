@@ -488,6 +488,42 @@ int sqphip_nlp_attach_data(sqphip_ctx *ctx, int64_t nterms, const int64_t *trow,
  * stays the caller's business. */
 int sqphip_nlp_set_instance_data(sqphip_ctx *ctx, int32_t inst, const double *fshift, const double *acoef,
                                  const double *fpar);
+/* Dense data blocks of the objective of an NLP context: block k adds
+ *     sum_{i < N} W[i] kappa(sum_{j < d} A[i][j] x_{cols[j]} + S[i])
+ * to row 0, kappa of the menu of sqphip_nlp_attach_general (kind 0..10; exp for POW, par for POWR), A a dense row-major
+ * N x d design matrix.  A, cols and the kind are shared by the batch; the weights W and shifts S belong to the instance
+ * (folds: 0 / 1 weights, bootstrap resamples: integer weights, measurements: shifts).  Limits: 1 <= d <= 128 distinct
+ * 1-based columns in any order, N >= 1, N d < 2^31, at most 4 blocks per context; a plain linear block (POW, e = 1) is
+ * refused -- that is what terms are for.  Domain (LOG, SQRT, POWR, negative powers) is the caller's business.
+ * Valid after any sqphip_nlp_attach* call and before the first sqphip_sqp_reset, sqphip_sqp_run or
+ * sqphip_nlp_stream_begin of the context (SQPHIP_ESTATE after).  The call re-lays the instances' blocks of doubles and keeps
+ * what they hold,
+ *     f0 | g0 | c | [b | a | p] | W_0 [N_0] | S_0 [N_0] | W_1 | S_1 | ...        (padded to an even count)
+ * fills W and S of every instance with weight and shift, uploads A once and maps every lower entry (r, c) of the block's
+ * d x d Hessian to its COO slot (the first COO copy of an entry owns it, as for the plans).  Unless nnzH = 0 the Hessian
+ * COO of sqphip_create must hold the lower entry of every pair of block columns, the diagonal included.
+ * SQPHIP_EINVAL, with sqphip_last_error naming the block and the 1-based column or entry: a context without an NLP attach,
+ * d outside 1..128, N < 1 or N d too large, a fifth block, a column out of range or twice, an unknown kind, POW with
+ * e = 1, e = 0 or |e| > 32, POWR with par zero or not finite, a missing Hessian entry.
+ * Evaluation, per block in block order, behind the plan passes of the terms (one workgroup per instance):
+ *   points    u_i = 0, u_i = fma(A[i][j], x_cols[j], u_i) for j = 0 .. d - 1, u_i += S[i] (the rule of
+ *             sqphip_nlp_attach_affine), then kappa, kappa', kappa'' by the code of the factors;
+ *   f         thread t sums W[i] kappa_i over i = t, t + 1024, ..., a wave adds its 64 sums by the xor butterfly
+ *             32, 16, .. 1, thread 0 adds the 16 wave sums in wave order, and the result is added to f;
+ *   gradient  column j: lane l of its wave sums (W[i] kappa'_i) A[i][j] over i = l, l + 64, ..., the same butterfly, added
+ *             to grad[cols[j]];
+ *   Hessian   A' diag(W kappa'') A by lower 16 x 16 tiles on v_mfma_f64_16x16x4_f64, four points per instruction in
+ *             rising order, operands (W[i] kappa''_i) A[i][r] (one rounding) and A[i][c], ragged edges as zeros; sigma
+ *             times the entry is added to its COO slot by one thread.
+ * No atomics: results are bit-reproducible and independent of slot, neighbours and instance groups.  They are not the
+ * bits of the same model written as one term per point (the sums run in another order).  Every other entry point sees
+ * an NLP context as before, and a context without a block files the bits it filed before this call existed. */
+int sqphip_nlp_add_block(sqphip_ctx *ctx, int32_t kind, int32_t exp, double par, int64_t N, int32_t d,
+                         const int64_t *cols /* [d] 1-based */, const double *A /* [N][d] row-major */,
+                         const double *shift /* [N] or NULL: zeros */, const double *weight /* [N] or NULL: ones */,
+                         int32_t *blk_out /* 0-based block number, or NULL */);
+/* weight [N], shift [N] of block blk of one instance; NULL: keep.  SQPHIP_EINVAL for inst or blk out of range. */
+int sqphip_nlp_set_instance_block(sqphip_ctx *ctx, int32_t inst, int32_t blk, const double *weight, const double *shift);
 /* Per-instance values (f0 one value, g0 [m], tcoef [nterms] in the term order of the attach) and the start x0 [n];
  * any pointer may be NULL: keep.  Bounds go through sqphip_set_bounds. */
 int sqphip_nlp_set_instance(sqphip_ctx *ctx, int32_t inst, const double *f0, const double *g0,
@@ -560,6 +596,11 @@ int sqphip_nlp_stream_set(sqphip_ctx *ctx, int32_t scenario, const double *xL, c
  * scenario outside the queue and for the values sqphip_nlp_set_instance_data refuses. */
 int sqphip_nlp_stream_set_data(sqphip_ctx *ctx, int32_t scenario, const double *fshift, const double *acoef,
                                const double *fpar);
+/* weight / shift of block blk of one scenario of the queue (sqphip_nlp_add_block): overlays the table entry.
+ * sqphip_nlp_stream_set writes the whole block with the add-call's weights and shifts, so the order is
+ * sqphip_nlp_stream_set, then this call; a later sqphip_nlp_stream_set restores the add-call's.  NULL: keep.  SQPHIP_EINVAL
+ * before sqphip_nlp_stream_begin, for a scenario outside the queue and for a blk the context does not have. */
+int sqphip_nlp_stream_set_block(sqphip_ctx *ctx, int32_t scenario, int32_t blk, const double *weight, const double *shift);
 /* everything sqphip_sqp_get returns, for a scenario of a queue begun with keep_multipliers = 1 (same signs as
  * sqphip_sqp_get: mult_g = -lambda, mult_x_U negated; any pointer may be NULL): the slot files them with the final
  * point before it draws its next scenario.  SQPHIP_ESTATE when the tables were not asked for (sqphip_qcqp_stream_begin

@@ -145,7 +145,7 @@ void make_lanes(Ctx &C)
         L->trans_period = C.trans_period; L->trans_ride = C.trans_ride; L->refine_slot = C.refine_slot; L->refine_period = C.refine_period; L->mf_big_lds = C.mf_big_lds; L->post_split = C.post_split; L->side_mode = C.side_mode; L->spec_tail = C.spec_tail; L->spec_mode0 = C.spec_mode0;
         L->d = group_view(C.d, lo, hi - lo, g);
         if (L->d.qcv) L->d.qcv += (long)lo * C.qc_nv;
-        if (L->d.nlv) { L->d.nlv += (long)lo * C.nl_nv; L->d.nlw += (long)lo * 3 * C.nl_nfac; }
+        if (L->d.nlv) { L->d.nlv += (long)lo * C.nl_nv; L->d.nlw += (long)lo * C.nl_ws; }
         // the first group runs on the owner's stream (idle during sqphip_sqp_run): HIP maps streams onto four hardware
         // queues by default, and a fifth stream would share one -- measured: 3131 QP/s with five streams against 5216
         // with four (or with GPU_MAX_HW_QUEUES=8)
@@ -1876,6 +1876,7 @@ static int nlp_attach_impl(sqphip_ctx *h, const char *who, bool affine, bool gen
         P.aptr = C.upload(ap); P.avar = C.upload(av); P.acoef = C.upload(ac); P.aw = C.upload(aw); P.multi = multi ? 1 : 0;
         P.fpar = C.upload(fpw);
         P.data = data ? 1 : 0; P.ob = (int)ob; P.oa = (int)oa; P.op = (int)op;
+        P.ws = 3 * (int)nfac;
         NlpDev *pd = (NlpDev *)C.dalloc<char>(sizeof(NlpDev));
         SQPHIP_HIP_OK(hipMemcpyAsync(pd, &P, sizeof(NlpDev), hipMemcpyHostToDevice, C.stream));
         std::vector<double> all((size_t)d.B * nv);
@@ -1884,6 +1885,7 @@ static int nlp_attach_impl(sqphip_ctx *h, const char *who, bool affine, bool gen
         d.nlw = C.dalloc<double>((size_t)d.B * 3 * (size_t)nfac);
         d.nlp = pd;
         C.nl_nv = nv; C.nl_nfac = nfac; C.nl_nterms = nterms;
+        C.nl_end = nvals; C.nl_ws = 3 * nfac; C.nl_blk.clear(); C.nl_started = false;
         C.h_nl_base = val0;                // (the instances' blocks are overwritten by sqphip_nlp_set_instance)
         C.nl_data = data; C.nl_ob = ob; C.nl_oa = oa; C.nl_op = op; C.nl_nargs = nargs;
         if (data) { C.h_nl_tptr = tp; C.h_nl_aptr = ap; C.h_nl_kind.assign(fkind, fkind + nfac); C.h_nl_lin = lin_terms; }
@@ -1988,6 +1990,146 @@ extern "C" int sqphip_nlp_set_instance(sqphip_ctx *h, int32_t inst, const double
     });
 }
 
+// ---- dense data blocks of the objective of a factorable NLP (nlp_block_dev.hpp)
+extern "C" int sqphip_nlp_add_block(sqphip_ctx *h, int32_t kind, int32_t exp, double par, int64_t N, int32_t d, const int64_t *cols,
+                                    const double *A, const double *shift, const double *weight, int32_t *blk_out)
+{
+    const std::string who = "sqphip_nlp_add_block";
+    if (!h) return SQPHIP_EINVAL;
+    Ctx &C0 = h->c;
+    if (!C0.d.nlp) { C0.err = who + ": the context has no factorable NLP attached (sqphip_nlp_attach*)"; return SQPHIP_EINVAL; }
+    if (C0.nl_started) {
+        C0.err = who + ": the layout of the instances is final after sqphip_sqp_reset, sqphip_sqp_run or sqphip_nlp_stream_begin";
+        return SQPHIP_ESTATE;
+    }
+    const int kb = (int)C0.nl_blk.size();
+    const std::string blk = who + ": block " + std::to_string(kb + 1);
+    auto fail = [&](const std::string &msg) { C0.err = blk + ": " + msg; return (int)SQPHIP_EINVAL; };
+    if (kb >= NLP_MAX_BLOCKS) return fail("a context takes at most " + std::to_string((int)NLP_MAX_BLOCKS) + " blocks");
+    if (d < 1 || d > NLP_BLOCK_MAX_D) return fail("d = " + std::to_string(d) + " columns (1.." + std::to_string((int)NLP_BLOCK_MAX_D) + ")");
+    if (N < 1) return fail("N = " + std::to_string(N) + " points (at least 1)");
+    if (N > INT32_MAX / d) return fail("N d = " + std::to_string(N) + " x " + std::to_string(d) + " is too large (N d < 2^31)");
+    if (!cols || !A) return fail("null cols or A");
+    if (kind < NLP_POW || kind > NLP_POWR) return fail("unknown kind " + std::to_string(kind));
+    const int e = kind == NLP_POW ? exp : 1;
+    if (kind == NLP_POW && e == 1) return fail("a plain linear block (POW, e = 1) belongs in the terms");
+    if (e == 0 || e > 32 || e < -32) return fail("exponent " + std::to_string(e) + " (1 <= |e| <= 32)");
+    if (kind == NLP_POWR && (!std::isfinite(par) || par == 0.0)) return fail("real exponent " + std::to_string(par) + " (finite and not 0)");
+    const int64_t n = C0.d.n, nnzH = C0.d.nnzh_coo;
+    for (int j = 0; j < d; ++j) {
+        if (cols[j] < 1 || cols[j] > n) return fail("column " + std::to_string(j + 1) + ": variable " + std::to_string(cols[j]) + " out of range");
+        for (int j2 = 0; j2 < j; ++j2)
+            if (cols[j2] == cols[j]) return fail("column " + std::to_string(j + 1) + ": variable " + std::to_string(cols[j]) + " twice (columns " +
+                                                 std::to_string(j2 + 1) + " and " + std::to_string(j + 1) + ")");
+    }
+    // the first COO copy of a structural entry owns it, as for the plans
+    std::vector<int> hs((size_t)d * (d + 1) / 2, -1), cv(d);
+    for (int j = 0; j < d; ++j) cv[j] = (int)cols[j] - 1;
+    if (nnzH > 0) {
+        std::unordered_map<int64_t, int> hslot;
+        for (int64_t k = nnzH - 1; k >= 0; --k) {
+            const int64_t r = C0.h_hrow[k] - 1, cc = C0.h_hcol[k] - 1;
+            hslot[std::max(r, cc) * n + std::min(r, cc)] = (int)k;
+        }
+        for (int r = 0; r < d; ++r)
+            for (int c = 0; c <= r; ++c) {
+                const int64_t vr = std::max(cv[r], cv[c]), vc = std::min(cv[r], cv[c]);
+                auto it = hslot.find(vr * n + vc);
+                if (it == hslot.end())
+                    return fail("entry (" + std::to_string(r + 1) + ", " + std::to_string(c + 1) + ") needs the Hessian entry (" + std::to_string(vr + 1) +
+                                ", " + std::to_string(vc + 1) + ") that the structure of sqphip_create lacks");
+                hs[(size_t)r * (r + 1) / 2 + c] = it->second;
+            }
+    }
+    const long ow = C0.nl_end, os = ow + N, end = os + N, nv = (end + 1) & ~1L;
+    const long wz = C0.nl_ws + (kb == 0 ? TPB / 64 + 3 * TPB : 0), ws = wz + 2 * N;
+    if (nv > INT32_MAX || ws > INT32_MAX) return fail("too many values per instance");
+    return guarded(h, [&](Ctx &C) {
+        DV &dv = C.d;
+        const long nv0 = C.nl_nv, B = dv.B;
+        // re-lay the instances' blocks behind what they hold
+        std::vector<double> old((size_t)B * nv0), all((size_t)B * nv, 0.0);
+        d2h(C, old.data(), dv.nlv, old.size());
+        NlpDev P;
+        SQPHIP_HIP_OK(hipMemcpyAsync(&P, dv.nlp, sizeof(NlpDev), hipMemcpyDeviceToHost, C.stream));
+        SQPHIP_HIP_OK(hipStreamSynchronize(C.stream));
+        auto fill = [&](double *v) {
+            for (long i = 0; i < N; ++i) { v[ow + i] = weight ? weight[i] : 1.0; v[os + i] = shift ? shift[i] : 0.0; }
+        };
+        for (long b = 0; b < B; ++b) {
+            std::copy(old.begin() + b * nv0, old.begin() + b * nv0 + C.nl_end, all.begin() + b * nv);
+            fill(all.data() + b * nv);
+        }
+        C.h_nl_base.resize(nv, 0.0);
+        std::fill(C.h_nl_base.begin() + C.nl_end, C.h_nl_base.end(), 0.0);
+        fill(C.h_nl_base.data());
+        std::vector<double> a(A, A + (size_t)N * d), at((size_t)N * d);
+        for (long i = 0; i < N; ++i)
+            for (int j = 0; j < d; ++j) at[(size_t)j * N + i] = a[(size_t)i * d + j];
+        NlpBlkDev &K = P.blk[kb];
+        K.ke = kind + (e + 32) * (1 << NLP_KIND_BITS); K.N = (int)N; K.d = d; K.ow = (int)ow; K.os = (int)os; K.wz = (int)wz;
+        K.par = kind == NLP_POWR ? par : 0.0;
+        K.A = C.upload(a); K.At = C.upload(at); K.col = C.upload(cv); K.hs = C.upload(hs);
+        P.nblk = kb + 1; P.nv = (int)nv; P.ws = (int)ws;
+        dv.nlv = C.upload(all);
+        dv.nlw = C.dalloc<double>((size_t)B * (size_t)ws);
+        SQPHIP_HIP_OK(hipMemcpyAsync(const_cast<NlpDev *>(dv.nlp), &P, sizeof(NlpDev), hipMemcpyHostToDevice, C.stream));
+        SQPHIP_HIP_OK(hipStreamSynchronize(C.stream));
+        C.nl_nv = nv; C.nl_end = end; C.nl_ws = ws;
+        C.nl_blk.push_back(Ctx::NlBlock{(long)N, ow, os});
+        make_lanes(C);
+        if (blk_out) *blk_out = kb;
+        return SQPHIP_OK;
+    });
+}
+
+// weight / shift of block blk into the block of values v (of an instance or of a scenario of the queue); NULL: kept
+static int nlp_block_put(sqphip_ctx *h, double *v, int32_t blk, const double *weight, const double *shift)
+{
+    return guarded(h, [&](Ctx &C) {
+        const Ctx::NlBlock &K = C.nl_blk[blk];
+        h2d(C, v + K.ow, weight, (size_t)K.N); h2d(C, v + K.os, shift, (size_t)K.N);
+        SQPHIP_HIP_OK(hipStreamSynchronize(C.stream));
+        return SQPHIP_OK;
+    });
+}
+
+static int nlp_block_check(sqphip_ctx *h, const std::string &who, int32_t blk)
+{
+    Ctx &C = h->c;
+    if (!C.d.nlp) { C.err = who + ": the context has no factorable NLP attached (sqphip_nlp_attach*)"; return SQPHIP_EINVAL; }
+    if (blk < 0 || blk >= (int)C.nl_blk.size()) {
+        C.err = who + ": block " + std::to_string(blk) + " is outside the " + std::to_string(C.nl_blk.size()) + " of the context (sqphip_nlp_add_block)";
+        return SQPHIP_EINVAL;
+    }
+    return SQPHIP_OK;
+}
+
+extern "C" int sqphip_nlp_set_instance_block(sqphip_ctx *h, int32_t inst, int32_t blk, const double *weight, const double *shift)
+{
+    const std::string who = "sqphip_nlp_set_instance_block";
+    if (!h) return SQPHIP_EINVAL;
+    if (int rc = nlp_block_check(h, who, blk)) return rc;
+    if (inst < 0 || inst >= h->c.d.B) {
+        h->c.err = who + ": instance " + std::to_string(inst) + " is outside the batch of " + std::to_string(h->c.d.B);
+        return SQPHIP_EINVAL;
+    }
+    return nlp_block_put(h, h->c.d.nlv + (size_t)inst * h->c.nl_nv, blk, weight, shift);
+}
+
+extern "C" int sqphip_nlp_stream_set_block(sqphip_ctx *h, int32_t scen, int32_t blk, const double *weight, const double *shift)
+{
+    const std::string who = "sqphip_nlp_stream_set_block";
+    if (!h) return SQPHIP_EINVAL;
+    if (int rc = nlp_block_check(h, who, blk)) return rc;
+    if (!h->c.d.stream.val) { h->c.err = who + ": no NLP queue (sqphip_nlp_stream_begin)"; return SQPHIP_EINVAL; }
+    if (scen < 0 || scen >= h->c.d.stream.M) {
+        h->c.err = who + ": scenario " + std::to_string(scen) + " is outside the " + std::to_string(h->c.d.stream.M) + " of the queue";
+        return SQPHIP_EINVAL;
+    }
+    return nlp_block_put(h, const_cast<double *>(h->c.d.stream.val) + (size_t)scen * h->c.nl_nv, blk, weight, shift);
+}
+
 extern "C" int sqphip_acopf_eval(sqphip_ctx *h, int32_t inst, const double *x, double sigma, const double *lambda,
                                  double *f, double *grad, double *g, double *jval, double *hval)
 {
@@ -2014,12 +2156,14 @@ extern "C" int sqphip_acopf_eval(sqphip_ctx *h, int32_t inst, const double *x, d
 extern "C" int sqphip_sqp_reset(sqphip_ctx *h)
 {
     if (!h || !h->c.acopf_attached) return SQPHIP_ESTATE;
+    h->c.nl_started = true;
     return guarded(h, [&](Ctx &C) { sqp_reset(C); return SQPHIP_OK; });
 }
 
 extern "C" int sqphip_sqp_run(sqphip_ctx *h, int32_t max_outer)
 {
     if (!h || !h->c.acopf_attached) return SQPHIP_ESTATE;
+    h->c.nl_started = true;
     return guarded(h, [&](Ctx &C) {
         auto t0 = std::chrono::steady_clock::now();
         sqp_run(C, max_outer);
@@ -2543,6 +2687,7 @@ extern "C" int sqphip_nlp_stream_begin(sqphip_ctx *h, int32_t n_scenarios, int32
     if (!h) return SQPHIP_EINVAL;
     if (!h->c.d.nlp) { h->c.err = "sqphip_nlp_stream_begin: the context has no factorable NLP attached (sqphip_nlp_attach)"; return SQPHIP_EINVAL; }
     if (n_scenarios <= 0) { h->c.err = "sqphip_nlp_stream_begin: n_scenarios must be positive"; return SQPHIP_EINVAL; }
+    h->c.nl_started = true;
     return value_stream_begin(h, n_scenarios, keep_multipliers, h->c.nl_nv);
 }
 

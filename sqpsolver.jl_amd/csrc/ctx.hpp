@@ -213,7 +213,7 @@ struct DV {
     double *qcv;                          // ... its values [B][qc->nv] (nv even)
     // ---- sparse factorable NLP evaluator data
     const NlpDev *nlp;                    // non-null: sums of products of univariate functions (nlp_dev.hpp nlp_eval; sqphip_nlp_attach), its plans in HBM
-    double *nlv, *nlw;                    // ... its values [B][nlp->nv] (nv even) and the factor workspace [B][3 nlp->nfac]
+    double *nlv, *nlw;                    // ... its values [B][nlp->nv] (nv even) and the workspace [B][nlp->ws] (3 nlp->nfac without blocks)
 };
 
 // phase codes by the side a kernel runs on (see the enum)
@@ -286,6 +286,13 @@ struct Ctx {
     long nl_ob = 0, nl_oa = 0, nl_op = -1, nl_nargs = 0;
     std::vector<int> h_nl_tptr, h_nl_aptr, h_nl_kind;   // [nterms + 1], [nfac + 1], [nfac]
     std::vector<int> h_nl_lin;                          // the terms of rows 1..num_linear
+    // sqphip_nlp_add_block: dense data blocks behind those segments, W_k [N_k] | S_k [N_k] each (nl_end: doubles in use before
+    // the padding to even); nl_ws: doubles of workspace per instance (DV::nlw); nl_started: a reset, run or queue has seen the
+    // layout, which is final from then on
+    struct NlBlock { long N, ow, os; };
+    std::vector<NlBlock> nl_blk;
+    long nl_end = 0, nl_ws = 0;
+    bool nl_started = false;
     std::vector<double> h_xL, h_xU, h_gL, h_gU; // the bounds given to sqphip_create (NULL bounds of a queue scenario)
     bool acopf_attached = false;
     bool mf_big_lds = false;        // the multifrontal kernels were granted 160 KB of dynamic LDS on this context's device (mf_device_setup)

@@ -33,6 +33,10 @@
 // the coefficient of an argument of a multi-argument factor, 1.0 for the argument of a one-argument factor (fvar >= 0),
 // whose a is folded into phi', phi'' as above.  The arithmetic is the same expression on other operands, so a data context
 // whose instances carry the attach's arrays files the bits of sqphip_nlp_attach_general; with the switch off no load moves.
+// sqphip_nlp_add_block: dense data blocks sum_i W_i kappa(A_i'x + S_i) in the objective, W and S behind the other segments of
+// the instance's block.  They are evaluated behind the plan passes by one out-of-line call per block (nlp_block_dev.hpp),
+// inside a branch on NlpDev::nblk that is uniform over the launch: a context without a block runs the passes above and
+// nothing else, on the workspace stride NlpDev::ws = 3 nfac it always had.
 #pragma once
 #include "ctx.hpp"
 #include "dev_util.hpp"
@@ -44,6 +48,19 @@ enum { NLP_POW = 0, NLP_SIN = 1, NLP_COS = 2, NLP_EXP = 3, NLP_LOG = 4,
        NLP_SQRT = 5, NLP_TANH = 6, NLP_ATAN = 7, NLP_SIGMOID = 8, NLP_SOFTPLUS = 9, NLP_POWR = 10 };
 enum { NLP_KIND_BITS = 4, NLP_KIND_MASK = (1 << NLP_KIND_BITS) - 1 };     // fke = kind + 16 * (exponent + 32)
 enum { NLP_NONE = -(1 << 30), NLP_ARG = (1 << 28) - 1 };     // no factor of a term; the argument bits of a plan entry (nargs <= 2^28)
+
+// a dense data block of the objective (sqphip_nlp_add_block; evaluator: nlp_block_dev.hpp, included below)
+enum { NLP_MAX_BLOCKS = 4, NLP_BLOCK_MAX_D = 128 };
+
+struct NlpBlkDev {
+    int ke, N, d;                         // kind + 16 * (exponent + 32) as NlpDev::fke; points; columns
+    int ow, os;                           // W [N], S [N] in the instance's block of DV::nlv
+    int wz;                               // z1 [N] | z2 [N] in the instance's workspace (DV::nlw)
+    double par;                           // real exponent (POWR)
+    const double *A, *At;                 // [N][d] row-major (Hessian) and its transpose [d][N] (points, gradient)
+    const int *col;                       // [d] variable of a column (0-based)
+    const int *hs;                        // [d (d + 1) / 2] COO slot of the lower entry (r, c) at r (r + 1) / 2 + c; -1: no Hessian structure
+};
 
 struct NlpDev {
     int n, m, nterms, nfac, nv, nobj;     // variables, rows, terms, factors, values per instance (even), objective terms
@@ -67,6 +84,9 @@ struct NlpDev {
     const double *fpar;                   // [nfac] real exponent of a POWR factor (loaded for that kind only)
     int data;                             // sqphip_nlp_attach_data: b, a, p are the instance's, in its block of DV::nlv at ...
     int ob, oa, op;                       // ... ob [nfac], oa [nargs], op [nfac] (op: with a POWR factor only); fab, acoef, aw, fpar unread
+    int ws;                               // doubles of workspace per instance (DV::nlw): 3 nfac, with blocks + TPB / 64 wave sums + 3 TPB kappa values + 2 sum N_k
+    int nblk;                             // dense data blocks of the objective (sqphip_nlp_add_block, nlp_block_dev.hpp); uniform over the launch
+    NlpBlkDev blk[NLP_MAX_BLOCKS];
 };
 
 // pass 1 of a factor of the kinds SQRT .. POWR at u: kappa, a kappa', a^2 kappa'' to w[0], w[nf], w[2 nf] (nd: how many
@@ -158,6 +178,10 @@ static __device__ __forceinline__ void nlp_factor(int ke, double a, double u, do
     if (d2) w[2 * nf + k] = p2;
 }
 
+}  // namespace sqphip
+#include "nlp_block_dev.hpp"
+namespace sqphip {
+
 // the acopf_eval signature; any of f_out, grad, gv, jv, hv may be null.  Called by every thread of the workgroup.
 static __device__ __forceinline__ void nlp_eval(const DV &d, int inst, const double *__restrict__ x, double sigma,
                                                 const double *__restrict__ lam, double *f_out, double *grad, double *gv,
@@ -166,7 +190,7 @@ static __device__ __forceinline__ void nlp_eval(const DV &d, int inst, const dou
     const NlpDev &q = *d.nlp;
     const int nf = q.nfac;
     const double *__restrict__ val = d.nlv + (long)inst * q.nv;
-    double *__restrict__ w = d.nlw + (long)inst * 3 * nf;
+    double *__restrict__ w = d.nlw + (long)inst * q.ws;
     const double *__restrict__ cf = val + 1 + q.m;
     const int *__restrict__ tptr = q.tptr;
     const bool d1 = grad || jv || hv, d2 = hv != nullptr;     // phi'' is read by the Hessian plan only
@@ -252,6 +276,14 @@ static __device__ __forceinline__ void nlp_eval(const DV &d, int inst, const dou
             hv[s_] = s;
         }
     }
+    // dense data blocks, in block order; a barrier in front of each: the plan passes above and an earlier block wrote
+    // f, grad and hv entries that this block adds to from other threads
+    if (q.nblk != 0)
+        #pragma unroll 1
+        for (int k = 0; k < q.nblk; ++k) {
+            __syncthreads();
+            nlp_block_eval(&q.blk[k], val, w, w + 3 * nf, x, sigma, f_out, grad, hv);
+        }
 }
 
 }  // namespace sqphip

@@ -528,6 +528,52 @@ class Context:
         self._ck(self.L.sqphip_qcqp_set_instance(self.h, inst, *[_d(a) for a in arr], _d(_f(x0))))
 
     # ---- a sparse factorable NLP (nlp_terms.py; csrc/nlp_dev.hpp nlp_eval)
+    def nlp_add_block(self, b) -> int:
+        """One dense data block of the objective (sqphip_nlp_add_block; b: nlp_terms.NlpBlock); before the first sqp_reset,
+        sqp_run or nlp_stream_begin.  Returns its number."""
+        if not hasattr(self.L, "sqphip_nlp_add_block"):
+            raise SqpHipError("libsqphip.so lacks sqphip_nlp_add_block: rebuild it")
+        A = _f(np.atleast_2d(b.A))
+        out = C.c_int32(-1)
+        self._ck(self.L.sqphip_nlp_add_block(self.h, int(b.kind), int(b.exp), float(b.par), A.shape[0], A.shape[1],
+                                             _l(np.ascontiguousarray(b.cols, dtype=np.int64)), _d(A),
+                                             _d(None if b.shift is None else _f(b.shift)),
+                                             _d(None if b.weight is None else _f(b.weight)), C.byref(out)))
+        return out.value
+
+    @staticmethod
+    def _nlp_block_data(who, p, values):
+        """[(block, weight or None, shift or None)] of p's blocks and of the keywords weight / shift, which override: an array
+        for block 0, or a list or dict of arrays by block (None: keep).  The keywords leave `values`."""
+        per = {}
+        for k, b in enumerate(getattr(p, "blocks", None) or []):
+            per[k] = [b.weight, b.shift]
+        for pos, key in enumerate(("weight", "shift")):
+            v = values.pop(key, None)
+            if v is None:
+                continue
+            if isinstance(v, dict):
+                items = v.items()
+            elif isinstance(v, (list, tuple)) and (len(v) == 0 or v[0] is None or np.ndim(v[0]) > 0):
+                items = enumerate(v)
+            else:
+                items = [(0, v)]
+            for k, a in items:
+                if a is not None:
+                    per.setdefault(int(k), [None, None])[pos] = a
+        return [(k, None if w is None else _f(np.atleast_1d(w)), None if s is None else _f(np.atleast_1d(s)))
+                for k, (w, s) in sorted(per.items()) if w is not None or s is not None]
+
+    def nlp_set_instance_block(self, inst, blk, weight=None, shift=None):
+        """weight / shift of block blk of one instance (sqphip_nlp_set_instance_block); None: keep."""
+        self._ck(self.L.sqphip_nlp_set_instance_block(self.h, int(inst), int(blk), _d(None if weight is None else _f(weight)),
+                                                      _d(None if shift is None else _f(shift))))
+
+    def nlp_stream_set_block(self, scen, blk, weight=None, shift=None):
+        """weight / shift of block blk of one scenario of the queue (sqphip_nlp_stream_set_block), after nlp_stream_set."""
+        self._ck(self.L.sqphip_nlp_stream_set_block(self.h, int(scen), int(blk), _d(None if weight is None else _f(weight)),
+                                                    _d(None if shift is None else _f(shift))))
+
     def nlp_attach(self, p, general=None, instance_data=False):
         """Structure of the batch and the values every instance starts with; p: nlp_terms.NlpTerms.  A p with argument arrays
         (affine multi-variable factors) goes through sqphip_nlp_attach_affine, any other through sqphip_nlp_attach; a p
@@ -538,7 +584,15 @@ class Context:
         instance_data = True goes through sqphip_nlp_attach_data: the class of the general call, with shifts, coefficients
         and real exponents owned by the instance (the block f0 | g0 | c | b | a | p).  p's data starts every instance;
         nlp_set_instance(inst, q) and nlp_stream_set(scen, q) then also send q's fshift, acoef and fpar, and q must have
-        p's structure."""
+        p's structure.
+        p's dense data blocks (p.blocks, nlp_terms.NlpBlock) follow whichever attach it was, through nlp_add_block in their
+        order: their weights and shifts start every instance."""
+        self._nlp_attach_terms(p, general, instance_data)
+        for b in getattr(p, "blocks", None) or []:
+            self.nlp_add_block(b)
+
+    def _nlp_attach_terms(self, p, general, instance_data):
+        # (sqphip_nlp_attach_data, _general, _affine or sqphip_nlp_attach: the choice nlp_attach documents)
         from .nlp_terms import nlp_terms_args
         if instance_data:
             if not hasattr(self.L, "sqphip_nlp_attach_data"):
@@ -605,7 +659,9 @@ class Context:
         f0, g0, tcoef override single parts, and what is given neither way is kept.  On a context of
         nlp_attach(instance_data=True) p's fshift, acoef and fpar go along (sqphip_nlp_set_instance_data; p must have the
         attached structure) and the keywords fshift, acoef, fpar override single parts."""
-        values, data = self._nlp_data_of("nlp_set_instance", p, dict(values))
+        values = dict(values)
+        blocks = self._nlp_block_data("nlp_set_instance", p, values)
+        values, data = self._nlp_data_of("nlp_set_instance", p, values)
         if p is not None:
             self.set_bounds(inst, p)
             values = {**{k: getattr(p, k) for k in ("f0", "g0", "tcoef")}, **values}
@@ -617,6 +673,8 @@ class Context:
         self._ck(self.L.sqphip_nlp_set_instance(self.h, inst, *[_d(a) for a in arr], _d(_f(x0))))
         if data is not None and any(a is not None for a in data):
             self._ck(self.L.sqphip_nlp_set_instance_data(self.h, inst, *[_d(a) for a in data]))
+        for k, w, sh in blocks:
+            self.nlp_set_instance_block(inst, k, w, sh)
 
     def acopf_eval(self, inst, x, sigma=1.0, lam=None):
         f = C.c_double(); grad = np.zeros(self.n); g = np.zeros(self.m)
@@ -800,7 +858,9 @@ class Context:
         attached structure); the keywords fshift, acoef, fpar override single parts, and a part given neither way is the
         attach's."""
         names, bnames = ("f0", "g0", "tcoef"), ("xL", "xU", "gL", "gU")
-        values, data = self._nlp_data_of("nlp_stream_set", p, dict(values))
+        values = dict(values)
+        blocks = self._nlp_block_data("nlp_stream_set", p, values)
+        values, data = self._nlp_data_of("nlp_stream_set", p, values)
         if p is not None:
             values = {**{k: getattr(p, k) for k in names + bnames}, **values}
             x0 = p.x0 if x0 is None else x0
@@ -811,6 +871,8 @@ class Context:
         self._ck(self.L.sqphip_nlp_stream_set(self.h, int(scen), *[_d(a) for a in arr], _d(_f(x0))))
         if data is not None and any(a is not None for a in data):
             self._ck(self.L.sqphip_nlp_stream_set_data(self.h, int(scen), *[_d(a) for a in data]))
+        for k, w, sh in blocks:
+            self.nlp_stream_set_block(scen, k, w, sh)
 
     def stream_get_full(self, scen):
         """The dict of sqp_get for a scenario of a queue begun with keep_multipliers (sqphip_sqp_stream_get_full)."""

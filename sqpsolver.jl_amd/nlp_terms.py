@@ -35,6 +35,11 @@ plain affine factors.  Twice inside one factor stays an error.  SQRT and POWR ne
     nlp_data_scenario    ... other shifts, argument coefficients and real exponents (sqphip_nlp_attach_data: the data of the
                          factors belongs to the instance), the same feasible start
     logistic_folds       the k training folds of a dataset as k logistic models of one structure
+    NlpBlock             a dense data block of the objective, sum_i w_i kappa(A_i'x_cols + b_i) (sqphip_nlp_add_block): A, the
+                         columns and the kind are shared by the batch, the weights and shifts belong to the instance
+    block_eval           value, gradient and dense Hessian of the blocks of a problem in numpy
+    logistic_block_model, poisson_block_model, least_squares_block_model     data fits of any size as one block plus terms
+    fold_weights         the k training folds of N points as 0 / 1 weight vectors (logistic_fold_indices)
     from_qcqp            a Qcqp (qcqp.py) restated as terms
     from_polar_acopf     the polar ACOPF of acopf_layout restated as terms, on that layout's COO structures
 
@@ -49,6 +54,28 @@ POW, SIN, COS, EXP, LOG = 0, 1, 2, 3, 4
 SQRT, TANH, ATAN, SIGMOID, SOFTPLUS, POWR = 5, 6, 7, 8, 9, 10
 MAX_FACTORS = 8
 MAX_ARGS = 8
+MAX_BLOCKS = 4
+MAX_BLOCK_COLS = 128
+
+
+@dataclasses.dataclass
+class NlpBlock:
+    """sum_{i < N} weight_i kappa(sum_j A[i, j] x_{cols[j]} + shift_i) in the objective: kind from the menu (exp for POW, par
+    for POWR), cols d distinct 1-based variables in any order (d <= 128), A [N, d]; shift None: zeros, weight None: ones."""
+    kind: int
+    cols: np.ndarray
+    A: np.ndarray
+    shift: np.ndarray | None = None
+    weight: np.ndarray | None = None
+    exp: int = 1
+    par: float = 0.0
+
+    def __post_init__(self):
+        self.cols = _i64(np.atleast_1d(self.cols))
+        self.A = _f64(np.atleast_2d(self.A))
+        N = self.A.shape[0]
+        self.shift = np.zeros(N) if self.shift is None else _f64(self.shift)
+        self.weight = np.ones(N) if self.weight is None else _f64(self.weight)
 
 
 @dataclasses.dataclass
@@ -77,6 +104,7 @@ class NlpTerms:
     fpar: np.ndarray | None = None     # [nfac] real exponent of a POWR factor (0 elsewhere); None: no POWR factor
     general: bool = False              # written for sqphip_nlp_attach_general (make_nlp_terms: needs_general); False: a model
                                        # of the older calls, which keep refusing what they refuse
+    blocks: list = dataclasses.field(default_factory=list)     # NlpBlock: dense data blocks of the objective (at most 4)
 
     @property
     def affine(self) -> bool:
@@ -115,7 +143,7 @@ def _f64(a):
     return np.ascontiguousarray(a, dtype=np.float64)
 
 
-def make_nlp_terms(n, m, num_linear, terms, g0=None, f0=0.0, xL=None, xU=None, gL=None, gU=None, x0=None) -> NlpTerms:
+def make_nlp_terms(n, m, num_linear, terms, g0=None, f0=0.0, xL=None, xU=None, gL=None, gU=None, x0=None, blocks=None) -> NlpTerms:
     """terms: (row, coefficient, factors) with row 0 for the objective and factors (variable, kind[, e[, a[, b]]]), 1-based
     variables; a factor may be (args, kind[, e[, b]]) with args a list of (variable, coefficient) pairs, and one such factor
     makes the problem an affine one (aptr / avar / acoef set).  The e of a POWR factor is its real exponent (fpar set).
@@ -145,6 +173,7 @@ def make_nlp_terms(n, m, num_linear, terms, g0=None, f0=0.0, xL=None, xU=None, g
                  np.ascontiguousarray(fe, dtype=np.int32), _f64(fa), _f64(fb), full(g0, m, 0.0), float(f0),
                  full(xL, n, -inf), full(xU, n, inf), full(gL, m, -inf), full(gU, m, inf), full(x0, n, 0.0), *extra)
     p.general = needs_general(p)
+    p.blocks = list(blocks or [])
     return p
 
 
@@ -155,7 +184,8 @@ def _term_of_factor(p: NlpTerms) -> np.ndarray:
 def nlp_terms_layout(p: NlpTerms) -> NlpTermsLayout:
     """Jacobian COO: (i, v) of every argument of every factor of a term of row i, row-major; Hessian COO: the lower entry
     (v, w) of every two distinct variables of one term -- except two arguments of one plain linear factor (POW, e = 1) --
-    and (v, v) of every argument of a factor that is not plain linear, column-major.  Each once."""
+    and (v, v) of every argument of a factor that is not plain linear, column-major; every pair of columns of a block,
+    the diagonal included.  Each once."""
     n = p.n
     aptr, avar, _ = nlp_terms_args(p)
     nargs = np.diff(aptr)
@@ -175,6 +205,9 @@ def nlp_terms_layout(p: NlpTerms) -> NlpTermsLayout:
             keep = (f[a] != f[b]) | curved[f[a]]
             a, b = a[keep], b[keep]
             hk.append((np.minimum(v[a], v[b]) - 1) * n + np.maximum(v[a], v[b]) - 1)      # column-major key of the lower entry
+    for b in getattr(p, "blocks", []):
+        a, c = np.tril_indices(len(b.cols))
+        hk.append((np.minimum(b.cols[a], b.cols[c]) - 1) * n + np.maximum(b.cols[a], b.cols[c]) - 1)
     hkey = np.unique(np.concatenate(hk)) if hk else np.zeros(0, np.int64)
     return NlpTermsLayout(n, p.m, p.num_linear, jkey // n + 1, jkey % n + 1, hkey % n + 1, hkey // n + 1,
                           p.xL.copy(), p.xU.copy(), p.gL.copy(), p.gU.copy(), p.x0.copy())
@@ -437,6 +470,97 @@ def logistic_model(X, y, reg) -> NlpTerms:
     terms += [(0, -float(y @ X[:, j]), [(j + 1, POW)]) for j in range(n)]
     terms += [(0, 0.5 * float(reg), [(j + 1, POW, 2)]) for j in range(n)]
     return make_nlp_terms(n, 0, 0, terms, xL=np.full(n, -50.0), xU=np.full(n, 50.0), x0=np.zeros(n))
+
+
+def _kappa3(kind, e, par, u):
+    """kappa, kappa', kappa'' of one menu entry at the array u."""
+    u = _f64(u)
+    with np.errstate(all="ignore"):
+        if kind == POW:
+            e = int(e)
+            return u ** e, e * u ** (e - 1), (e * (e - 1)) * u ** (e - 2) if e != 1 else np.zeros_like(u)
+        if kind == POWR:
+            return u ** par, par * u ** (par - 1.0), par * (par - 1.0) * u ** (par - 2.0)
+        if kind == SIN:
+            return np.sin(u), np.cos(u), -np.sin(u)
+        if kind == COS:
+            return np.cos(u), -np.sin(u), -np.cos(u)
+        if kind == EXP:
+            return np.exp(u), np.exp(u), np.exp(u)
+        if kind == LOG:
+            return np.log(u), 1.0 / u, -1.0 / (u * u)
+        if kind == SQRT:
+            r = np.sqrt(u)
+            return r, 0.5 / r, -0.25 / (u * r)
+        if kind == TANH:
+            t = np.tanh(u)
+            return t, 1.0 - t * t, -2.0 * t * (1.0 - t * t)
+        if kind == ATAN:
+            q = 1.0 / (1.0 + u * u)
+            return np.arctan(u), q, -2.0 * u * q * q
+        e_ = np.exp(-np.abs(u))
+        sg, sc = np.where(u < 0, e_ / (1.0 + e_), 1.0 / (1.0 + e_)), np.where(u < 0, 1.0 / (1.0 + e_), e_ / (1.0 + e_))
+        if kind == SIGMOID:
+            return sg, sg * sc, sg * sc * (sc - sg)
+        if kind == SOFTPLUS:
+            return np.maximum(u, 0.0) + np.log1p(e_), sg, sg * sc
+    raise ValueError(f"unknown kind {kind}")
+
+
+def block_eval(p: NlpTerms, x, blocks=None):
+    """(f, grad [n], H [n, n]) of the blocks of p at x: sum_i w_i kappa(u_i), A'(w kappa'), A' diag(w kappa'') A scattered to
+    the blocks' columns."""
+    x = _f64(x)
+    f, g, H = 0.0, np.zeros(p.n), np.zeros((p.n, p.n))
+    for b in (p.blocks if blocks is None else blocks):
+        c = b.cols - 1
+        k0, k1, k2 = _kappa3(b.kind, b.exp, b.par, b.A @ x[c] + b.shift)
+        f += float(b.weight @ k0)
+        np.add.at(g, c, b.A.T @ (b.weight * k1))
+        H[np.ix_(c, c)] += b.A.T @ ((b.weight * k2)[:, None] * b.A)
+    return f, g, H
+
+
+def fold_weights(N: int, k: int) -> np.ndarray:
+    """[k, N] 0 / 1 weights: row f is 1 on the training rows of fold f of logistic_fold_indices(N, k), 0 on its validation
+    rows and on the N % k rows that no fold uses."""
+    W = np.zeros((int(k), int(N)))
+    for f, (tr, _) in enumerate(logistic_fold_indices(N, k)):
+        W[f, tr] = 1.0
+    return W
+
+
+def _ridge(n, reg):
+    return [(0, 0.5 * float(reg), [(j + 1, POW, 2)]) for j in range(n)] if reg else []
+
+
+def logistic_block_model(X, y, reg, weight=None) -> NlpTerms:
+    """logistic_model as one SOFTPLUS block: softplus(u) - y u = softplus((1 - 2 y) u) for y in {0, 1}, so row i of X enters
+    as (1 - 2 y_i) X_i and the model is sum_i w_i softplus(A_i'w) + reg / 2 |w|^2 -- no linear terms, and the folds or
+    resamples of one dataset differ in the weights only (fold_weights).  -50 <= w <= 50, from w = 0."""
+    X, y = np.atleast_2d(_f64(X)), _f64(y)
+    N, n = X.shape
+    blk = NlpBlock(SOFTPLUS, np.arange(1, n + 1), (1.0 - 2.0 * y)[:, None] * X, None, weight)
+    return make_nlp_terms(n, 0, 0, _ridge(n, reg), xL=np.full(n, -50.0), xU=np.full(n, 50.0), x0=np.zeros(n), blocks=[blk])
+
+
+def poisson_block_model(X, counts, reg, weight=None) -> NlpTerms:
+    """Ridge-regularised Poisson regression, sum_i w_i [exp(X_i'b) - c_i X_i'b] + reg / 2 |b|^2: an EXP block and the linear
+    terms -(sum_i w_i c_i X_ij) b_j, whose coefficients are the instance's as the weights are.  -50 <= b <= 50, from 0."""
+    X, c = np.atleast_2d(_f64(X)), _f64(counts)
+    N, n = X.shape
+    w = np.ones(N) if weight is None else _f64(weight)
+    terms = [(0, -float((w * c) @ X[:, j]), [(j + 1, POW)]) for j in range(n)] + _ridge(n, reg)
+    blk = NlpBlock(EXP, np.arange(1, n + 1), X, None, w)
+    return make_nlp_terms(n, 0, 0, terms, xL=np.full(n, -50.0), xU=np.full(n, 50.0), x0=np.zeros(n), blocks=[blk])
+
+
+def least_squares_block_model(A, b, reg) -> NlpTerms:
+    """sum_i (A_i'x - b_i)^2 + reg / 2 |x|^2: a POW 2 block with the shifts -b (measurements: one b per instance).  No
+    bounds, from x = 0."""
+    A, b = np.atleast_2d(_f64(A)), _f64(b)
+    n = A.shape[1]
+    return make_nlp_terms(n, 0, 0, _ridge(n, reg), x0=np.zeros(n), blocks=[NlpBlock(POW, np.arange(1, n + 1), A, -b, None, exp=2)])
 
 
 def nlp_terms_scenario(p: NlpTerms, s: int, seed: int = 1, noise: float = 0.05) -> NlpTerms:
