@@ -522,8 +522,46 @@ int sqphip_nlp_add_block(sqphip_ctx *ctx, int32_t kind, int32_t exp, double par,
                          const int64_t *cols /* [d] 1-based */, const double *A /* [N][d] row-major */,
                          const double *shift /* [N] or NULL: zeros */, const double *weight /* [N] or NULL: ones */,
                          int32_t *blk_out /* 0-based block number, or NULL */);
-/* weight [N], shift [N] of block blk of one instance; NULL: keep.  SQPHIP_EINVAL for inst or blk out of range. */
+/* weight [N], shift [N] (a softmax block: [Kf][N]) of block blk of one instance; NULL: keep.  SQPHIP_EINVAL for inst or blk
+ * out of range. */
 int sqphip_nlp_set_instance_block(sqphip_ctx *ctx, int32_t inst, int32_t blk, const double *weight, const double *shift);
+/* Multinomial (softmax) data blocks of the objective of an NLP context: the block adds
+ *     sum_{i < N} W[i] [ log sum_{k < K} exp(u_ik) - u_{i, labels[i]} ],   u_ik = sum_{j < d} A[i][j] x_{cols[k][j]} + S[k][i]
+ * to row 0: K-class logistic regression on a dense row-major N x d design matrix A.  A, cols, the labels (0-based, < K) and
+ * K are shared by the batch; the weights W [N] (folds, resamples) and the per-class offsets S [Kf][N] (prior correction,
+ * stage-wise fitting) belong to the instance.  pinned = 1: the last class has no variables and u_{i, K - 1} = 0 (the
+ * identifiable form), Kf = K - 1; pinned = 0: Kf = K.  Limits: 2 <= K <= 64, d >= 1, Kf d <= 128, N >= 1, N d < 2^31; the Kf d
+ * columns are distinct and 1-based, in any order.  Softmax blocks count among the four blocks of a context and are evaluated
+ * in block order with the blocks of sqphip_nlp_add_block, behind the same barrier.  With q = k d + j and the softmax
+ * probabilities p_ik: gradient g_q = sum_i W[i] (p_ik - [labels[i] = k]) A[i][j], Hessian
+ * H_qq' = sum_i W[i] p_ik ([k = l] - p_il) A[i][j] A[i][j'] (q' = l d + j').
+ * State rules and re-lay as for sqphip_nlp_add_block (SQPHIP_ESTATE once the layout is final); the instance's block grows by
+ *     W [N] | S [Kf N]                                                            (padded to an even count)
+ * sqphip_nlp_set_instance_block and sqphip_nlp_stream_set_block serve the block unchanged, with a shift array of Kf N entries.
+ * Unless nnzH = 0 the Hessian COO of sqphip_create must hold the lower entry of every pair of the block's Kf d columns.
+ * SQPHIP_EINVAL, with sqphip_last_error naming the block and the 1-based column, entry or point: a context without an NLP
+ * attach, K outside 2..64, d < 1, Kf d > 128, N < 1 or N d too large, a fifth block, a column out of range or twice anywhere
+ * in the block, a label outside 0..K-1, null cols, A or labels, a missing Hessian entry.
+ * Evaluation (one workgroup per instance; every sum in an order that depends on N, d, K and pinned only, no atomics):
+ *   points    u_ik = 0, u_ik = fma(A[i][j], x_cols[k][j], u_ik) for j = 0 .. d - 1, u_ik += S[k][i]; m = max_k u_ik (the pinned
+ *             class enters with 0); e_k = exp(u_ik - m), s = sum of e_k for k = 0 .. Kf - 1 in that order, then exp(0 - m) of
+ *             the pinned class; lse = m + log(s); p_ik = e_k / s.  u_ik - m <= 0 and s >= 1: logits of +-800 give finite
+ *             results;
+ *   f         thread t sums W[i] (lse_i - u_{i, labels[i]}) over i = t, t + 1024, ..., a wave adds its 64 sums by the xor
+ *             butterfly 32, 16, .. 1, thread 0 adds the 16 wave sums in wave order, and the result is added to f;
+ *   gradient  entry q: lane l of its wave sums (W[i] (p_ik - [labels[i] = k])) A[i][j] over i = l, l + 64, ..., the same
+ *             butterfly, added to grad[cols[k][j]];
+ *   Hessian   lower 16 x 16 tiles of the Kf d x Kf d matrix on v_mfma_f64_16x16x4_f64, four points per instruction in rising
+ *             order, two accumulator chains with the shared operand (W[i] p_ik) A[i][j] (two roundings) against
+ *             (-p_il) A[i][j'] (one rounding) and against A[i][j']; the second chain counts for the entries with k = l only
+ *             and is skipped for a tile without any; ragged edges as zeros; sigma times (chain 1 + [k = l] chain 2) is added
+ *             to the entry's COO slot by one thread.
+ * Results are bit-reproducible and independent of slot, neighbours and instance groups.  A context without a softmax
+ * block files the bits it filed before this call existed. */
+int sqphip_nlp_add_softmax_block(sqphip_ctx *ctx, int64_t N, int32_t d, int32_t K, int32_t pinned,
+                                 const int64_t *cols /* [Kf][d] 1-based */, const double *A /* [N][d] row-major */,
+                                 const int32_t *labels /* [N] 0-based */, const double *shift /* [Kf][N] or NULL: zeros */,
+                                 const double *weight /* [N] or NULL: ones */, int32_t *blk_out /* 0-based block number, or NULL */);
 /* Per-instance values (f0 one value, g0 [m], tcoef [nterms] in the term order of the attach) and the start x0 [n];
  * any pointer may be NULL: keep.  Bounds go through sqphip_set_bounds. */
 int sqphip_nlp_set_instance(sqphip_ctx *ctx, int32_t inst, const double *f0, const double *g0,

@@ -1990,60 +1990,66 @@ extern "C" int sqphip_nlp_set_instance(sqphip_ctx *h, int32_t inst, const double
     });
 }
 
-// ---- dense data blocks of the objective of a factorable NLP (nlp_block_dev.hpp)
-extern "C" int sqphip_nlp_add_block(sqphip_ctx *h, int32_t kind, int32_t exp, double par, int64_t N, int32_t d, const int64_t *cols,
-                                    const double *A, const double *shift, const double *weight, int32_t *blk_out)
+// ---- dense data blocks of the objective of a factorable NLP (nlp_block_dev.hpp, nlp_softmax_dev.hpp)
+// the state rules of the add calls; kb: the number of the block to be, blk: "who: block kb + 1" for the messages
+static int nlp_block_begin(sqphip_ctx *h, const std::string &who, int &kb, std::string &blk)
 {
-    const std::string who = "sqphip_nlp_add_block";
-    if (!h) return SQPHIP_EINVAL;
     Ctx &C0 = h->c;
     if (!C0.d.nlp) { C0.err = who + ": the context has no factorable NLP attached (sqphip_nlp_attach*)"; return SQPHIP_EINVAL; }
     if (C0.nl_started) {
         C0.err = who + ": the layout of the instances is final after sqphip_sqp_reset, sqphip_sqp_run or sqphip_nlp_stream_begin";
         return SQPHIP_ESTATE;
     }
-    const int kb = (int)C0.nl_blk.size();
-    const std::string blk = who + ": block " + std::to_string(kb + 1);
-    auto fail = [&](const std::string &msg) { C0.err = blk + ": " + msg; return (int)SQPHIP_EINVAL; };
-    if (kb >= NLP_MAX_BLOCKS) return fail("a context takes at most " + std::to_string((int)NLP_MAX_BLOCKS) + " blocks");
-    if (d < 1 || d > NLP_BLOCK_MAX_D) return fail("d = " + std::to_string(d) + " columns (1.." + std::to_string((int)NLP_BLOCK_MAX_D) + ")");
-    if (N < 1) return fail("N = " + std::to_string(N) + " points (at least 1)");
-    if (N > INT32_MAX / d) return fail("N d = " + std::to_string(N) + " x " + std::to_string(d) + " is too large (N d < 2^31)");
-    if (!cols || !A) return fail("null cols or A");
-    if (kind < NLP_POW || kind > NLP_POWR) return fail("unknown kind " + std::to_string(kind));
-    const int e = kind == NLP_POW ? exp : 1;
-    if (kind == NLP_POW && e == 1) return fail("a plain linear block (POW, e = 1) belongs in the terms");
-    if (e == 0 || e > 32 || e < -32) return fail("exponent " + std::to_string(e) + " (1 <= |e| <= 32)");
-    if (kind == NLP_POWR && (!std::isfinite(par) || par == 0.0)) return fail("real exponent " + std::to_string(par) + " (finite and not 0)");
+    kb = (int)C0.nl_blk.size();
+    blk = who + ": block " + std::to_string(kb + 1);
+    if (kb >= NLP_MAX_BLOCKS) { C0.err = blk + ": a context takes at most " + std::to_string((int)NLP_MAX_BLOCKS) + " blocks"; return SQPHIP_EINVAL; }
+    return SQPHIP_OK;
+}
+
+// cols [D] 1-based, in range and distinct, to cv (0-based), and the COO slot of every lower entry (r, c) of the block's
+// D x D Hessian to hs (-1 throughout when nnzH = 0): the first COO copy of a structural entry owns it, as for the plans.
+// Returns the complaint, empty when there is none.
+static std::string nlp_block_columns(const Ctx &C0, int D, const int64_t *cols, std::vector<int> &cv, std::vector<int> &hs)
+{
     const int64_t n = C0.d.n, nnzH = C0.d.nnzh_coo;
-    for (int j = 0; j < d; ++j) {
-        if (cols[j] < 1 || cols[j] > n) return fail("column " + std::to_string(j + 1) + ": variable " + std::to_string(cols[j]) + " out of range");
+    for (int j = 0; j < D; ++j) {
+        if (cols[j] < 1 || cols[j] > n) return "column " + std::to_string(j + 1) + ": variable " + std::to_string(cols[j]) + " out of range";
         for (int j2 = 0; j2 < j; ++j2)
-            if (cols[j2] == cols[j]) return fail("column " + std::to_string(j + 1) + ": variable " + std::to_string(cols[j]) + " twice (columns " +
-                                                 std::to_string(j2 + 1) + " and " + std::to_string(j + 1) + ")");
+            if (cols[j2] == cols[j]) return "column " + std::to_string(j + 1) + ": variable " + std::to_string(cols[j]) + " twice (columns " +
+                                            std::to_string(j2 + 1) + " and " + std::to_string(j + 1) + ")";
     }
-    // the first COO copy of a structural entry owns it, as for the plans
-    std::vector<int> hs((size_t)d * (d + 1) / 2, -1), cv(d);
-    for (int j = 0; j < d; ++j) cv[j] = (int)cols[j] - 1;
+    hs.assign((size_t)D * (D + 1) / 2, -1); cv.resize(D);
+    for (int j = 0; j < D; ++j) cv[j] = (int)cols[j] - 1;
     if (nnzH > 0) {
         std::unordered_map<int64_t, int> hslot;
         for (int64_t k = nnzH - 1; k >= 0; --k) {
             const int64_t r = C0.h_hrow[k] - 1, cc = C0.h_hcol[k] - 1;
             hslot[std::max(r, cc) * n + std::min(r, cc)] = (int)k;
         }
-        for (int r = 0; r < d; ++r)
+        for (int r = 0; r < D; ++r)
             for (int c = 0; c <= r; ++c) {
                 const int64_t vr = std::max(cv[r], cv[c]), vc = std::min(cv[r], cv[c]);
                 auto it = hslot.find(vr * n + vc);
                 if (it == hslot.end())
-                    return fail("entry (" + std::to_string(r + 1) + ", " + std::to_string(c + 1) + ") needs the Hessian entry (" + std::to_string(vr + 1) +
-                                ", " + std::to_string(vc + 1) + ") that the structure of sqphip_create lacks");
+                    return "entry (" + std::to_string(r + 1) + ", " + std::to_string(c + 1) + ") needs the Hessian entry (" + std::to_string(vr + 1) +
+                           ", " + std::to_string(vc + 1) + ") that the structure of sqphip_create lacks";
                 hs[(size_t)r * (r + 1) / 2 + c] = it->second;
             }
     }
-    const long ow = C0.nl_end, os = ow + N, end = os + N, nv = (end + 1) & ~1L;
-    const long wz = C0.nl_ws + (kb == 0 ? TPB / 64 + 3 * TPB : 0), ws = wz + 2 * N;
-    if (nv > INT32_MAX || ws > INT32_MAX) return fail("too many values per instance");
+    return "";
+}
+
+// Re-lays the instances' blocks of doubles behind what they hold with W [N] | S [nS] of block kb (weight NULL: ones, shift
+// NULL: zeros), uploads A [N][d] and its transpose, cv and hs, and files the block K (ke, par, K, Kf, y: the caller's; wsz:
+// its doubles of workspace) in the context's NlpDev.
+static int nlp_block_commit(sqphip_ctx *h, const std::string &blk, int kb, long N, int d, long nS, long wsz, const double *A,
+                            const std::vector<int> &cv, const std::vector<int> &hs, const double *weight, const double *shift,
+                            NlpBlkDev K, int32_t *blk_out)
+{
+    Ctx &C0 = h->c;
+    const long ow = C0.nl_end, os = ow + N, end = os + nS, nv = (end + 1) & ~1L;
+    const long wz = C0.nl_ws + (kb == 0 ? TPB / 64 + 3 * TPB : 0), ws = wz + wsz;
+    if (nv > INT32_MAX || ws > INT32_MAX) { C0.err = blk + ": too many values per instance"; return SQPHIP_EINVAL; }
     return guarded(h, [&](Ctx &C) {
         DV &dv = C.d;
         const long nv0 = C.nl_nv, B = dv.B;
@@ -2054,7 +2060,8 @@ extern "C" int sqphip_nlp_add_block(sqphip_ctx *h, int32_t kind, int32_t exp, do
         SQPHIP_HIP_OK(hipMemcpyAsync(&P, dv.nlp, sizeof(NlpDev), hipMemcpyDeviceToHost, C.stream));
         SQPHIP_HIP_OK(hipStreamSynchronize(C.stream));
         auto fill = [&](double *v) {
-            for (long i = 0; i < N; ++i) { v[ow + i] = weight ? weight[i] : 1.0; v[os + i] = shift ? shift[i] : 0.0; }
+            for (long i = 0; i < N; ++i) v[ow + i] = weight ? weight[i] : 1.0;
+            for (long i = 0; i < nS; ++i) v[os + i] = shift ? shift[i] : 0.0;
         };
         for (long b = 0; b < B; ++b) {
             std::copy(old.begin() + b * nv0, old.begin() + b * nv0 + C.nl_end, all.begin() + b * nv);
@@ -2066,21 +2073,79 @@ extern "C" int sqphip_nlp_add_block(sqphip_ctx *h, int32_t kind, int32_t exp, do
         std::vector<double> a(A, A + (size_t)N * d), at((size_t)N * d);
         for (long i = 0; i < N; ++i)
             for (int j = 0; j < d; ++j) at[(size_t)j * N + i] = a[(size_t)i * d + j];
-        NlpBlkDev &K = P.blk[kb];
-        K.ke = kind + (e + 32) * (1 << NLP_KIND_BITS); K.N = (int)N; K.d = d; K.ow = (int)ow; K.os = (int)os; K.wz = (int)wz;
-        K.par = kind == NLP_POWR ? par : 0.0;
+        K.N = (int)N; K.d = d; K.ow = (int)ow; K.os = (int)os; K.wz = (int)wz;
         K.A = C.upload(a); K.At = C.upload(at); K.col = C.upload(cv); K.hs = C.upload(hs);
+        P.blk[kb] = K;
         P.nblk = kb + 1; P.nv = (int)nv; P.ws = (int)ws;
         dv.nlv = C.upload(all);
         dv.nlw = C.dalloc<double>((size_t)B * (size_t)ws);
         SQPHIP_HIP_OK(hipMemcpyAsync(const_cast<NlpDev *>(dv.nlp), &P, sizeof(NlpDev), hipMemcpyHostToDevice, C.stream));
         SQPHIP_HIP_OK(hipStreamSynchronize(C.stream));
         C.nl_nv = nv; C.nl_end = end; C.nl_ws = ws;
-        C.nl_blk.push_back(Ctx::NlBlock{(long)N, ow, os});
+        C.nl_blk.push_back(Ctx::NlBlock{N, ow, os, nS});
         make_lanes(C);
         if (blk_out) *blk_out = kb;
         return SQPHIP_OK;
     });
+}
+
+extern "C" int sqphip_nlp_add_block(sqphip_ctx *h, int32_t kind, int32_t exp, double par, int64_t N, int32_t d, const int64_t *cols,
+                                    const double *A, const double *shift, const double *weight, int32_t *blk_out)
+{
+    const std::string who = "sqphip_nlp_add_block";
+    if (!h) return SQPHIP_EINVAL;
+    Ctx &C0 = h->c;
+    int kb; std::string blk;
+    if (int rc = nlp_block_begin(h, who, kb, blk)) return rc;
+    auto fail = [&](const std::string &msg) { C0.err = blk + ": " + msg; return (int)SQPHIP_EINVAL; };
+    if (d < 1 || d > NLP_BLOCK_MAX_D) return fail("d = " + std::to_string(d) + " columns (1.." + std::to_string((int)NLP_BLOCK_MAX_D) + ")");
+    if (N < 1) return fail("N = " + std::to_string(N) + " points (at least 1)");
+    if (N > INT32_MAX / d) return fail("N d = " + std::to_string(N) + " x " + std::to_string(d) + " is too large (N d < 2^31)");
+    if (!cols || !A) return fail("null cols or A");
+    if (kind < NLP_POW || kind > NLP_POWR) return fail("unknown kind " + std::to_string(kind));
+    const int e = kind == NLP_POW ? exp : 1;
+    if (kind == NLP_POW && e == 1) return fail("a plain linear block (POW, e = 1) belongs in the terms");
+    if (e == 0 || e > 32 || e < -32) return fail("exponent " + std::to_string(e) + " (1 <= |e| <= 32)");
+    if (kind == NLP_POWR && (!std::isfinite(par) || par == 0.0)) return fail("real exponent " + std::to_string(par) + " (finite and not 0)");
+    std::vector<int> hs, cv;
+    const std::string bad = nlp_block_columns(C0, d, cols, cv, hs);
+    if (!bad.empty()) return fail(bad);
+    NlpBlkDev K = {};
+    K.ke = kind + (e + 32) * (1 << NLP_KIND_BITS);
+    K.par = kind == NLP_POWR ? par : 0.0;
+    return nlp_block_commit(h, blk, kb, (long)N, d, (long)N, 2 * (long)N, A, cv, hs, weight, shift, K, blk_out);
+}
+
+// a multinomial (softmax) block (nlp_softmax_dev.hpp)
+extern "C" int sqphip_nlp_add_softmax_block(sqphip_ctx *h, int64_t N, int32_t d, int32_t K, int32_t pinned, const int64_t *cols,
+                                            const double *A, const int32_t *labels, const double *shift, const double *weight,
+                                            int32_t *blk_out)
+{
+    const std::string who = "sqphip_nlp_add_softmax_block";
+    if (!h) return SQPHIP_EINVAL;
+    Ctx &C0 = h->c;
+    int kb; std::string blk;
+    if (int rc = nlp_block_begin(h, who, kb, blk)) return rc;
+    auto fail = [&](const std::string &msg) { C0.err = blk + ": " + msg; return (int)SQPHIP_EINVAL; };
+    if (K < 2 || K > NLP_SOFTMAX_MAX_K) return fail("K = " + std::to_string(K) + " classes (2.." + std::to_string((int)NLP_SOFTMAX_MAX_K) + ")");
+    if (d < 1) return fail("d = " + std::to_string(d) + " features (at least 1)");
+    const int Kf = pinned ? K - 1 : K;
+    if ((long)Kf * d > NLP_BLOCK_MAX_D)
+        return fail("Kf d = " + std::to_string(Kf) + " x " + std::to_string(d) + " columns (at most " + std::to_string((int)NLP_BLOCK_MAX_D) + ")");
+    if (N < 1) return fail("N = " + std::to_string(N) + " points (at least 1)");
+    if (N > INT32_MAX / d) return fail("N d = " + std::to_string(N) + " x " + std::to_string(d) + " is too large (N d < 2^31)");
+    if (!cols || !A || !labels) return fail("null cols, A or labels");
+    for (int64_t i = 0; i < N; ++i)
+        if (labels[i] < 0 || labels[i] >= K)
+            return fail("point " + std::to_string(i + 1) + ": label " + std::to_string(labels[i]) + " outside 0.." + std::to_string(K - 1));
+    std::vector<int> hs, cv;
+    const std::string bad = nlp_block_columns(C0, Kf * d, cols, cv, hs);
+    if (!bad.empty()) return fail(bad);
+    NlpBlkDev Kb = {};
+    Kb.K = K; Kb.Kf = Kf;
+    const int rc = guarded(h, [&](Ctx &C) { Kb.y = C.upload(std::vector<int>(labels, labels + N)); return SQPHIP_OK; });
+    if (rc) return rc;
+    return nlp_block_commit(h, blk, kb, (long)N, d, (long)Kf * N, (long)Kf * N, A, cv, hs, weight, shift, Kb, blk_out);
 }
 
 // weight / shift of block blk into the block of values v (of an instance or of a scenario of the queue); NULL: kept
@@ -2088,7 +2153,7 @@ static int nlp_block_put(sqphip_ctx *h, double *v, int32_t blk, const double *we
 {
     return guarded(h, [&](Ctx &C) {
         const Ctx::NlBlock &K = C.nl_blk[blk];
-        h2d(C, v + K.ow, weight, (size_t)K.N); h2d(C, v + K.os, shift, (size_t)K.N);
+        h2d(C, v + K.ow, weight, (size_t)K.N); h2d(C, v + K.os, shift, (size_t)K.nS);
         SQPHIP_HIP_OK(hipStreamSynchronize(C.stream));
         return SQPHIP_OK;
     });

@@ -286,10 +286,10 @@ struct Ctx {
     long nl_ob = 0, nl_oa = 0, nl_op = -1, nl_nargs = 0;
     std::vector<int> h_nl_tptr, h_nl_aptr, h_nl_kind;   // [nterms + 1], [nfac + 1], [nfac]
     std::vector<int> h_nl_lin;                          // the terms of rows 1..num_linear
-    // sqphip_nlp_add_block: dense data blocks behind those segments, W_k [N_k] | S_k [N_k] each (nl_end: doubles in use before
+    // sqphip_nlp_add_block: dense data blocks behind those segments, W_k [N_k] | S_k [N_k] each (S_k [Kf N_k] for a softmax block; nl_end: doubles in use before
     // the padding to even); nl_ws: doubles of workspace per instance (DV::nlw); nl_started: a reset, run or queue has seen the
     // layout, which is final from then on
-    struct NlBlock { long N, ow, os; };
+    struct NlBlock { long N, ow, os, nS; };      // nS: doubles of S (N; Kf N for a softmax block)
     std::vector<NlBlock> nl_blk;
     long nl_end = 0, nl_ws = 0;
     bool nl_started = false;

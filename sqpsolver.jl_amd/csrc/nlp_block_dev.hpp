@@ -3,8 +3,9 @@
 // with a dense N x d design matrix A shared by the batch (d <= 128, up to 4 blocks) and the weights W and shifts S of the
 // instance, which sit behind the other segments of its block of values (NlpBlkDev::ow, os).  Gradient A'(W kappa'),
 // Hessian A' diag(W kappa'') A: a dense fp64 rank-N update, done on the MFMA pipe (v_mfma_f64_16x16x4_f64).
-// nlp_eval calls nlp_block_eval for every block in block order, behind its plan passes and a barrier, with a barrier
-// between two blocks (they may share gradient entries and Hessian slots).  One call, by every thread of the workgroup:
+// nlp_eval's one call for blocks (nlp_blocks_eval, nlp_softmax_dev.hpp) calls nlp_block_eval for every such block in block
+// order, behind the plan passes and a barrier, with a barrier between two blocks (they may share gradient entries and
+// Hessian slots).  One call, by every thread of the workgroup:
 //   1. points: thread i % TPB computes u_i = 0, u_i = fma(A[i][j], x_{col_j}, u_i) for j = 0 .. d - 1 in that order, u_i += S_i
 //      (the rule of sqphip_nlp_attach_affine; A is read through its transpose At [d][N], so the lanes of a wave read
 //      consecutive doubles), then kappa, kappa', kappa'' through nlp_factor -- the menu exists once -- and stores

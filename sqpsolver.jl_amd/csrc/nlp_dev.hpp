@@ -37,6 +37,9 @@
 // the instance's block.  They are evaluated behind the plan passes by one out-of-line call per block (nlp_block_dev.hpp),
 // inside a branch on NlpDev::nblk that is uniform over the launch: a context without a block runs the passes above and
 // nothing else, on the workspace stride NlpDev::ws = 3 nfac it always had.
+// sqphip_nlp_add_softmax_block: multinomial blocks sum_i W_i [log sum_k exp(u_ik) - u_{i, y_i}] count among the same four
+// blocks; nlp_eval's one call for blocks is nlp_blocks_eval (nlp_softmax_dev.hpp), which walks the blocks in block order and
+// hands each to nlp_block_eval or nlp_softmax_eval.
 #pragma once
 #include "ctx.hpp"
 #include "dev_util.hpp"
@@ -50,7 +53,7 @@ enum { NLP_KIND_BITS = 4, NLP_KIND_MASK = (1 << NLP_KIND_BITS) - 1 };     // fke
 enum { NLP_NONE = -(1 << 30), NLP_ARG = (1 << 28) - 1 };     // no factor of a term; the argument bits of a plan entry (nargs <= 2^28)
 
 // a dense data block of the objective (sqphip_nlp_add_block; evaluator: nlp_block_dev.hpp, included below)
-enum { NLP_MAX_BLOCKS = 4, NLP_BLOCK_MAX_D = 128 };
+enum { NLP_MAX_BLOCKS = 4, NLP_BLOCK_MAX_D = 128, NLP_SOFTMAX_MAX_K = 64 };
 
 struct NlpBlkDev {
     int ke, N, d;                         // kind + 16 * (exponent + 32) as NlpDev::fke; points; columns
@@ -60,6 +63,10 @@ struct NlpBlkDev {
     const double *A, *At;                 // [N][d] row-major (Hessian) and its transpose [d][N] (points, gradient)
     const int *col;                       // [d] variable of a column (0-based)
     const int *hs;                        // [d (d + 1) / 2] COO slot of the lower entry (r, c) at r (r + 1) / 2 + c; -1: no Hessian structure
+    // a softmax block (sqphip_nlp_add_softmax_block; nlp_softmax_dev.hpp): K != 0, ke and par unread.  Kf = K or K - 1 classes
+    // carry variables; col [Kf d] and hs over the flat index k d + j; S [Kf][N] at os; wz: P [Kf][N]
+    int K, Kf;
+    const int *y;                         // [N] label of a point, 0 .. K - 1
 };
 
 struct NlpDev {
@@ -180,6 +187,7 @@ static __device__ __forceinline__ void nlp_factor(int ke, double a, double u, do
 
 }  // namespace sqphip
 #include "nlp_block_dev.hpp"
+#include "nlp_softmax_dev.hpp"
 namespace sqphip {
 
 // the acopf_eval signature; any of f_out, grad, gv, jv, hv may be null.  Called by every thread of the workgroup.
@@ -276,14 +284,8 @@ static __device__ __forceinline__ void nlp_eval(const DV &d, int inst, const dou
             hv[s_] = s;
         }
     }
-    // dense data blocks, in block order; a barrier in front of each: the plan passes above and an earlier block wrote
-    // f, grad and hv entries that this block adds to from other threads
-    if (q.nblk != 0)
-        #pragma unroll 1
-        for (int k = 0; k < q.nblk; ++k) {
-            __syncthreads();
-            nlp_block_eval(&q.blk[k], val, w, w + 3 * nf, x, sigma, f_out, grad, hv);
-        }
+    // dense data blocks of either sort, in block order behind a barrier each: one out-of-line call (nlp_softmax_dev.hpp)
+    if (q.nblk != 0) nlp_blocks_eval(q.blk, q.nblk, val, w, w + 3 * nf, x, sigma, f_out, grad, hv);
 }
 
 }  // namespace sqphip

@@ -530,7 +530,20 @@ class Context:
     # ---- a sparse factorable NLP (nlp_terms.py; csrc/nlp_dev.hpp nlp_eval)
     def nlp_add_block(self, b) -> int:
         """One dense data block of the objective (sqphip_nlp_add_block; b: nlp_terms.NlpBlock); before the first sqp_reset,
-        sqp_run or nlp_stream_begin.  Returns its number."""
+        sqp_run or nlp_stream_begin.  Returns its number.  An nlp_terms.NlpSoftmaxBlock goes through
+        sqphip_nlp_add_softmax_block."""
+        from .nlp_terms import NlpSoftmaxBlock
+        if isinstance(b, NlpSoftmaxBlock):
+            if not hasattr(self.L, "sqphip_nlp_add_softmax_block"):
+                raise SqpHipError("libsqphip.so lacks sqphip_nlp_add_softmax_block: rebuild it")
+            A = _f(np.atleast_2d(b.A))
+            out = C.c_int32(-1)
+            self._ck(self.L.sqphip_nlp_add_softmax_block(self.h, A.shape[0], A.shape[1], int(b.K), int(bool(b.pinned)),
+                                                         _l(np.ascontiguousarray(b.cols, dtype=np.int64).ravel()), _d(A),
+                                                         _i(np.ascontiguousarray(b.labels, dtype=np.int32)),
+                                                         _d(None if b.shift is None else _f(b.shift).ravel()),
+                                                         _d(None if b.weight is None else _f(b.weight)), C.byref(out)))
+            return out.value
         if not hasattr(self.L, "sqphip_nlp_add_block"):
             raise SqpHipError("libsqphip.so lacks sqphip_nlp_add_block: rebuild it")
         A = _f(np.atleast_2d(b.A))

@@ -37,7 +37,10 @@ plain affine factors.  Twice inside one factor stays an error.  SQRT and POWR ne
     logistic_folds       the k training folds of a dataset as k logistic models of one structure
     NlpBlock             a dense data block of the objective, sum_i w_i kappa(A_i'x_cols + b_i) (sqphip_nlp_add_block): A, the
                          columns and the kind are shared by the batch, the weights and shifts belong to the instance
+    NlpSoftmaxBlock      a multinomial (softmax) data block, sum_i w_i [log sum_k exp(u_ik) - u_{i, y_i}] with
+                         u_ik = A_i'x_cols[k] + shift_ki (sqphip_nlp_add_softmax_block); it sits in NlpTerms.blocks beside NlpBlock
     block_eval           value, gradient and dense Hessian of the blocks of a problem in numpy
+    multinomial_block_model  ridge-regularised K-class logistic regression as one softmax block plus terms
     logistic_block_model, poisson_block_model, least_squares_block_model     data fits of any size as one block plus terms
     fold_weights         the k training folds of N points as 0 / 1 weight vectors (logistic_fold_indices)
     from_qcqp            a Qcqp (qcqp.py) restated as terms
@@ -56,6 +59,7 @@ MAX_FACTORS = 8
 MAX_ARGS = 8
 MAX_BLOCKS = 4
 MAX_BLOCK_COLS = 128
+MAX_SOFTMAX_CLASSES = 64
 
 
 @dataclasses.dataclass
@@ -76,6 +80,46 @@ class NlpBlock:
         N = self.A.shape[0]
         self.shift = np.zeros(N) if self.shift is None else _f64(self.shift)
         self.weight = np.ones(N) if self.weight is None else _f64(self.weight)
+
+
+@dataclasses.dataclass
+class NlpSoftmaxBlock:
+    """sum_{i < N} weight_i [log sum_{k < K} exp(u_ik) - u_{i, labels_i}], u_ik = sum_j A[i, j] x_{cols[k, j]} + shift[k, i], in the
+    objective: cols [Kf, d] distinct 1-based variables in any order (Kf d <= 128), A [N, d], labels [N] in 0..K-1, 2 <= K <= 64.
+    pinned: the last class has no variables and u_{i, K-1} = 0, Kf = K - 1; else Kf = K.  shift [Kf, N] None: zeros, weight [N]
+    None: ones."""
+    cols: np.ndarray
+    A: np.ndarray
+    labels: np.ndarray
+    K: int
+    pinned: bool = True
+    shift: np.ndarray | None = None
+    weight: np.ndarray | None = None
+
+    def __post_init__(self):
+        self.A = _f64(np.atleast_2d(self.A))
+        N, d = self.A.shape
+        self.K, self.pinned = int(self.K), bool(self.pinned)
+        if not 2 <= self.K <= MAX_SOFTMAX_CLASSES:
+            raise ValueError(f"K = {self.K} classes (2..{MAX_SOFTMAX_CLASSES})")
+        Kf = self.Kf
+        if Kf * d > MAX_BLOCK_COLS:
+            raise ValueError(f"Kf d = {Kf} x {d} columns (at most {MAX_BLOCK_COLS})")
+        self.cols = _i64(self.cols)
+        if self.cols.size != Kf * d:
+            raise ValueError(f"cols holds {self.cols.size} variables, not Kf d = {Kf} x {d}")
+        self.cols = self.cols.reshape(Kf, d)
+        if len(np.unique(self.cols)) != Kf * d:
+            raise ValueError("a variable sits in two columns of the block")
+        self.labels = np.ascontiguousarray(self.labels, dtype=np.int32)
+        if self.labels.shape != (N,) or (N and (self.labels.min() < 0 or self.labels.max() >= self.K)):
+            raise ValueError(f"labels: {N} values in 0..{self.K - 1}")
+        self.shift = np.zeros((Kf, N)) if self.shift is None else _f64(self.shift).reshape(Kf, N)
+        self.weight = np.ones(N) if self.weight is None else _f64(self.weight)
+
+    @property
+    def Kf(self) -> int:
+        return self.K - 1 if self.pinned else self.K
 
 
 @dataclasses.dataclass
@@ -104,7 +148,7 @@ class NlpTerms:
     fpar: np.ndarray | None = None     # [nfac] real exponent of a POWR factor (0 elsewhere); None: no POWR factor
     general: bool = False              # written for sqphip_nlp_attach_general (make_nlp_terms: needs_general); False: a model
                                        # of the older calls, which keep refusing what they refuse
-    blocks: list = dataclasses.field(default_factory=list)     # NlpBlock: dense data blocks of the objective (at most 4)
+    blocks: list = dataclasses.field(default_factory=list)     # NlpBlock, NlpSoftmaxBlock: dense data blocks of the objective (at most 4)
 
     @property
     def affine(self) -> bool:
@@ -174,6 +218,11 @@ def make_nlp_terms(n, m, num_linear, terms, g0=None, f0=0.0, xL=None, xU=None, g
                  full(xL, n, -inf), full(xU, n, inf), full(gL, m, -inf), full(gU, m, inf), full(x0, n, 0.0), *extra)
     p.general = needs_general(p)
     p.blocks = list(blocks or [])
+    if len(p.blocks) > MAX_BLOCKS:
+        raise ValueError(f"{len(p.blocks)} blocks (at most {MAX_BLOCKS})")
+    for k, b in enumerate(p.blocks):
+        if isinstance(b, NlpSoftmaxBlock) and (b.cols.min() < 1 or b.cols.max() > n):
+            raise ValueError(f"block {k + 1}: a column outside 1..{n}")
     return p
 
 
@@ -206,8 +255,9 @@ def nlp_terms_layout(p: NlpTerms) -> NlpTermsLayout:
             a, b = a[keep], b[keep]
             hk.append((np.minimum(v[a], v[b]) - 1) * n + np.maximum(v[a], v[b]) - 1)      # column-major key of the lower entry
     for b in getattr(p, "blocks", []):
-        a, c = np.tril_indices(len(b.cols))
-        hk.append((np.minimum(b.cols[a], b.cols[c]) - 1) * n + np.maximum(b.cols[a], b.cols[c]) - 1)
+        cols = np.ravel(b.cols)                       # (a softmax block: every pair of its Kf d columns)
+        a, c = np.tril_indices(len(cols))
+        hk.append((np.minimum(cols[a], cols[c]) - 1) * n + np.maximum(cols[a], cols[c]) - 1)
     hkey = np.unique(np.concatenate(hk)) if hk else np.zeros(0, np.int64)
     return NlpTermsLayout(n, p.m, p.num_linear, jkey // n + 1, jkey % n + 1, hkey % n + 1, hkey // n + 1,
                           p.xL.copy(), p.xU.copy(), p.gL.copy(), p.gU.copy(), p.x0.copy())
@@ -507,12 +557,44 @@ def _kappa3(kind, e, par, u):
     raise ValueError(f"unknown kind {kind}")
 
 
+def _softmax_eval(b: NlpSoftmaxBlock, x):
+    """(f, grad [Kf d], H [Kf d, Kf d]) of a softmax block over the flat index k d + j.  The logits are shifted by their
+    maximum (the pinned class enters with 0), so any finite logits give finite results; the Hessian is formed as
+    A'diag(w p_k) A on the class diagonal minus A'diag(w p_k p_l) A everywhere, as the device forms it."""
+    Kf, d = b.cols.shape
+    N = b.A.shape[0]
+    u = np.stack([b.A @ x[b.cols[k] - 1] + b.shift[k] for k in range(Kf)])          # [Kf, N]
+    if b.pinned:
+        u = np.vstack([u, np.zeros(N)])
+    m = u.max(axis=0)
+    e = np.exp(u - m)
+    s = e.sum(axis=0)
+    P = (e / s)[:Kf]
+    f = float(b.weight @ ((m + np.log(s)) - u[b.labels, np.arange(N)]))
+    Y = (b.labels[None, :] == np.arange(Kf)[:, None]).astype(float)
+    g = ((b.weight * (P - Y)) @ b.A).ravel()
+    H = np.zeros((Kf * d, Kf * d))
+    for k in range(Kf):
+        wp = b.weight * P[k]
+        for l in range(Kf):
+            H[k * d:(k + 1) * d, l * d:(l + 1) * d] = -(b.A.T @ ((wp * P[l])[:, None] * b.A))
+        H[k * d:(k + 1) * d, k * d:(k + 1) * d] += b.A.T @ (wp[:, None] * b.A)
+    return f, g, H
+
+
 def block_eval(p: NlpTerms, x, blocks=None):
     """(f, grad [n], H [n, n]) of the blocks of p at x: sum_i w_i kappa(u_i), A'(w kappa'), A' diag(w kappa'') A scattered to
     the blocks' columns."""
     x = _f64(x)
     f, g, H = 0.0, np.zeros(p.n), np.zeros((p.n, p.n))
     for b in (p.blocks if blocks is None else blocks):
+        if isinstance(b, NlpSoftmaxBlock):
+            fb, gb, Hb = _softmax_eval(b, x)
+            c = b.cols.ravel() - 1
+            f += fb
+            np.add.at(g, c, gb)
+            H[np.ix_(c, c)] += Hb
+            continue
         c = b.cols - 1
         k0, k1, k2 = _kappa3(b.kind, b.exp, b.par, b.A @ x[c] + b.shift)
         f += float(b.weight @ k0)
@@ -541,6 +623,19 @@ def logistic_block_model(X, y, reg, weight=None) -> NlpTerms:
     X, y = np.atleast_2d(_f64(X)), _f64(y)
     N, n = X.shape
     blk = NlpBlock(SOFTPLUS, np.arange(1, n + 1), (1.0 - 2.0 * y)[:, None] * X, None, weight)
+    return make_nlp_terms(n, 0, 0, _ridge(n, reg), xL=np.full(n, -50.0), xU=np.full(n, 50.0), x0=np.zeros(n), blocks=[blk])
+
+
+def multinomial_block_model(X, y, K, reg, pinned=True, weight=None) -> NlpTerms:
+    """Ridge-regularised K-class logistic regression, sum_i w_i [log sum_k exp(X_i'b_k) - X_i'b_{y_i}] + reg / 2 |b|^2, as one
+    softmax block on the variables b_k = x[k d : (k + 1) d] (class-major) plus the ridge terms.  pinned: b_{K-1} = 0, the
+    identifiable form.  The folds or resamples of one dataset differ in the weights only (fold_weights).  -50 <= b <= 50,
+    from b = 0."""
+    X = np.atleast_2d(_f64(X))
+    N, d = X.shape
+    Kf = int(K) - 1 if pinned else int(K)
+    n = Kf * d
+    blk = NlpSoftmaxBlock(np.arange(1, n + 1).reshape(Kf, d), X, y, K, pinned, None, weight)
     return make_nlp_terms(n, 0, 0, _ridge(n, reg), xL=np.full(n, -50.0), xU=np.full(n, 50.0), x0=np.zeros(n), blocks=[blk])
 
 
