@@ -2,16 +2,12 @@
 // Builds the shared sparsity structure once on the host (what `sparse(I,J,V)` does in
 // /root/reference/src/algorithms/sqp_trust_region.jl:47-48,56-57 plus the symmetric mirroring of
 // sqp.jl:96-101), lays the batch out in HBM and forwards to the kernels.
-#include "ctx.hpp"
-#include "qcqp_dev.hpp"
-#include "nlp_dev.hpp"
+#include "api_util.hpp"
 #include <algorithm>
-#include <array>
 #include <chrono>
 #include <cmath>
 #include <cstring>
 #include <tuple>
-#include <unordered_map>
 
 using namespace sqphip;
 
@@ -62,29 +58,6 @@ Pattern build_pattern(int64_t ncols, int64_t nnz, const int64_t *row, const int6
     return P;
 }
 
-template <class F> int guarded(sqphip_ctx *h, F &&f)
-{
-    try {
-        SQPHIP_HIP_OK(hipSetDevice(h->c.opt.device));
-        return f(h->c);
-    } catch (const std::string &e) {
-        h->c.err = e;
-        return SQPHIP_EHIP;
-    } catch (const std::bad_alloc &) {
-        h->c.err = "out of host memory";
-        return SQPHIP_ENOMEM;
-    }
-}
-
-void h2d(Ctx &C, double *dst, const double *src, size_t k)
-{
-    if (src && k) SQPHIP_HIP_OK(hipMemcpyAsync(dst, src, sizeof(double) * k, hipMemcpyHostToDevice, C.stream));
-}
-void d2h(Ctx &C, double *dst, const double *src, size_t k)
-{
-    if (dst && k) SQPHIP_HIP_OK(hipMemcpyAsync(dst, src, sizeof(double) * k, hipMemcpyDeviceToHost, C.stream));
-}
-
 // the device view of instances [i0, i0 + Bg): every per-instance array advanced to the group's first instance, so that
 // the kernels see an ordinary (smaller) batch.  Shared structure arrays stay as they are.
 DV group_view(const DV &d, int i0, int Bg, int g)
@@ -117,8 +90,10 @@ DV group_view(const DV &d, int i0, int Bg, int g)
     return v;
 }
 
-// (re)build the lanes from the owner's current device view (after sqphip_create and after sqphip_acopf_attach)
-void make_lanes(Ctx &C)
+}  // namespace
+
+// (re)build the lanes from the owner's current device view (after sqphip_create and after every *_attach)
+void sqphip::make_lanes(Ctx &C)
 {
     for (const auto &L : C.lanes)           // (the launch census of the groups being replaced stays with the context)
         for (int k = 0; k < MFK_COUNT; ++k) C.mf_census[k] += L->mf_census[k];
@@ -140,12 +115,12 @@ void make_lanes(Ctx &C)
         const int lo = (int)((long)C.d.B * g / G), hi = (int)((long)C.d.B * (g + 1) / G);
         std::unique_ptr<Ctx> L(new Ctx());
         L->is_lane = true;
-        L->opt = C.opt; L->n = C.n; L->m = C.m; L->acopf_attached = C.acopf_attached;
+        L->opt = C.opt; L->n = C.n; L->m = C.m; L->evaluator_attached = C.evaluator_attached;
         L->mfp_ = C.mfp_;
         L->trans_period = C.trans_period; L->trans_ride = C.trans_ride; L->refine_slot = C.refine_slot; L->refine_period = C.refine_period; L->mf_big_lds = C.mf_big_lds; L->post_split = C.post_split; L->side_mode = C.side_mode; L->spec_tail = C.spec_tail; L->spec_mode0 = C.spec_mode0;
         L->d = group_view(C.d, lo, hi - lo, g);
-        if (L->d.qcv) L->d.qcv += (long)lo * C.qc_nv;
-        if (L->d.nlv) { L->d.nlv += (long)lo * C.nl_nv; L->d.nlw += (long)lo * C.nl_ws; }
+        if (L->d.qcv) L->d.qcv += (long)lo * C.qc.nv;
+        if (L->d.nlv) { L->d.nlv += (long)lo * C.nl.nv; L->d.nlw += (long)lo * C.nl.ws; }
         // the first group runs on the owner's stream (idle during sqphip_sqp_run): HIP maps streams onto four hardware
         // queues by default, and a fifth stream would share one -- measured: 3131 QP/s with five streams against 5216
         // with four (or with GPU_MAX_HW_QUEUES=8)
@@ -170,6 +145,8 @@ void make_lanes(Ctx &C)
         C.lanes.push_back(std::move(L));
     }
 }
+
+namespace {
 
 __global__ void k_qp_request(DV d, int inst, int mode, double delta, double mu_pen)
 {
@@ -1201,7 +1178,7 @@ extern "C" int sqphip_acopf_armijo(sqphip_ctx *h, int32_t inst, const double *x,
                                    double D, double eta, double tau, double min_alpha, int32_t feasibility_restoration,
                                    double *alpha, int32_t *is_valid, int32_t *n_eval)
 {
-    if (!h || !h->c.acopf_attached || inst < 0 || inst >= h->c.d.B || !x || !p || !alpha || !is_valid) return SQPHIP_EINVAL;
+    if (!h || !h->c.evaluator_attached || inst < 0 || inst >= h->c.d.B || !x || !p || !alpha || !is_valid) return SQPHIP_EINVAL;
     if (!(tau > 0.0 && tau < 1.0)) return SQPHIP_EINVAL;        // the loop must terminate
     return guarded(h, [&](Ctx &C) {
         DV &d = C.d;
@@ -1272,933 +1249,10 @@ extern "C" int sqphip_compute_mu_rule(int32_t rule, int64_t iter, double rho, do
     return SQPHIP_OK;
 }
 
-// ---- ACOPF evaluator + batched SQP -----------------------------------------------------------------
-// structure counts of the two layouts (acopf_synth.py acopf_layout / acr_layout) without shunts
-static int acopf_nnzj(int acr, int nb, int ng, int nl, int ndc)
-{
-    const int nbal = 2 * nl + ng + 2 * ndc;
-    return acr ? 1 + 2 * nbal + 4 * nb + 24 * nl + 2 * ndc : 32 * nl + 2 * ng + 1 + 6 * ndc;
-}
-static int acopf_nnzh(int acr, int nb, int ng, int nl) { return acr ? ng + 28 * nl + 4 * nb : ng + 44 * nl; }
-// ... and of the W-space layout (acwr_layout): the shunt entries are part of the structure
-static int acwr_n(int nb, int nbp, int ng, int nl) { return 3 * nb + 2 * nbp + 2 * ng + 4 * nl; }
-static int acwr_m(int nb, int nbp, int nl) { return 1 + 3 * nb + 4 * nbp + 6 * nl; }
-static int acwr_nnzj(int nb, int nbp, int ng, int nl, int ndc)
-{
-    const int nbal = 2 * nl + ng + 2 * ndc;
-    return 1 + 2 * nbal + 2 * nb + 4 * nbp + 16 * nl + 3 * nb + 10 * nbp + 4 * nl + 2 * ndc;
-}
-static int acwr_nnzh(int nb, int nbp, int ng, int nl) { return ng + 4 * nl + 2 * nb + 4 * nbp; }
-
-static int acopf_attach_impl(sqphip_ctx *h, int acr, int32_t nb, int32_t ng, int32_t nl, const int32_t *f_bus,
-                             const int32_t *t_bus, const int32_t *gen_bus, const int32_t *bal_ptr,
-                             const int32_t *bal_colP, const int32_t *bal_colQ, const double *bal_coef,
-                             int32_t ref_bus)
-{
-    if (!h || nb <= 0 || ng <= 0 || nl <= 0) return SQPHIP_EINVAL;
-    if (!f_bus || !t_bus || !gen_bus || !bal_ptr || !bal_colP || !bal_colQ || !bal_coef) return SQPHIP_EINVAL;
-    Ctx &C0 = h->c;
-    // HVDC lines add 4 variables, 1 row, 2 balance incidences (= 4 Jacobian entries) and 2 loss-row entries each
-    const int n_ac = 2 * nb + 2 * ng + 4 * nl, m_ac = acr ? 1 + 4 * nb + 6 * nl : 1 + 2 * nb + 8 * nl;
-    if (C0.d.n < n_ac || (C0.d.n - n_ac) % 4 != 0) return SQPHIP_EINVAL;
-    const int ndc = (C0.d.n - n_ac) / 4;
-    if (C0.d.m != m_ac + ndc) return SQPHIP_EINVAL;
-    const int nbal = bal_ptr[nb];
-    // (a structure with bus shunts has 2 (polar) / 4 (rectangular) more Jacobian and 1 / 2 more Hessian entries per
-    // shunted bus at the end of the lists; sqphip_acopf_set_shunts checks the exact counts)
-    const int extraJ = C0.d.nnzj_coo - acopf_nnzj(acr, nb, ng, nl, ndc), extraH = C0.d.nnzh_coo - acopf_nnzh(acr, nb, ng, nl);
-    if (extraJ < 0 || extraJ != 2 * extraH || extraH > (acr ? 2 * nb : nb) || nbal != 2 * nl + ng + 2 * ndc) return SQPHIP_EINVAL;
-    for (int l = 0; l < nl; ++l)
-        if (f_bus[l] < 0 || f_bus[l] >= nb || t_bus[l] < 0 || t_bus[l] >= nb) return SQPHIP_EINVAL;
-    for (int k = 0; k < nbal; ++k)
-        if (bal_colP[k] < 0 || bal_colP[k] >= C0.d.n || bal_colQ[k] < 0 || bal_colQ[k] >= C0.d.n) return SQPHIP_EINVAL;
-    if (ref_bus < 0 || ref_bus >= nb) return SQPHIP_EINVAL;
-    return guarded(h, [&](Ctx &C) {
-        DV &d = C.d;
-        d.nb = nb; d.ng = ng; d.nl = nl; d.ref_bus = ref_bus; d.acr = acr; d.acwr = 0;
-        d.ndc = ndc;
-        d.dc_loss1 = C.upload(std::vector<double>(ndc > 0 ? ndc : 1, 0.0));   // sqphip_acopf_set_dclines overrides
-        d.f_bus = C.upload(std::vector<int>(f_bus, f_bus + nl));
-        d.t_bus = C.upload(std::vector<int>(t_bus, t_bus + nl));
-        d.gen_bus = C.upload(std::vector<int>(gen_bus, gen_bus + ng));
-        d.bal_ptr = C.upload(std::vector<int>(bal_ptr, bal_ptr + nb + 1));
-        d.bal_colP = C.upload(std::vector<int>(bal_colP, bal_colP + nbal));
-        d.bal_colQ = C.upload(std::vector<int>(bal_colQ, bal_colQ + nbal));
-        d.bal_coef = C.upload(std::vector<double>(bal_coef, bal_coef + nbal));
-        d.br_ohm = C.dalloc<double>((size_t)d.B * nl * 12);
-        d.c2 = C.dalloc<double>((size_t)d.B * ng); d.c1 = C.dalloc<double>((size_t)d.B * ng);
-        SQPHIP_HIP_OK(hipStreamSynchronize(C.stream));
-        C.acopf_attached = true;
-        make_lanes(C);
-        return SQPHIP_OK;
-    });
-}
-
-extern "C" int sqphip_acopf_attach(sqphip_ctx *h, int32_t nb, int32_t ng, int32_t nl, const int32_t *f_bus,
-                                   const int32_t *t_bus, const int32_t *gen_bus, const int32_t *bal_ptr,
-                                   const int32_t *bal_colP, const int32_t *bal_colQ, const double *bal_coef,
-                                   int32_t ref_bus)
-{
-    return acopf_attach_impl(h, 0, nb, ng, nl, f_bus, t_bus, gen_bus, bal_ptr, bal_colP, bal_colQ, bal_coef, ref_bus);
-}
-
-extern "C" int sqphip_acopf_attach_acr(sqphip_ctx *h, int32_t nb, int32_t ng, int32_t nl, const int32_t *f_bus,
-                                       const int32_t *t_bus, const int32_t *gen_bus, const int32_t *bal_ptr,
-                                       const int32_t *bal_colP, const int32_t *bal_colQ, const double *bal_coef,
-                                       int32_t ref_bus)
-{
-    return acopf_attach_impl(h, 1, nb, ng, nl, f_bus, t_bus, gen_bus, bal_ptr, bal_colP, bal_colQ, bal_coef, ref_bus);
-}
-
-extern "C" int sqphip_acopf_attach_acwr(sqphip_ctx *h, int32_t nb, int32_t ng, int32_t nl, const int32_t *f_bus,
-                                        const int32_t *t_bus, const int32_t *gen_bus, const int32_t *bal_ptr,
-                                        const int32_t *bal_colP, const int32_t *bal_colQ, const double *bal_coef,
-                                        int32_t ref_bus, int32_t nbp, const int32_t *bp_i, const int32_t *bp_j,
-                                        const int32_t *br_bp, const double *br_sig, const double *bp_tmin,
-                                        const double *bp_tmax)
-{
-    if (!h || nb <= 0 || ng <= 0 || nl <= 0 || nbp <= 0 || nbp > nl) return SQPHIP_EINVAL;
-    if (!f_bus || !t_bus || !gen_bus || !bal_ptr || !bal_colP || !bal_colQ || !bal_coef) return SQPHIP_EINVAL;
-    if (!bp_i || !bp_j || !br_bp || !br_sig || !bp_tmin || !bp_tmax) return SQPHIP_EINVAL;
-    Ctx &C0 = h->c;
-    const int n_ac = acwr_n(nb, nbp, ng, nl);
-    if (C0.d.n < n_ac || (C0.d.n - n_ac) % 4 != 0) return SQPHIP_EINVAL;
-    const int ndc = (C0.d.n - n_ac) / 4;
-    if (C0.d.m != acwr_m(nb, nbp, nl) + ndc) return SQPHIP_EINVAL;
-    const int nbal = bal_ptr[nb];
-    if (C0.d.nnzj_coo != acwr_nnzj(nb, nbp, ng, nl, ndc) || C0.d.nnzh_coo != acwr_nnzh(nb, nbp, ng, nl) ||
-        nbal != 2 * nl + ng + 2 * ndc) return SQPHIP_EINVAL;
-    for (int l = 0; l < nl; ++l)
-        if (f_bus[l] < 0 || f_bus[l] >= nb || t_bus[l] < 0 || t_bus[l] >= nb || br_bp[l] < 0 || br_bp[l] >= nbp ||
-            !(br_sig[l] == 1.0 || br_sig[l] == -1.0)) return SQPHIP_EINVAL;
-    for (int k = 0; k < nbp; ++k)
-        if (bp_i[k] < 0 || bp_j[k] >= nb || bp_i[k] >= bp_j[k]) return SQPHIP_EINVAL;
-    for (int k = 0; k < nbal; ++k)
-        if (bal_colP[k] < 0 || bal_colP[k] >= C0.d.n || bal_colQ[k] < 0 || bal_colQ[k] >= C0.d.n) return SQPHIP_EINVAL;
-    if (ref_bus < 0 || ref_bus >= nb) return SQPHIP_EINVAL;
-    return guarded(h, [&](Ctx &C) {
-        DV &d = C.d;
-        d.nb = nb; d.ng = ng; d.nl = nl; d.ref_bus = ref_bus; d.acr = 0; d.acwr = 1; d.nbp = nbp;
-        d.ndc = ndc;
-        d.dc_loss1 = C.upload(std::vector<double>(ndc > 0 ? ndc : 1, 0.0));
-        d.f_bus = C.upload(std::vector<int>(f_bus, f_bus + nl));
-        d.t_bus = C.upload(std::vector<int>(t_bus, t_bus + nl));
-        d.gen_bus = C.upload(std::vector<int>(gen_bus, gen_bus + ng));
-        d.bal_ptr = C.upload(std::vector<int>(bal_ptr, bal_ptr + nb + 1));
-        d.bal_colP = C.upload(std::vector<int>(bal_colP, bal_colP + nbal));
-        d.bal_colQ = C.upload(std::vector<int>(bal_colQ, bal_colQ + nbal));
-        d.bal_coef = C.upload(std::vector<double>(bal_coef, bal_coef + nbal));
-        d.bp_i = C.upload(std::vector<int>(bp_i, bp_i + nbp)); d.bp_j = C.upload(std::vector<int>(bp_j, bp_j + nbp));
-        d.br_bp = C.upload(std::vector<int>(br_bp, br_bp + nl));
-        d.br_sig = C.upload(std::vector<double>(br_sig, br_sig + nl));
-        d.bp_tmin = C.upload(std::vector<double>(bp_tmin, bp_tmin + nbp));
-        d.bp_tmax = C.upload(std::vector<double>(bp_tmax, bp_tmax + nbp));
-        d.br_ohm = C.dalloc<double>((size_t)d.B * nl * 12);
-        d.c2 = C.dalloc<double>((size_t)d.B * ng); d.c1 = C.dalloc<double>((size_t)d.B * ng);
-        SQPHIP_HIP_OK(hipStreamSynchronize(C.stream));
-        C.acopf_attached = true;
-        make_lanes(C);
-        return SQPHIP_OK;
-    });
-}
-
-// The tables of sqphip_acopf_set_* and of the ACOPF scenario queue (sqphip_sqp_stream_begin / _set) exist on a context
-// attached with one of the three ACOPF forms only: on a dense, QCQP or factorable-NLP context those entry points are
-// refused here, on the host, before anything touches the device.  Returns 0 on an ACOPF (or unattached) context.
-static int acopf_only(sqphip_ctx *h, const char *fn)
-{
-    if (!h) return 0;
-    const DV &d = h->c.d;
-    const char *what = d.qc ? "a QCQP context (sqphip_qcqp_attach; use sqphip_qcqp_set_instance, sqphip_qcqp_stream_begin / _set)"
-                     : d.nlp ? "an NLP context (sqphip_nlp_attach; use sqphip_nlp_set_instance, sqphip_nlp_stream_begin / _set)"
-                     : d.dense_nlp ? "a dense context (sqphip_dense_attach; use sqphip_dense_set_instance)" : nullptr;
-    if (!what) return 0;
-    h->c.err = std::string(fn) + ": not available on " + what;
-    return SQPHIP_EINVAL;
-}
-
-extern "C" int sqphip_acopf_set_shunts(sqphip_ctx *h, int32_t nsh, const int32_t *sh_bus, const double *gs,
-                                       const double *bs)
-{
-    if (acopf_only(h, "sqphip_acopf_set_shunts")) return SQPHIP_EINVAL;
-    if (!h || !h->c.acopf_attached || nsh < 0) return SQPHIP_EINVAL;
-    Ctx &C0 = h->c;
-    const int nl = C0.d.nl, ng = C0.d.ng, nb = C0.d.nb;
-    const int acr = C0.d.acr;
-    if (!C0.d.acwr) {                    // (the W-space structure carries the shunt entries of every bus already)
-        if (C0.d.nnzj_coo != acopf_nnzj(acr, nb, ng, nl, C0.d.ndc) + (acr ? 4 : 2) * nsh ||
-            C0.d.nnzh_coo != acopf_nnzh(acr, nb, ng, nl) + (acr ? 2 : 1) * nsh) return SQPHIP_EINVAL;
-        if (nsh > 0 && C0.d.nlin != (acr ? 1 : 2 * nl + 1)) return SQPHIP_EINVAL; // balance rows must not be declared linear
-    }
-    std::vector<int> of(nb, -1);
-    for (int s = 0; s < nsh; ++s) {
-        if (sh_bus[s] < 0 || sh_bus[s] >= nb || of[sh_bus[s]] >= 0) return SQPHIP_EINVAL;
-        of[sh_bus[s]] = s;
-    }
-    return guarded(h, [&](Ctx &C) {
-        DV &d = C.d;
-        d.nsh = nsh;
-        d.sh_bus = C.upload(std::vector<int>(sh_bus, sh_bus + nsh));
-        d.sh_of_bus = C.upload(of);
-        d.sh_gs = C.upload(std::vector<double>(gs, gs + nsh));
-        d.sh_bs = C.upload(std::vector<double>(bs, bs + nsh));
-        SQPHIP_HIP_OK(hipStreamSynchronize(C.stream));
-        make_lanes(C);
-        return SQPHIP_OK;
-    });
-}
-
-extern "C" int sqphip_acopf_set_dclines(sqphip_ctx *h, int32_t ndc, const double *loss1)
-{
-    if (acopf_only(h, "sqphip_acopf_set_dclines")) return SQPHIP_EINVAL;
-    if (!h || !h->c.acopf_attached || ndc != h->c.d.ndc || (ndc > 0 && !loss1)) return SQPHIP_EINVAL;
-    if (ndc == 0) return SQPHIP_OK;
-    return guarded(h, [&](Ctx &C) {
-        C.d.dc_loss1 = C.upload(std::vector<double>(loss1, loss1 + ndc));
-        SQPHIP_HIP_OK(hipStreamSynchronize(C.stream));
-        make_lanes(C);
-        return SQPHIP_OK;
-    });
-}
-
-extern "C" int sqphip_acopf_set_instance(sqphip_ctx *h, int32_t inst, const double *ohm, const double *c2,
-                                         const double *c1, const double *x0)
-{
-    if (acopf_only(h, "sqphip_acopf_set_instance")) return SQPHIP_EINVAL;
-    if (!h || !h->c.acopf_attached || inst < 0 || inst >= h->c.d.B) return SQPHIP_EINVAL;
-    return guarded(h, [&](Ctx &C) {
-        DV &d = C.d;
-        h2d(C, d.br_ohm + (size_t)inst * d.nl * 12, ohm, (size_t)d.nl * 12);
-        h2d(C, d.c2 + (size_t)inst * d.ng, c2, d.ng); h2d(C, d.c1 + (size_t)inst * d.ng, c1, d.ng);
-        h2d(C, d.x0 + (size_t)inst * d.n, x0, d.n);
-        SQPHIP_HIP_OK(hipStreamSynchronize(C.stream));
-        return SQPHIP_OK;
-    });
-}
-
-// ---- the synthetic dense-Hessian NLP (acopf_dev.hpp dense_eval): structure as sqpsolver.jl_amd/dense_synth.py lays it out
-extern "C" int sqphip_dense_attach(sqphip_ctx *h, const double *Q, const double *A, double kappa)
-{
-    if (!h || !Q || !A || !(kappa >= 0.0)) return SQPHIP_EINVAL;
-    Ctx &C0 = h->c;
-    const long n = C0.d.n, m = C0.d.m;
-    if (C0.d.nnzj_coo != m * n || C0.d.nnzh_coo != n * (n + 1) / 2 || C0.d.nlin != m) return SQPHIP_EINVAL;
-    return guarded(h, [&](Ctx &C) {
-        DV &d = C.d;
-        double *q = C.dalloc<double>((size_t)(n * n)), *a = C.dalloc<double>((size_t)(m * n));
-        h2d(C, q, Q, (size_t)(n * n)); h2d(C, a, A, (size_t)(m * n));
-        d.dnQ = q; d.dnA = a; d.dn_kappa = kappa;
-        d.dnc = C.dalloc<double>((size_t)d.B * n);
-        d.dense_nlp = 1;
-        SQPHIP_HIP_OK(hipStreamSynchronize(C.stream));
-        C.acopf_attached = true;           // (the batched run! has its device callbacks)
-        make_lanes(C);
-        return SQPHIP_OK;
-    });
-}
-
-extern "C" int sqphip_dense_set_instance(sqphip_ctx *h, int32_t inst, const double *c, const double *x0)
-{
-    if (!h || !h->c.d.dense_nlp || inst < 0 || inst >= h->c.d.B || !c || !x0) return SQPHIP_EINVAL;
-    return guarded(h, [&](Ctx &C) {
-        DV &d = C.d;
-        h2d(C, d.dnc + (size_t)inst * d.n, c, d.n);
-        h2d(C, d.x0 + (size_t)inst * d.n, x0, d.n);
-        SQPHIP_HIP_OK(hipStreamSynchronize(C.stream));
-        return SQPHIP_OK;
-    });
-}
-
-// ---- a general sparse QCQP (qcqp_dev.hpp qcqp_eval): the gather plans are built here, once, from the terms and the COO
-// structures of sqphip_create
-static int qcqp_fail(sqphip_ctx *h, const std::string &msg)
-{
-    h->c.err = "sqphip_qcqp_attach: " + msg;
-    return SQPHIP_EINVAL;
-}
-
-static std::string qcqp_term(const char *kind, int64_t t, int64_t a, int64_t b, int64_t c = 0)
-{
-    std::string s = std::string(kind) + " term " + std::to_string(t) + " (" + std::to_string(a) + ", " + std::to_string(b);
-    if (c) s += ", " + std::to_string(c);
-    return s + ")";
-}
-
-// a gather plan: (owner, value index, variable or row) entries in the order they were produced -> CSR by owner, the
-// entries of one owner kept in that order
-struct PlanCsr {
-    std::vector<std::array<int, 3>> ent;
-    void finish(int owners, std::vector<int> &ptr, std::vector<int> &v, std::vector<int> &w) const
-    {
-        ptr.assign(owners + 1, 0);
-        for (auto &e : ent) ptr[e[0] + 1]++;
-        for (int r = 0; r < owners; ++r) ptr[r + 1] += ptr[r];
-        std::vector<int> fill(ptr.begin(), ptr.end() - 1);
-        v.assign(ent.size() ? ent.size() : 1, 0); w.assign(v.size(), 0);
-        for (auto &e : ent) { const int k = fill[e[0]]++; v[k] = e[1]; w[k] = e[2]; }
-    }
-};
-
-extern "C" int sqphip_qcqp_attach(sqphip_ctx *h, int64_t nnzQ0, const int64_t *q0r, const int64_t *q0c, const double *q0v,
-                                  int64_t nnzA, const int64_t *ar, const int64_t *ac, const double *av, int64_t nnzQ,
-                                  const int64_t *qi, const int64_t *qr, const int64_t *qc, const double *qv,
-                                  const double *c, const double *g0, double f0)
-{
-    if (!h) return SQPHIP_EINVAL;
-    Ctx &C0 = h->c;
-    if (C0.acopf_attached) {
-        C0.err = "sqphip_qcqp_attach: the context already has device callbacks (an earlier *_attach)";
-        return SQPHIP_ESTATE;
-    }
-    if (nnzQ0 < 0 || nnzA < 0 || nnzQ < 0) return qcqp_fail(h, "negative term count");
-    if ((nnzQ0 > 0 && (!q0r || !q0c || !q0v)) || (nnzA > 0 && (!ar || !ac || !av)) ||
-        (nnzQ > 0 && (!qi || !qr || !qc || !qv))) return qcqp_fail(h, "null term array");
-    const int64_t n = C0.d.n, m = C0.d.m, nlin = C0.d.nlin, nnzJ = C0.d.nnzj_coo, nnzH = C0.d.nnzh_coo;
-    // first COO slot of every structural entry (later duplicates get no plan entries: 0, gather_csc sums them)
-    std::unordered_map<int64_t, int> jslot, hslot;
-    for (int64_t k = nnzJ - 1; k >= 0; --k) jslot[(C0.h_jrow[k] - 1) * n + (C0.h_jcol[k] - 1)] = (int)k;
-    for (int64_t k = nnzH - 1; k >= 0; --k) {
-        const int64_t r = C0.h_hrow[k] - 1, cc = C0.h_hcol[k] - 1;
-        hslot[std::max(r, cc) * n + std::min(r, cc)] = (int)k;
-    }
-    auto jfind = [&](int64_t i, int64_t j) { auto it = jslot.find(i * n + j); return it == jslot.end() ? -1 : it->second; };
-    auto hfind = [&](int64_t r, int64_t cc) {
-        auto it = hslot.find(std::max(r, cc) * n + std::min(r, cc)); return it == hslot.end() ? -1 : it->second; };
-    const std::string jmiss = " needs a Jacobian entry that the structure of sqphip_create lacks",
-                      hmiss = " needs a Hessian entry that the structure of sqphip_create lacks";
-    // values of an instance: f0 | c | Q0 | g0 | A | Q
-    const int off_c = 1, off_q0 = off_c + (int)n, off_g0 = off_q0 + (int)nnzQ0, off_a = off_g0 + (int)m,
-              off_q = off_a + (int)nnzA;
-    const long nvals = (long)off_q + nnzQ;
-    const long nv = (nvals + 1) & ~1L;     // stride of an instance's block, padded to even: every block is 16-byte aligned (b_sqp_stream)
-    PlanCsr G, F, J, H;
-    for (int64_t t = 0; t < nnzQ0; ++t) {
-        const int64_t r = q0r[t] - 1, cc = q0c[t] - 1;
-        if (r < 0 || r >= n || cc < 0 || cc >= n) return qcqp_fail(h, qcqp_term("Q0", t + 1, q0r[t], q0c[t]) + ": index out of range");
-        const int hs = hfind(r, cc);
-        if (nnzH > 0 && hs < 0) return qcqp_fail(h, qcqp_term("Q0", t + 1, q0r[t], q0c[t]) + hmiss);
-        const int v = off_q0 + (int)t;
-        F.ent.push_back({(int)r, v, (int)cc});
-        if (r != cc) F.ent.push_back({(int)cc, v, (int)r});
-        if (hs >= 0) H.ent.push_back({hs, v, -1});
-    }
-    for (int64_t t = 0; t < nnzA; ++t) {
-        const int64_t i = ar[t] - 1, j = ac[t] - 1;
-        if (i < 0 || i >= m || j < 0 || j >= n) return qcqp_fail(h, qcqp_term("A", t + 1, ar[t], ac[t]) + ": index out of range");
-        const int js = jfind(i, j);
-        if (js < 0) return qcqp_fail(h, qcqp_term("A", t + 1, ar[t], ac[t]) + jmiss);
-        const int v = off_a + (int)t;
-        G.ent.push_back({(int)i, v, (int)j});
-        J.ent.push_back({js, v, -1});
-    }
-    std::vector<int> gsecond(nnzA, -1);       // second variable of every row-plan entry (-1: linear), in production order
-    for (int64_t t = 0; t < nnzQ; ++t) {
-        const int64_t i = qi[t] - 1, r = qr[t] - 1, cc = qc[t] - 1;
-        const std::string what = qcqp_term("Q", t + 1, qi[t], qr[t], qc[t]);
-        if (i < 0 || i >= m || r < 0 || r >= n || cc < 0 || cc >= n) return qcqp_fail(h, what + ": index out of range");
-        if (i < nlin) return qcqp_fail(h, what + ": a quadratic term in row " + std::to_string(i + 1) +
-                                              ", one of the num_linear = " + std::to_string(nlin) + " linear rows");
-        const int jr = jfind(i, r), jc = jfind(i, cc), hs = hfind(r, cc);
-        if (jr < 0 || jc < 0) return qcqp_fail(h, what + jmiss);
-        if (nnzH > 0 && hs < 0) return qcqp_fail(h, what + hmiss);
-        const int v = off_q + (int)t;
-        G.ent.push_back({(int)i, v, (int)r}); gsecond.push_back((int)cc);
-        J.ent.push_back({jr, v, (int)cc});
-        if (r != cc) J.ent.push_back({jc, v, (int)r});
-        if (hs >= 0) H.ent.push_back({hs, v, (int)i});
-    }
-    std::vector<int> g_ptr, g_v, g_a, g_b, f_ptr, f_v, f_x, j_ptr, j_v, j_x, h_ptr, h_v, h_r;
-    G.finish((int)m, g_ptr, g_v, g_a);
-    {   // the second variables follow their entries through the same placement
-        std::vector<int> fill(g_ptr.begin(), g_ptr.end() - 1);
-        g_b.assign(g_v.size(), -1);
-        for (size_t e = 0; e < G.ent.size(); ++e) g_b[fill[G.ent[e][0]]++] = gsecond[e];
-    }
-    F.finish((int)n, f_ptr, f_v, f_x);
-    J.finish((int)nnzJ, j_ptr, j_v, j_x);
-    H.finish((int)nnzH, h_ptr, h_v, h_r);
-    std::vector<double> val0(nv, 0.0);
-    val0[0] = f0;
-    if (c) std::copy(c, c + n, val0.begin() + off_c);
-    if (nnzQ0) std::copy(q0v, q0v + nnzQ0, val0.begin() + off_q0);
-    if (g0) std::copy(g0, g0 + m, val0.begin() + off_g0);
-    if (nnzA) std::copy(av, av + nnzA, val0.begin() + off_a);
-    if (nnzQ) std::copy(qv, qv + nnzQ, val0.begin() + off_q);
-    std::vector<int2> q0(nnzQ0 ? nnzQ0 : 1, int2{0, 0});
-    for (int64_t t = 0; t < nnzQ0; ++t) q0[t] = int2{(int)std::max(q0r[t], q0c[t]) - 1, (int)std::min(q0r[t], q0c[t]) - 1};
-    // packed plans: the row pointers back to back, the entries as int2 / int4
-    std::vector<int> ptr(g_ptr);
-    const int fp = (int)ptr.size(); ptr.insert(ptr.end(), f_ptr.begin(), f_ptr.end());
-    const int jp = (int)ptr.size(); ptr.insert(ptr.end(), j_ptr.begin(), j_ptr.end());
-    const int hp = (int)ptr.size(); ptr.insert(ptr.end(), h_ptr.begin(), h_ptr.end());
-    auto pack2 = [](const std::vector<int> &a, const std::vector<int> &b) {
-        std::vector<int2> o(a.size());
-        for (size_t k = 0; k < a.size(); ++k) o[k] = int2{a[k], b[k]};
-        return o;
-    };
-    std::vector<int4> ge(g_v.size());
-    for (size_t k = 0; k < g_v.size(); ++k) ge[k] = int4{g_v[k], g_a[k], g_b[k], 0};
-    return guarded(h, [&](Ctx &C) {
-        DV &d = C.d;
-        QcqpDev P = {};
-        P.n = (int)n; P.m = (int)m; P.nv = (int)nv; P.nq0 = (int)nnzQ0;
-        P.off_c = off_c; P.off_q0 = off_q0; P.off_g0 = off_g0;
-        P.f_ptr = fp; P.j_ptr = jp; P.h_ptr = hp;
-        P.ptr = C.upload(ptr); P.q0 = C.upload(q0); P.ge = C.upload(ge);
-        P.fe = C.upload(pack2(f_v, f_x)); P.je = C.upload(pack2(j_v, j_x)); P.he = C.upload(pack2(h_v, h_r));
-        QcqpDev *pd = (QcqpDev *)C.dalloc<char>(sizeof(QcqpDev));
-        SQPHIP_HIP_OK(hipMemcpyAsync(pd, &P, sizeof(QcqpDev), hipMemcpyHostToDevice, C.stream));
-        std::vector<double> all((size_t)d.B * nv);
-        for (int b = 0; b < d.B; ++b) std::copy(val0.begin(), val0.end(), all.begin() + (size_t)b * nv);
-        d.qcv = C.upload(all);
-        d.qc = pd;
-        C.qc_nv = nv;
-        const long off[7] = {0, off_c, off_q0, off_g0, off_a, off_q, nvals};
-        std::copy(off, off + 7, C.qc_off);
-        C.h_qc_base = val0;                // (the instances' blocks are overwritten by sqphip_qcqp_set_instance)
-        SQPHIP_HIP_OK(hipStreamSynchronize(C.stream));
-        C.acopf_attached = true;           // (the batched run! has its device callbacks)
-        make_lanes(C);
-        return SQPHIP_OK;
-    });
-}
-
-extern "C" int sqphip_qcqp_set_instance(sqphip_ctx *h, int32_t inst, const double *f0, const double *c, const double *q0v,
-                                        const double *g0, const double *av, const double *qv, const double *x0)
-{
-    if (h && !h->c.d.qc && h->c.acopf_attached) {
-        h->c.err = "sqphip_qcqp_set_instance: the context has no QCQP attached (sqphip_qcqp_attach)";
-        return SQPHIP_EINVAL;
-    }
-    if (!h || !h->c.d.qc || inst < 0 || inst >= h->c.d.B) return SQPHIP_EINVAL;
-    return guarded(h, [&](Ctx &C) {
-        DV &d = C.d;
-        const long *o = C.qc_off;           // f0 | c | Q0 | g0 | A | Q | end
-        double *v = d.qcv + (size_t)inst * C.qc_nv;
-        const double *src[6] = {f0, c, q0v, g0, av, qv};
-        for (int k = 0; k < 6; ++k) h2d(C, v + o[k], src[k], (size_t)(o[k + 1] - o[k]));
-        h2d(C, d.x0 + (size_t)inst * d.n, x0, d.n);
-        SQPHIP_HIP_OK(hipStreamSynchronize(C.stream));
-        return SQPHIP_OK;
-    });
-}
-
-// ---- a sparse factorable NLP (nlp_dev.hpp nlp_eval): sums of products of univariate functions.  The gather plans are
-// built here, once, from the terms and the COO structures of sqphip_create
-static int nlp_fail(sqphip_ctx *h, const char *who, int64_t t, int64_t k, const std::string &msg)
-{
-    h->c.err = std::string(who) + ": term " + std::to_string(t + 1) + (k >= 0 ? " factor " + std::to_string(k + 1) : std::string()) + ": " + msg;
-    return SQPHIP_EINVAL;
-}
-
-// owners of a plan's entries (in production order) -> CSR row pointers and the stable order of the entries by owner
-static void plan_order(int owners, const std::vector<int> &own, std::vector<int> &ptr, std::vector<int> &ord)
-{
-    ptr.assign(owners + 1, 0);
-    for (int o : own) ptr[o + 1]++;
-    for (int r = 0; r < owners; ++r) ptr[r + 1] += ptr[r];
-    std::vector<int> fill(ptr.begin(), ptr.end() - 1);
-    ord.assign(own.size(), 0);
-    for (size_t e = 0; e < own.size(); ++e) ord[fill[own[e]]++] = (int)e;
-}
-
-// The three entry points.  !affine: sqphip_nlp_attach, aptr is null and factor k has the one argument avar[k] with coefficient acoef[k].
-// A one-argument factor keeps its coefficient in pass 1 (fab, chain factors folded into phi', phi'') and weight 1.0 in the
-// plans; a factor of several arguments stores kappa', kappa'' and its arguments weigh a_v (nlp_dev.hpp).
-// general: sqphip_nlp_attach_general -- the menu up to POWR (fpar: its real exponents) and variables shared by the factors of
-// a term; the two older calls are this one with the menu check at LOG and the distinct-variables check switched on.
-// data: sqphip_nlp_attach_data -- the general call with b | a | p appended to every instance's block (nlp_dev.hpp NlpDev::data).
-static int nlp_attach_impl(sqphip_ctx *h, const char *who, bool affine, bool general, bool data, int64_t nterms, const int64_t *trow, const double *tcoef,
-                           const int64_t *tptr, const int64_t *aptr, const int64_t *avar, const double *acoef, const int32_t *fkind,
-                           const int32_t *fexp, const double *fpar, const double *fshift, const double *g0, double f0)
-{
-    const int last_kind = general ? NLP_POWR : NLP_LOG;
-    if (!h) return SQPHIP_EINVAL;
-    Ctx &C0 = h->c;
-    if (C0.acopf_attached) {
-        C0.err = std::string(who) + ": the context already has device callbacks (an earlier *_attach)";
-        return SQPHIP_ESTATE;
-    }
-    auto fail = [&](const char *msg) { C0.err = std::string(who) + ": " + msg; return (int)SQPHIP_EINVAL; };
-    if (affine && !aptr) return fail("null aptr");
-    if (nterms < 0) return fail("negative term count");
-    if (!tptr || (nterms > 0 && (!trow || !tcoef))) return fail("null term array");
-    if (tptr[0] != 0) return fail("tptr[0] must be 0");
-    for (int64_t t = 0; t < nterms; ++t)
-        if (tptr[t + 1] < tptr[t]) return nlp_fail(h, who, t, -1, "tptr decreases");
-    const int64_t nfac = tptr[nterms];
-    if (nfac > 0 && (!avar || !fkind || !fexp)) return fail("null factor array");
-    if (nfac > (1 << 28) || nterms > (1 << 28)) return fail("too many terms");
-    if (affine) {
-        if (aptr[0] != 0) return fail("aptr[0] must be 0");
-        for (int64_t t = 0; t < nterms; ++t)
-            for (int64_t k = tptr[t]; k < tptr[t + 1]; ++k) {
-                if (aptr[k + 1] < aptr[k]) return nlp_fail(h, who, t, k - tptr[t], "aptr decreases");
-                if (aptr[k + 1] == aptr[k]) return nlp_fail(h, who, t, k - tptr[t], "no arguments");
-                if (aptr[k + 1] - aptr[k] > 8) return nlp_fail(h, who, t, k - tptr[t], "more than 8 arguments");
-            }
-    }
-    const int64_t nargs = affine ? aptr[nfac] : nfac;
-    if (nargs > (1 << 28)) return fail("too many arguments");
-    auto a0 = [&](int64_t k) { return affine ? aptr[k] : k; };
-    const int64_t n = C0.d.n, m = C0.d.m, nlin = C0.d.nlin, nnzJ = C0.d.nnzj_coo, nnzH = C0.d.nnzh_coo;
-    // first COO slot of every structural entry (later duplicates get no plan entries: 0, gather_csc sums them)
-    std::unordered_map<int64_t, int> jslot, hslot;
-    for (int64_t k = nnzJ - 1; k >= 0; --k) jslot[(C0.h_jrow[k] - 1) * n + (C0.h_jcol[k] - 1)] = (int)k;
-    for (int64_t k = nnzH - 1; k >= 0; --k) {
-        const int64_t r = C0.h_hrow[k] - 1, cc = C0.h_hcol[k] - 1;
-        hslot[std::max(r, cc) * n + std::min(r, cc)] = (int)k;
-    }
-    auto jfind = [&](int64_t i, int64_t j) { auto it = jslot.find(i * n + j); return it == jslot.end() ? -1 : it->second; };
-    auto hfind = [&](int64_t r, int64_t cc) {
-        auto it = hslot.find(std::max(r, cc) * n + std::min(r, cc)); return it == hslot.end() ? -1 : it->second; };
-    std::vector<int> ot, g_own, g_t, f_own, j_own, h_own;
-    std::vector<int2> f_e, j_e;
-    std::vector<int4> h_e;
-    std::vector<int> fke((size_t)std::max<int64_t>(nfac, 1), 0), fv(fke.size(), 0);
-    std::vector<double2> fab(fke.size(), double2{1.0, 0.0});
-    std::vector<int> ap((size_t)nfac + 1, 0), av((size_t)std::max<int64_t>(nargs, 1), 0);
-    std::vector<double> ac(av.size(), 1.0), aw(av.size(), 1.0), fpw(fke.size(), 0.0);
-    bool multi = false, powr = false;
-    std::vector<int> lin_terms;
-    for (int64_t t = 0; t < nterms; ++t) {
-        const int64_t i = trow[t], k0 = tptr[t], k1 = tptr[t + 1];
-        if (i < 0 || i > m) return nlp_fail(h, who, t, -1, "row " + std::to_string(i) + " out of range (0: objective, 1.." + std::to_string(m) + ")");
-        if (k1 == k0) return nlp_fail(h, who, t, -1, "no factors (a constant belongs in f0 / g0)");
-        if (k1 - k0 > 8) return nlp_fail(h, who, t, -1, "more than 8 factors");
-        bool plain[8];
-        for (int64_t k = k0; k < k1; ++k) {
-            const int64_t kf = k - k0, j0 = a0(k), j1 = a0(k + 1);
-            const double b = fshift ? fshift[k] : 0.0;
-            for (int64_t j = j0; j < j1; ++j)
-                if (avar[j] < 1 || avar[j] > n) return nlp_fail(h, who, t, kf, "variable " + std::to_string(avar[j]) + " out of range");
-            if (fkind[k] < NLP_POW || fkind[k] > last_kind) return nlp_fail(h, who, t, kf, "unknown kind " + std::to_string(fkind[k]));
-            if (fkind[k] == NLP_POWR) {
-                if (!fpar) return nlp_fail(h, who, t, kf, "a POWR factor needs its real exponent: fpar is null");
-                if (!std::isfinite(fpar[k]) || fpar[k] == 0.0)
-                    return nlp_fail(h, who, t, kf, "real exponent " + std::to_string(fpar[k]) + " (finite and not 0)");
-                fpw[k] = fpar[k];
-                powr = true;
-            }
-            const int e = fkind[k] == NLP_POW ? fexp[k] : 1;
-            if (e == 0 || e > 32 || e < -32) return nlp_fail(h, who, t, kf, "exponent " + std::to_string(e) + " (1 <= |e| <= 32)");
-            for (int64_t j = j0; j < j1; ++j) {
-                for (int64_t j2 = j0; j2 < j; ++j2)
-                    if (avar[j2] == avar[j]) return nlp_fail(h, who, t, kf, "variable " + std::to_string(avar[j]) + " twice in one factor (add the coefficients)");
-                for (int64_t j2 = a0(k0); !general && j2 < j0; ++j2)
-                    if (avar[j2] == avar[j]) return nlp_fail(h, who, t, kf, "variable " + std::to_string(avar[j]) + " twice in one term (write x^2)");
-            }
-            plain[kf] = fkind[k] == NLP_POW && e == 1;
-            const bool one = j1 - j0 == 1;
-            multi = multi || !one;
-            const double a = one && acoef ? acoef[j0] : 1.0;
-            if (i >= 1 && i <= nlin && !(k1 - k0 == 1 && one && plain[kf] && a == 1.0 && b == 0.0))
-                return nlp_fail(h, who, t, kf, "row " + std::to_string(i) + " is one of the num_linear = " + std::to_string(nlin) +
-                                          (affine ? " linear rows: a single POW factor with e = 1, one argument with coefficient 1, shift 0 only"
-                                                  : " linear rows: a single POW factor with e = 1, a = 1, b = 0 only"));
-            fv[k] = one ? (int)avar[j0] - 1 : -1; fke[k] = fkind[k] + (e + 32) * (1 << NLP_KIND_BITS); fab[k] = double2{a, b};
-            ap[k] = (int)j0; ap[k + 1] = (int)j1;
-            for (int64_t j = j0; j < j1; ++j) {
-                av[j] = (int)avar[j] - 1; ac[j] = acoef ? acoef[j] : 1.0; aw[j] = one ? 1.0 : ac[j];
-            }
-        }
-        if (i >= 1 && i <= nlin) lin_terms.push_back((int)t);
-        if (i == 0) ot.push_back((int)t); else { g_own.push_back((int)i - 1); g_t.push_back((int)t); }
-        // a plan entry names an argument and, in the bits above 2^28, its factor within the term
-        auto ent = [&](int64_t k, int64_t j) { return (int)(j | ((k - k0) << 28)); };
-        for (int64_t k = k0; k < k1; ++k)
-            for (int64_t j = a0(k); j < a0(k + 1); ++j) {
-                if (i == 0) { f_own.push_back(av[j]); f_e.push_back(int2{(int)t, ent(k, j)}); continue; }
-                const int js = jfind(i - 1, av[j]);
-                if (js < 0) return nlp_fail(h, who, t, k - k0, "needs the Jacobian entry (" + std::to_string(i) + ", " + std::to_string(avar[j]) +
-                                                          ") that the structure of sqphip_create lacks");
-                j_own.push_back(js); j_e.push_back(int2{(int)t, ent(k, j)});
-            }
-        if (nnzH > 0)
-            for (int64_t k = k0; k < k1; ++k)
-                for (int64_t j = a0(k); j < a0(k + 1); ++j)
-                    for (int64_t k2 = k0; k2 <= k; ++k2) {
-                        if (k2 == k && plain[k - k0]) continue;            // phi'' = 0
-                        for (int64_t j2 = a0(k2); j2 < (k2 == k ? j + 1 : a0(k2 + 1)); ++j2) {
-                            const int hs = hfind(av[j], av[j2]);
-                            if (hs < 0) return nlp_fail(h, who, t, k - k0, "needs the Hessian entry (" + std::to_string(std::max(avar[j], avar[j2])) + ", " +
-                                                                      std::to_string(std::min(avar[j], avar[j2])) + ") that the structure of sqphip_create lacks");
-                            // two arguments on one variable (general only: different factors): both ordered pairs count
-                            for (int c = (j2 != j && av[j2] == av[j]) ? 2 : 1; c > 0; --c) {
-                                h_own.push_back(hs); h_e.push_back(int4{(int)t, ent(k2, j2), ent(k, j), (int)i - 1});
-                            }
-                        }
-                    }
-    }
-    // CSR by owner, the entries of one owner kept in production (term) order
-    std::vector<int> g_ptr, f_ptr, j_ptr, h_ptr, ord;
-    plan_order((int)m, g_own, g_ptr, ord);
-    std::vector<int> ge(std::max<size_t>(ord.size(), 1), 0);
-    for (size_t e = 0; e < ord.size(); ++e) ge[e] = g_t[ord[e]];
-    plan_order((int)n, f_own, f_ptr, ord);
-    std::vector<int2> fe(std::max<size_t>(ord.size(), 1), int2{0, 0});
-    for (size_t e = 0; e < ord.size(); ++e) fe[e] = f_e[ord[e]];
-    plan_order((int)nnzJ, j_own, j_ptr, ord);
-    std::vector<int2> je(std::max<size_t>(ord.size(), 1), int2{0, 0});
-    for (size_t e = 0; e < ord.size(); ++e) je[e] = j_e[ord[e]];
-    plan_order((int)nnzH, h_own, h_ptr, ord);
-    std::vector<int4> he(std::max<size_t>(ord.size(), 1), int4{0, 0, 0, 0});
-    for (size_t e = 0; e < ord.size(); ++e) he[e] = h_e[ord[e]];
-    std::vector<int> ptr(g_ptr);
-    const int fp = (int)ptr.size(); ptr.insert(ptr.end(), f_ptr.begin(), f_ptr.end());
-    const int jp = (int)ptr.size(); ptr.insert(ptr.end(), j_ptr.begin(), j_ptr.end());
-    const int hp = (int)ptr.size(); ptr.insert(ptr.end(), h_ptr.begin(), h_ptr.end());
-    std::vector<int> tp((size_t)nterms + 1);
-    for (int64_t t = 0; t <= nterms; ++t) tp[t] = (int)tptr[t];
-    // values of an instance: f0 | g0 | c, the stride padded to even: every block is 16-byte aligned, as the QCQP blocks are;
-    // data: f0 | g0 | c | b [nfac] | a [nargs] | p [nfac, with a POWR factor only]
-    const long ob = 1 + (long)m + nterms, oa = ob + nfac, op = powr ? oa + nargs : -1;
-    const long nvals = data ? oa + nargs + (powr ? nfac : 0) : ob, nv = (nvals + 1) & ~1L;
-    if (nv > INT32_MAX) return fail("too many values per instance");
-    std::vector<double> val0(nv, 0.0);
-    val0[0] = f0;
-    if (g0) std::copy(g0, g0 + m, val0.begin() + 1);
-    if (nterms) std::copy(tcoef, tcoef + nterms, val0.begin() + 1 + m);
-    if (data) {
-        for (int64_t k = 0; k < nfac; ++k) val0[ob + k] = fab[k].y;
-        std::copy(ac.begin(), ac.begin() + nargs, val0.begin() + oa);
-        if (powr) std::copy(fpw.begin(), fpw.begin() + nfac, val0.begin() + op);
-    }
-    const int nobj = (int)ot.size();
-    if (ot.empty()) ot.push_back(0);
-    return guarded(h, [&](Ctx &C) {
-        DV &d = C.d;
-        NlpDev P = {};
-        P.n = (int)n; P.m = (int)m; P.nterms = (int)nterms; P.nfac = (int)nfac; P.nv = (int)nv; P.nobj = nobj;
-        P.f_ptr = fp; P.j_ptr = jp; P.h_ptr = hp;
-        P.ptr = C.upload(ptr); P.tptr = C.upload(tp); P.fvar = C.upload(fv); P.fke = C.upload(fke); P.fab = C.upload(fab);
-        P.ot = C.upload(ot); P.ge = C.upload(ge); P.fe = C.upload(fe); P.je = C.upload(je); P.he = C.upload(he);
-        P.aptr = C.upload(ap); P.avar = C.upload(av); P.acoef = C.upload(ac); P.aw = C.upload(aw); P.multi = multi ? 1 : 0;
-        P.fpar = C.upload(fpw);
-        P.data = data ? 1 : 0; P.ob = (int)ob; P.oa = (int)oa; P.op = (int)op;
-        P.ws = 3 * (int)nfac;
-        NlpDev *pd = (NlpDev *)C.dalloc<char>(sizeof(NlpDev));
-        SQPHIP_HIP_OK(hipMemcpyAsync(pd, &P, sizeof(NlpDev), hipMemcpyHostToDevice, C.stream));
-        std::vector<double> all((size_t)d.B * nv);
-        for (int b = 0; b < d.B; ++b) std::copy(val0.begin(), val0.end(), all.begin() + (size_t)b * nv);
-        d.nlv = C.upload(all);
-        d.nlw = C.dalloc<double>((size_t)d.B * 3 * (size_t)nfac);
-        d.nlp = pd;
-        C.nl_nv = nv; C.nl_nfac = nfac; C.nl_nterms = nterms;
-        C.nl_end = nvals; C.nl_ws = 3 * nfac; C.nl_blk.clear(); C.nl_started = false;
-        C.h_nl_base = val0;                // (the instances' blocks are overwritten by sqphip_nlp_set_instance)
-        C.nl_data = data; C.nl_ob = ob; C.nl_oa = oa; C.nl_op = op; C.nl_nargs = nargs;
-        if (data) { C.h_nl_tptr = tp; C.h_nl_aptr = ap; C.h_nl_kind.assign(fkind, fkind + nfac); C.h_nl_lin = lin_terms; }
-        SQPHIP_HIP_OK(hipStreamSynchronize(C.stream));
-        C.acopf_attached = true;           // (the batched run! has its device callbacks)
-        make_lanes(C);
-        return SQPHIP_OK;
-    });
-}
-
-extern "C" int sqphip_nlp_attach(sqphip_ctx *h, int64_t nterms, const int64_t *trow, const double *tcoef, const int64_t *tptr,
-                                 const int64_t *fvar, const int32_t *fkind, const int32_t *fexp, const double *fscale,
-                                 const double *fshift, const double *g0, double f0)
-{
-    return nlp_attach_impl(h, "sqphip_nlp_attach", false, false, false, nterms, trow, tcoef, tptr, nullptr, fvar, fscale, fkind, fexp, nullptr, fshift, g0, f0);
-}
-
-extern "C" int sqphip_nlp_attach_affine(sqphip_ctx *h, int64_t nterms, const int64_t *trow, const double *tcoef, const int64_t *tptr,
-                                        const int64_t *aptr, const int64_t *avar, const double *acoef, const int32_t *fkind,
-                                        const int32_t *fexp, const double *fshift, const double *g0, double f0)
-{
-    return nlp_attach_impl(h, "sqphip_nlp_attach_affine", true, false, false, nterms, trow, tcoef, tptr, aptr, avar, acoef, fkind, fexp, nullptr, fshift, g0, f0);
-}
-
-extern "C" int sqphip_nlp_attach_general(sqphip_ctx *h, int64_t nterms, const int64_t *trow, const double *tcoef, const int64_t *tptr,
-                                         const int64_t *aptr, const int64_t *avar, const double *acoef, const int32_t *fkind,
-                                         const int32_t *fexp, const double *fpar, const double *fshift, const double *g0, double f0)
-{
-    return nlp_attach_impl(h, "sqphip_nlp_attach_general", true, true, false, nterms, trow, tcoef, tptr, aptr, avar, acoef, fkind, fexp, fpar, fshift, g0, f0);
-}
-
-extern "C" int sqphip_nlp_attach_data(sqphip_ctx *h, int64_t nterms, const int64_t *trow, const double *tcoef, const int64_t *tptr,
-                                      const int64_t *aptr, const int64_t *avar, const double *acoef, const int32_t *fkind,
-                                      const int32_t *fexp, const double *fpar, const double *fshift, const double *g0, double f0)
-{
-    return nlp_attach_impl(h, "sqphip_nlp_attach_data", true, true, true, nterms, trow, tcoef, tptr, aptr, avar, acoef, fkind, fexp, fpar, fshift, g0, f0);
-}
-
-// what sqphip_nlp_set_instance_data and sqphip_nlp_stream_set_data refuse of the data of one instance (NULL: kept, unchecked:
-// what an instance holds has passed these checks)
-static int nlp_data_check(sqphip_ctx *h, const char *who, const double *fshift, const double *acoef, const double *fpar)
-{
-    Ctx &C = h->c;
-    if (!C.d.nlp || !C.nl_data) {
-        C.err = std::string(who) + ": the data of this context is shared by the batch (attach with sqphip_nlp_attach_data)";
-        return SQPHIP_EINVAL;
-    }
-    if (fpar && C.nl_op < 0) { C.err = std::string(who) + ": fpar given, but the model has no POWR factor"; return SQPHIP_EINVAL; }
-    if (fpar)
-        for (long t = 0; t < C.nl_nterms; ++t)
-            for (int k = C.h_nl_tptr[t]; k < C.h_nl_tptr[t + 1]; ++k)
-                if (C.h_nl_kind[k] == NLP_POWR && (!std::isfinite(fpar[k]) || fpar[k] == 0.0))
-                    return nlp_fail(h, who, t, k - C.h_nl_tptr[t], "real exponent " + std::to_string(fpar[k]) + " (finite and not 0)");
-    for (int t : C.h_nl_lin) {
-        const int k = C.h_nl_tptr[t];              // (the attach made sure: one factor, one argument)
-        if ((acoef && acoef[C.h_nl_aptr[k]] != 1.0) || (fshift && fshift[k] != 0.0))
-            return nlp_fail(h, who, t, 0, "the term is in one of the num_linear = " + std::to_string(C.d.nlin) +
-                                          " linear rows: coefficient 1 and shift 0 only");
-    }
-    return SQPHIP_OK;
-}
-
-// ... and the upload of the parts given into the block v (of an instance or of a scenario of the queue)
-static void nlp_data_upload(Ctx &C, double *v, const double *fshift, const double *acoef, const double *fpar)
-{
-    h2d(C, v + C.nl_ob, fshift, (size_t)C.nl_nfac); h2d(C, v + C.nl_oa, acoef, (size_t)C.nl_nargs);
-    if (C.nl_op >= 0) h2d(C, v + C.nl_op, fpar, (size_t)C.nl_nfac);
-}
-
-extern "C" int sqphip_nlp_set_instance_data(sqphip_ctx *h, int32_t inst, const double *fshift, const double *acoef, const double *fpar)
-{
-    const char *who = "sqphip_nlp_set_instance_data";
-    if (!h) return SQPHIP_EINVAL;
-    if (int rc = nlp_data_check(h, who, nullptr, nullptr, nullptr)) return rc;
-    if (inst < 0 || inst >= h->c.d.B) {
-        h->c.err = std::string(who) + ": instance " + std::to_string(inst) + " is outside the batch of " + std::to_string(h->c.d.B);
-        return SQPHIP_EINVAL;
-    }
-    if (int rc = nlp_data_check(h, who, fshift, acoef, fpar)) return rc;
-    return guarded(h, [&](Ctx &C) {
-        nlp_data_upload(C, C.d.nlv + (size_t)inst * C.nl_nv, fshift, acoef, fpar);
-        SQPHIP_HIP_OK(hipStreamSynchronize(C.stream));
-        return SQPHIP_OK;
-    });
-}
-
-extern "C" int sqphip_nlp_set_instance(sqphip_ctx *h, int32_t inst, const double *f0, const double *g0, const double *tcoef,
-                                       const double *x0)
-{
-    if (h && !h->c.d.nlp) {
-        h->c.err = "sqphip_nlp_set_instance: the context has no factorable NLP attached (sqphip_nlp_attach)";
-        return SQPHIP_EINVAL;
-    }
-    if (!h || inst < 0 || inst >= h->c.d.B) return SQPHIP_EINVAL;
-    return guarded(h, [&](Ctx &C) {
-        DV &d = C.d;
-        double *v = d.nlv + (size_t)inst * C.nl_nv;           // f0 | g0 | c
-        h2d(C, v, f0, 1); h2d(C, v + 1, g0, d.m); h2d(C, v + 1 + d.m, tcoef, (size_t)C.nl_nterms);
-        h2d(C, d.x0 + (size_t)inst * d.n, x0, d.n);
-        SQPHIP_HIP_OK(hipStreamSynchronize(C.stream));
-        return SQPHIP_OK;
-    });
-}
-
-// ---- dense data blocks of the objective of a factorable NLP (nlp_block_dev.hpp, nlp_softmax_dev.hpp)
-// the state rules of the add calls; kb: the number of the block to be, blk: "who: block kb + 1" for the messages
-static int nlp_block_begin(sqphip_ctx *h, const std::string &who, int &kb, std::string &blk)
-{
-    Ctx &C0 = h->c;
-    if (!C0.d.nlp) { C0.err = who + ": the context has no factorable NLP attached (sqphip_nlp_attach*)"; return SQPHIP_EINVAL; }
-    if (C0.nl_started) {
-        C0.err = who + ": the layout of the instances is final after sqphip_sqp_reset, sqphip_sqp_run or sqphip_nlp_stream_begin";
-        return SQPHIP_ESTATE;
-    }
-    kb = (int)C0.nl_blk.size();
-    blk = who + ": block " + std::to_string(kb + 1);
-    if (kb >= NLP_MAX_BLOCKS) { C0.err = blk + ": a context takes at most " + std::to_string((int)NLP_MAX_BLOCKS) + " blocks"; return SQPHIP_EINVAL; }
-    return SQPHIP_OK;
-}
-
-// cols [D] 1-based, in range and distinct, to cv (0-based), and the COO slot of every lower entry (r, c) of the block's
-// D x D Hessian to hs (-1 throughout when nnzH = 0): the first COO copy of a structural entry owns it, as for the plans.
-// Returns the complaint, empty when there is none.
-static std::string nlp_block_columns(const Ctx &C0, int D, const int64_t *cols, std::vector<int> &cv, std::vector<int> &hs)
-{
-    const int64_t n = C0.d.n, nnzH = C0.d.nnzh_coo;
-    for (int j = 0; j < D; ++j) {
-        if (cols[j] < 1 || cols[j] > n) return "column " + std::to_string(j + 1) + ": variable " + std::to_string(cols[j]) + " out of range";
-        for (int j2 = 0; j2 < j; ++j2)
-            if (cols[j2] == cols[j]) return "column " + std::to_string(j + 1) + ": variable " + std::to_string(cols[j]) + " twice (columns " +
-                                            std::to_string(j2 + 1) + " and " + std::to_string(j + 1) + ")";
-    }
-    hs.assign((size_t)D * (D + 1) / 2, -1); cv.resize(D);
-    for (int j = 0; j < D; ++j) cv[j] = (int)cols[j] - 1;
-    if (nnzH > 0) {
-        std::unordered_map<int64_t, int> hslot;
-        for (int64_t k = nnzH - 1; k >= 0; --k) {
-            const int64_t r = C0.h_hrow[k] - 1, cc = C0.h_hcol[k] - 1;
-            hslot[std::max(r, cc) * n + std::min(r, cc)] = (int)k;
-        }
-        for (int r = 0; r < D; ++r)
-            for (int c = 0; c <= r; ++c) {
-                const int64_t vr = std::max(cv[r], cv[c]), vc = std::min(cv[r], cv[c]);
-                auto it = hslot.find(vr * n + vc);
-                if (it == hslot.end())
-                    return "entry (" + std::to_string(r + 1) + ", " + std::to_string(c + 1) + ") needs the Hessian entry (" + std::to_string(vr + 1) +
-                           ", " + std::to_string(vc + 1) + ") that the structure of sqphip_create lacks";
-                hs[(size_t)r * (r + 1) / 2 + c] = it->second;
-            }
-    }
-    return "";
-}
-
-// Re-lays the instances' blocks of doubles behind what they hold with W [N] | S [nS] of block kb (weight NULL: ones, shift
-// NULL: zeros), uploads A [N][d] and its transpose, cv and hs, and files the block K (ke, par, K, Kf, y: the caller's; wsz:
-// its doubles of workspace) in the context's NlpDev.
-static int nlp_block_commit(sqphip_ctx *h, const std::string &blk, int kb, long N, int d, long nS, long wsz, const double *A,
-                            const std::vector<int> &cv, const std::vector<int> &hs, const double *weight, const double *shift,
-                            NlpBlkDev K, int32_t *blk_out)
-{
-    Ctx &C0 = h->c;
-    const long ow = C0.nl_end, os = ow + N, end = os + nS, nv = (end + 1) & ~1L;
-    const long wz = C0.nl_ws + (kb == 0 ? TPB / 64 + 3 * TPB : 0), ws = wz + wsz;
-    if (nv > INT32_MAX || ws > INT32_MAX) { C0.err = blk + ": too many values per instance"; return SQPHIP_EINVAL; }
-    return guarded(h, [&](Ctx &C) {
-        DV &dv = C.d;
-        const long nv0 = C.nl_nv, B = dv.B;
-        // re-lay the instances' blocks behind what they hold
-        std::vector<double> old((size_t)B * nv0), all((size_t)B * nv, 0.0);
-        d2h(C, old.data(), dv.nlv, old.size());
-        NlpDev P;
-        SQPHIP_HIP_OK(hipMemcpyAsync(&P, dv.nlp, sizeof(NlpDev), hipMemcpyDeviceToHost, C.stream));
-        SQPHIP_HIP_OK(hipStreamSynchronize(C.stream));
-        auto fill = [&](double *v) {
-            for (long i = 0; i < N; ++i) v[ow + i] = weight ? weight[i] : 1.0;
-            for (long i = 0; i < nS; ++i) v[os + i] = shift ? shift[i] : 0.0;
-        };
-        for (long b = 0; b < B; ++b) {
-            std::copy(old.begin() + b * nv0, old.begin() + b * nv0 + C.nl_end, all.begin() + b * nv);
-            fill(all.data() + b * nv);
-        }
-        C.h_nl_base.resize(nv, 0.0);
-        std::fill(C.h_nl_base.begin() + C.nl_end, C.h_nl_base.end(), 0.0);
-        fill(C.h_nl_base.data());
-        std::vector<double> a(A, A + (size_t)N * d), at((size_t)N * d);
-        for (long i = 0; i < N; ++i)
-            for (int j = 0; j < d; ++j) at[(size_t)j * N + i] = a[(size_t)i * d + j];
-        K.N = (int)N; K.d = d; K.ow = (int)ow; K.os = (int)os; K.wz = (int)wz;
-        K.A = C.upload(a); K.At = C.upload(at); K.col = C.upload(cv); K.hs = C.upload(hs);
-        P.blk[kb] = K;
-        P.nblk = kb + 1; P.nv = (int)nv; P.ws = (int)ws;
-        dv.nlv = C.upload(all);
-        dv.nlw = C.dalloc<double>((size_t)B * (size_t)ws);
-        SQPHIP_HIP_OK(hipMemcpyAsync(const_cast<NlpDev *>(dv.nlp), &P, sizeof(NlpDev), hipMemcpyHostToDevice, C.stream));
-        SQPHIP_HIP_OK(hipStreamSynchronize(C.stream));
-        C.nl_nv = nv; C.nl_end = end; C.nl_ws = ws;
-        C.nl_blk.push_back(Ctx::NlBlock{N, ow, os, nS});
-        make_lanes(C);
-        if (blk_out) *blk_out = kb;
-        return SQPHIP_OK;
-    });
-}
-
-extern "C" int sqphip_nlp_add_block(sqphip_ctx *h, int32_t kind, int32_t exp, double par, int64_t N, int32_t d, const int64_t *cols,
-                                    const double *A, const double *shift, const double *weight, int32_t *blk_out)
-{
-    const std::string who = "sqphip_nlp_add_block";
-    if (!h) return SQPHIP_EINVAL;
-    Ctx &C0 = h->c;
-    int kb; std::string blk;
-    if (int rc = nlp_block_begin(h, who, kb, blk)) return rc;
-    auto fail = [&](const std::string &msg) { C0.err = blk + ": " + msg; return (int)SQPHIP_EINVAL; };
-    if (d < 1 || d > NLP_BLOCK_MAX_D) return fail("d = " + std::to_string(d) + " columns (1.." + std::to_string((int)NLP_BLOCK_MAX_D) + ")");
-    if (N < 1) return fail("N = " + std::to_string(N) + " points (at least 1)");
-    if (N > INT32_MAX / d) return fail("N d = " + std::to_string(N) + " x " + std::to_string(d) + " is too large (N d < 2^31)");
-    if (!cols || !A) return fail("null cols or A");
-    if (kind < NLP_POW || kind > NLP_POWR) return fail("unknown kind " + std::to_string(kind));
-    const int e = kind == NLP_POW ? exp : 1;
-    if (kind == NLP_POW && e == 1) return fail("a plain linear block (POW, e = 1) belongs in the terms");
-    if (e == 0 || e > 32 || e < -32) return fail("exponent " + std::to_string(e) + " (1 <= |e| <= 32)");
-    if (kind == NLP_POWR && (!std::isfinite(par) || par == 0.0)) return fail("real exponent " + std::to_string(par) + " (finite and not 0)");
-    std::vector<int> hs, cv;
-    const std::string bad = nlp_block_columns(C0, d, cols, cv, hs);
-    if (!bad.empty()) return fail(bad);
-    NlpBlkDev K = {};
-    K.ke = kind + (e + 32) * (1 << NLP_KIND_BITS);
-    K.par = kind == NLP_POWR ? par : 0.0;
-    return nlp_block_commit(h, blk, kb, (long)N, d, (long)N, 2 * (long)N, A, cv, hs, weight, shift, K, blk_out);
-}
-
-// a multinomial (softmax) block (nlp_softmax_dev.hpp)
-extern "C" int sqphip_nlp_add_softmax_block(sqphip_ctx *h, int64_t N, int32_t d, int32_t K, int32_t pinned, const int64_t *cols,
-                                            const double *A, const int32_t *labels, const double *shift, const double *weight,
-                                            int32_t *blk_out)
-{
-    const std::string who = "sqphip_nlp_add_softmax_block";
-    if (!h) return SQPHIP_EINVAL;
-    Ctx &C0 = h->c;
-    int kb; std::string blk;
-    if (int rc = nlp_block_begin(h, who, kb, blk)) return rc;
-    auto fail = [&](const std::string &msg) { C0.err = blk + ": " + msg; return (int)SQPHIP_EINVAL; };
-    if (K < 2 || K > NLP_SOFTMAX_MAX_K) return fail("K = " + std::to_string(K) + " classes (2.." + std::to_string((int)NLP_SOFTMAX_MAX_K) + ")");
-    if (d < 1) return fail("d = " + std::to_string(d) + " features (at least 1)");
-    const int Kf = pinned ? K - 1 : K;
-    if ((long)Kf * d > NLP_BLOCK_MAX_D)
-        return fail("Kf d = " + std::to_string(Kf) + " x " + std::to_string(d) + " columns (at most " + std::to_string((int)NLP_BLOCK_MAX_D) + ")");
-    if (N < 1) return fail("N = " + std::to_string(N) + " points (at least 1)");
-    if (N > INT32_MAX / d) return fail("N d = " + std::to_string(N) + " x " + std::to_string(d) + " is too large (N d < 2^31)");
-    if (!cols || !A || !labels) return fail("null cols, A or labels");
-    for (int64_t i = 0; i < N; ++i)
-        if (labels[i] < 0 || labels[i] >= K)
-            return fail("point " + std::to_string(i + 1) + ": label " + std::to_string(labels[i]) + " outside 0.." + std::to_string(K - 1));
-    std::vector<int> hs, cv;
-    const std::string bad = nlp_block_columns(C0, Kf * d, cols, cv, hs);
-    if (!bad.empty()) return fail(bad);
-    NlpBlkDev Kb = {};
-    Kb.K = K; Kb.Kf = Kf;
-    const int rc = guarded(h, [&](Ctx &C) { Kb.y = C.upload(std::vector<int>(labels, labels + N)); return SQPHIP_OK; });
-    if (rc) return rc;
-    return nlp_block_commit(h, blk, kb, (long)N, d, (long)Kf * N, (long)Kf * N, A, cv, hs, weight, shift, Kb, blk_out);
-}
-
-// weight / shift of block blk into the block of values v (of an instance or of a scenario of the queue); NULL: kept
-static int nlp_block_put(sqphip_ctx *h, double *v, int32_t blk, const double *weight, const double *shift)
-{
-    return guarded(h, [&](Ctx &C) {
-        const Ctx::NlBlock &K = C.nl_blk[blk];
-        h2d(C, v + K.ow, weight, (size_t)K.N); h2d(C, v + K.os, shift, (size_t)K.nS);
-        SQPHIP_HIP_OK(hipStreamSynchronize(C.stream));
-        return SQPHIP_OK;
-    });
-}
-
-static int nlp_block_check(sqphip_ctx *h, const std::string &who, int32_t blk)
-{
-    Ctx &C = h->c;
-    if (!C.d.nlp) { C.err = who + ": the context has no factorable NLP attached (sqphip_nlp_attach*)"; return SQPHIP_EINVAL; }
-    if (blk < 0 || blk >= (int)C.nl_blk.size()) {
-        C.err = who + ": block " + std::to_string(blk) + " is outside the " + std::to_string(C.nl_blk.size()) + " of the context (sqphip_nlp_add_block)";
-        return SQPHIP_EINVAL;
-    }
-    return SQPHIP_OK;
-}
-
-extern "C" int sqphip_nlp_set_instance_block(sqphip_ctx *h, int32_t inst, int32_t blk, const double *weight, const double *shift)
-{
-    const std::string who = "sqphip_nlp_set_instance_block";
-    if (!h) return SQPHIP_EINVAL;
-    if (int rc = nlp_block_check(h, who, blk)) return rc;
-    if (inst < 0 || inst >= h->c.d.B) {
-        h->c.err = who + ": instance " + std::to_string(inst) + " is outside the batch of " + std::to_string(h->c.d.B);
-        return SQPHIP_EINVAL;
-    }
-    return nlp_block_put(h, h->c.d.nlv + (size_t)inst * h->c.nl_nv, blk, weight, shift);
-}
-
-extern "C" int sqphip_nlp_stream_set_block(sqphip_ctx *h, int32_t scen, int32_t blk, const double *weight, const double *shift)
-{
-    const std::string who = "sqphip_nlp_stream_set_block";
-    if (!h) return SQPHIP_EINVAL;
-    if (int rc = nlp_block_check(h, who, blk)) return rc;
-    if (!h->c.d.stream.val) { h->c.err = who + ": no NLP queue (sqphip_nlp_stream_begin)"; return SQPHIP_EINVAL; }
-    if (scen < 0 || scen >= h->c.d.stream.M) {
-        h->c.err = who + ": scenario " + std::to_string(scen) + " is outside the " + std::to_string(h->c.d.stream.M) + " of the queue";
-        return SQPHIP_EINVAL;
-    }
-    return nlp_block_put(h, const_cast<double *>(h->c.d.stream.val) + (size_t)scen * h->c.nl_nv, blk, weight, shift);
-}
-
 extern "C" int sqphip_acopf_eval(sqphip_ctx *h, int32_t inst, const double *x, double sigma, const double *lambda,
                                  double *f, double *grad, double *g, double *jval, double *hval)
 {
-    if (!h || !h->c.acopf_attached || inst < 0 || inst >= h->c.d.B || !x) return SQPHIP_EINVAL;
+    if (!h || !h->c.evaluator_attached || inst < 0 || inst >= h->c.d.B || !x) return SQPHIP_EINVAL;
     if (hval && !lambda) return SQPHIP_EINVAL;
     return guarded(h, [&](Ctx &C) {
         DV &d = C.d;
@@ -2220,15 +1274,15 @@ extern "C" int sqphip_acopf_eval(sqphip_ctx *h, int32_t inst, const double *x, d
 
 extern "C" int sqphip_sqp_reset(sqphip_ctx *h)
 {
-    if (!h || !h->c.acopf_attached) return SQPHIP_ESTATE;
-    h->c.nl_started = true;
+    if (!h || !h->c.evaluator_attached) return SQPHIP_ESTATE;
+    h->c.nl.started = true;
     return guarded(h, [&](Ctx &C) { sqp_reset(C); return SQPHIP_OK; });
 }
 
 extern "C" int sqphip_sqp_run(sqphip_ctx *h, int32_t max_outer)
 {
-    if (!h || !h->c.acopf_attached) return SQPHIP_ESTATE;
-    h->c.nl_started = true;
+    if (!h || !h->c.evaluator_attached) return SQPHIP_ESTATE;
+    h->c.nl.started = true;
     return guarded(h, [&](Ctx &C) {
         auto t0 = std::chrono::steady_clock::now();
         sqp_run(C, max_outer);
@@ -2454,36 +1508,8 @@ extern "C" int sqphip_sqp_last_request(sqphip_ctx *h, int32_t inst, int32_t *mod
 extern "C" int sqphip_sqp_stream_begin(sqphip_ctx *h, int32_t n_scenarios)
 {
     if (acopf_only(h, "sqphip_sqp_stream_begin")) return SQPHIP_EINVAL;
-    if (!h || !h->c.acopf_attached || n_scenarios <= 0) return SQPHIP_EINVAL;
-    return guarded(h, [&](Ctx &C) {
-        DV &d = C.d;
-        StreamDev &Q = d.stream;
-        const size_t M = (size_t)n_scenarios;
-        Q.M = n_scenarios;
-        Q.next = C.dalloc<int>(1); Q.slot_scen = C.dalloc<int>((size_t)d.B);
-        Q.qend = C.dalloc<int>(1);
-        {   // hand-out order: identity, all M scenarios (sqphip_sqp_stream_assign changes it)
-            std::vector<int> ids(M);
-            for (size_t k = 0; k < M; ++k) ids[k] = (int)k;
-            Q.qids = C.upload(ids);
-            SQPHIP_HIP_OK(hipMemcpyAsync(Q.qend, &Q.M, sizeof(int), hipMemcpyHostToDevice, C.stream));
-        }
-        C.stream_started = false;
-        Q.xL = C.dalloc<double>(M * d.n); Q.xU = C.dalloc<double>(M * d.n); Q.x0 = C.dalloc<double>(M * d.n);
-        Q.gL = C.dalloc<double>(M * d.m); Q.gU = C.dalloc<double>(M * d.m);
-        Q.ohm = C.dalloc<double>(M * d.nl * 12); Q.c2 = C.dalloc<double>(M * d.ng); Q.c1 = C.dalloc<double>(M * d.ng);
-        Q.rx = C.dalloc<double>(M * d.n); Q.robj = C.dalloc<double>(M);
-        Q.rstat = C.dalloc<int>(M); Q.riter = C.dalloc<int>(M);
-        // every slot starts as "queue exhausted" (-1): the stage kernel's queue step stays off until
-        // sqphip_sqp_stream_run arms the slots (-2), so a plain sqp_reset / sqp_run between _begin and _stream_run
-        // behaves as if no queue existed (dalloc zero-fills, and 0 is a valid scenario id)
-        SQPHIP_HIP_OK(hipMemsetAsync(Q.slot_scen, 0xff, sizeof(int) * (size_t)d.B, C.stream));
-        // riter = -1: "no result filed by this context" (sqphip_sqp_stream_get; reset by _stream_run and _stream_assign)
-        SQPHIP_HIP_OK(hipMemsetAsync(Q.riter, 0xff, sizeof(int) * M, C.stream));
-        SQPHIP_HIP_OK(hipStreamSynchronize(C.stream));
-        make_lanes(C);
-        return SQPHIP_OK;
-    });
+    if (!h || !h->c.evaluator_attached || n_scenarios <= 0) return SQPHIP_EINVAL;
+    return stream_begin(h, n_scenarios, 0, -1);      // (api_models.hip: the tables of the three kinds of queue)
 }
 
 extern "C" int sqphip_sqp_stream_set(sqphip_ctx *h, int32_t scen, const double *xL, const double *xU, const double *gL,
@@ -2516,7 +1542,7 @@ extern "C" int sqphip_sqp_stream_set(sqphip_ctx *h, int32_t scen, const double *
 
 extern "C" int sqphip_sqp_stream_run(sqphip_ctx *h)
 {
-    if (!h || !h->c.acopf_attached || h->c.d.stream.M <= 0) return SQPHIP_ESTATE;
+    if (!h || !h->c.evaluator_attached || h->c.d.stream.M <= 0) return SQPHIP_ESTATE;
     return guarded(h, [&](Ctx &C) {
         auto t0 = std::chrono::steady_clock::now();
         SQPHIP_HIP_OK(hipMemsetAsync(C.d.stream.next, 0, sizeof(int), C.stream));
@@ -2596,7 +1622,7 @@ extern "C" int sqphip_sqp_stream_release(sqphip_ctx *h, int32_t n, int32_t *ids_
 // n_unstarted = ids of this rank's queue nobody has drawn yet, n_active = slots with a run in progress
 extern "C" int sqphip_sqp_stream_run_some(sqphip_ctx *h, int32_t max_outer, int32_t *n_unstarted, int32_t *n_active)
 {
-    if (!h || !h->c.acopf_attached || h->c.d.stream.M <= 0 || max_outer < 1) return SQPHIP_ESTATE;
+    if (!h || !h->c.evaluator_attached || h->c.d.stream.M <= 0 || max_outer < 1) return SQPHIP_ESTATE;
     return guarded(h, [&](Ctx &C) {
         auto t0 = std::chrono::steady_clock::now();
         if (!C.stream_started) { sqp_stream_arm(C); C.stream_started = true; }
@@ -2634,158 +1660,6 @@ extern "C" int sqphip_sqp_stream_get(sqphip_ctx *h, int32_t scen, double *x, dou
         SQPHIP_HIP_OK(hipStreamSynchronize(C.stream));
         if (status) *status = st;
         if (iter) *iter = it;
-        return SQPHIP_OK;
-    });
-}
-
-// ---- the queue on a QCQP or factorable-NLP context: a scenario is one block of values in the layout of DV::qcv / DV::nlv, so
-// that the loader of the stage kernel (sqp_dev.hpp, b_sqp_stream) is one streaming copy; _run / _run_some / _assign / _append /
-// _release / _get are shared.  The tables of a queue of n_scenarios blocks of nv doubles:
-static int value_stream_begin(sqphip_ctx *h, int32_t n_scenarios, int32_t keep_multipliers, long nv)
-{
-    return guarded(h, [&](Ctx &C) {
-        DV &d = C.d;
-        StreamDev Q = {};
-        const size_t M = (size_t)n_scenarios;
-        Q.M = n_scenarios;
-        Q.next = C.dalloc<int>(1); Q.slot_scen = C.dalloc<int>((size_t)d.B);
-        Q.qend = C.dalloc<int>(1);
-        {   // hand-out order: identity, all M scenarios (sqphip_sqp_stream_assign changes it)
-            std::vector<int> ids(M);
-            for (size_t k = 0; k < M; ++k) ids[k] = (int)k;
-            Q.qids = C.upload(ids);
-            SQPHIP_HIP_OK(hipMemcpyAsync(Q.qend, &Q.M, sizeof(int), hipMemcpyHostToDevice, C.stream));
-        }
-        C.stream_started = false;
-        Q.xL = C.dalloc<double>(M * d.n); Q.xU = C.dalloc<double>(M * d.n); Q.x0 = C.dalloc<double>(M * d.n);
-        Q.gL = C.dalloc<double>(M * d.m); Q.gU = C.dalloc<double>(M * d.m);
-        Q.val = C.dalloc<double>(M * (size_t)nv);
-        Q.rx = C.dalloc<double>(M * d.n); Q.robj = C.dalloc<double>(M);
-        Q.rstat = C.dalloc<int>(M); Q.riter = C.dalloc<int>(M);
-        if (keep_multipliers) {
-            Q.rE = C.dalloc<double>(M * d.m); Q.rlam = C.dalloc<double>(M * d.m);
-            Q.rmxL = C.dalloc<double>(M * d.n); Q.rmxU = C.dalloc<double>(M * d.n);
-        }
-        // slots "queue exhausted" (-1) until a _stream_run arms them; riter = -1: nothing filed (as sqphip_sqp_stream_begin)
-        SQPHIP_HIP_OK(hipMemsetAsync(Q.slot_scen, 0xff, sizeof(int) * (size_t)d.B, C.stream));
-        SQPHIP_HIP_OK(hipMemsetAsync(Q.riter, 0xff, sizeof(int) * M, C.stream));
-        SQPHIP_HIP_OK(hipStreamSynchronize(C.stream));
-        d.stream = Q;
-        make_lanes(C);
-        return SQPHIP_OK;
-    });
-}
-
-// the checks of a scenario that both value queues share (fn: the entry point, for the message); NULL bounds become those
-// of sqphip_create
-static int value_stream_check(sqphip_ctx *h, const char *fn, int32_t scen, const double *&xL, const double *&xU,
-                              const double *&gL, const double *&gU, const double *x0)
-{
-    const std::string f(fn);
-    if (scen < 0 || scen >= h->c.d.stream.M) {
-        h->c.err = f + ": scenario " + std::to_string(scen) + " is outside the " + std::to_string(h->c.d.stream.M) + " of the queue";
-        return SQPHIP_EINVAL;
-    }
-    if (!x0) { h->c.err = f + ": x0 is NULL (a scenario needs its start)"; return SQPHIP_EINVAL; }
-    if (!xL) xL = h->c.h_xL.data();
-    if (!xU) xU = h->c.h_xU.data();
-    if (!gL) gL = h->c.h_gL.data();
-    if (!gU) gU = h->c.h_gU.data();
-    for (int i = 0; i < h->c.d.m; ++i) {
-        if (gL[i] == -INFINITY && gU[i] == INFINITY) {
-            h->c.err = f + ": row " + std::to_string(i) + " is unbounded on both sides";
-            return SQPHIP_EINVAL;
-        }
-        if (h->c.d.condense && gL[i] == gU[i] && h->c.h_kpos[i] < 0) {
-            h->c.err = f + ": row " + std::to_string(i) + " is an equality for this scenario but was not one when "
-                       "the context was created (options.kkt_condense = 1 fixes the kept rows)";
-            return SQPHIP_EINVAL;
-        }
-    }
-    return SQPHIP_OK;
-}
-
-// ... and the upload: bounds, start and the block v of nv values
-static int value_stream_upload(sqphip_ctx *h, int32_t scen, const double *xL, const double *xU, const double *gL,
-                               const double *gU, const double *x0, const std::vector<double> &v)
-{
-    return guarded(h, [&](Ctx &C) {
-        DV &d = C.d;
-        const StreamDev &Q = d.stream;
-        const size_t s = (size_t)scen;
-        h2d(C, const_cast<double *>(Q.xL) + s * d.n, xL, d.n); h2d(C, const_cast<double *>(Q.xU) + s * d.n, xU, d.n);
-        h2d(C, const_cast<double *>(Q.x0) + s * d.n, x0, d.n);
-        h2d(C, const_cast<double *>(Q.gL) + s * d.m, gL, d.m); h2d(C, const_cast<double *>(Q.gU) + s * d.m, gU, d.m);
-        h2d(C, const_cast<double *>(Q.val) + s * v.size(), v.data(), v.size());
-        SQPHIP_HIP_OK(hipStreamSynchronize(C.stream));
-        return SQPHIP_OK;
-    });
-}
-
-extern "C" int sqphip_qcqp_stream_begin(sqphip_ctx *h, int32_t n_scenarios, int32_t keep_multipliers)
-{
-    if (!h) return SQPHIP_EINVAL;
-    if (!h->c.d.qc) { h->c.err = "sqphip_qcqp_stream_begin: the context has no QCQP attached (sqphip_qcqp_attach)"; return SQPHIP_EINVAL; }
-    if (n_scenarios <= 0) { h->c.err = "sqphip_qcqp_stream_begin: n_scenarios must be positive"; return SQPHIP_EINVAL; }
-    return value_stream_begin(h, n_scenarios, keep_multipliers, h->c.qc_nv);
-}
-
-extern "C" int sqphip_qcqp_stream_set(sqphip_ctx *h, int32_t scen, const double *xL, const double *xU, const double *gL,
-                                      const double *gU, const double *f0, const double *c, const double *q0v,
-                                      const double *g0, const double *av, const double *qv, const double *x0)
-{
-    if (!h) return SQPHIP_EINVAL;
-    if (!h->c.d.qc || !h->c.d.stream.val) { h->c.err = "sqphip_qcqp_stream_set: no QCQP queue (sqphip_qcqp_stream_begin)"; return SQPHIP_EINVAL; }
-    if (int rc = value_stream_check(h, "sqphip_qcqp_stream_set", scen, xL, xU, gL, gU, x0)) return rc;
-    // the scenario's block: the values of the attach, overlaid with the parts given (f0 | c | Q0 | g0 | A | Q)
-    std::vector<double> v(h->c.h_qc_base);
-    const long *o = h->c.qc_off;
-    const double *src[6] = {f0, c, q0v, g0, av, qv};
-    for (int k = 0; k < 6; ++k) if (src[k]) std::copy(src[k], src[k] + (o[k + 1] - o[k]), v.begin() + o[k]);
-    return value_stream_upload(h, scen, xL, xU, gL, gU, x0, v);
-}
-
-// ---- the queue on a factorable-NLP context: the same tables, the block in the layout of DV::nlv (f0 | g0 | c, on a context
-// of sqphip_nlp_attach_data | b | a | p; padded to even)
-extern "C" int sqphip_nlp_stream_begin(sqphip_ctx *h, int32_t n_scenarios, int32_t keep_multipliers)
-{
-    if (!h) return SQPHIP_EINVAL;
-    if (!h->c.d.nlp) { h->c.err = "sqphip_nlp_stream_begin: the context has no factorable NLP attached (sqphip_nlp_attach)"; return SQPHIP_EINVAL; }
-    if (n_scenarios <= 0) { h->c.err = "sqphip_nlp_stream_begin: n_scenarios must be positive"; return SQPHIP_EINVAL; }
-    h->c.nl_started = true;
-    return value_stream_begin(h, n_scenarios, keep_multipliers, h->c.nl_nv);
-}
-
-extern "C" int sqphip_nlp_stream_set(sqphip_ctx *h, int32_t scen, const double *xL, const double *xU, const double *gL,
-                                     const double *gU, const double *f0, const double *g0, const double *tcoef,
-                                     const double *x0)
-{
-    if (!h) return SQPHIP_EINVAL;
-    if (!h->c.d.nlp || !h->c.d.stream.val) { h->c.err = "sqphip_nlp_stream_set: no NLP queue (sqphip_nlp_stream_begin)"; return SQPHIP_EINVAL; }
-    if (int rc = value_stream_check(h, "sqphip_nlp_stream_set", scen, xL, xU, gL, gU, x0)) return rc;
-    // the scenario's block: the values of the attach, overlaid with the parts given
-    std::vector<double> v(h->c.h_nl_base);
-    const long m = h->c.d.m;
-    if (f0) v[0] = *f0;
-    if (g0) std::copy(g0, g0 + m, v.begin() + 1);
-    if (tcoef) std::copy(tcoef, tcoef + h->c.nl_nterms, v.begin() + 1 + m);
-    return value_stream_upload(h, scen, xL, xU, gL, gU, x0, v);
-}
-
-extern "C" int sqphip_nlp_stream_set_data(sqphip_ctx *h, int32_t scen, const double *fshift, const double *acoef, const double *fpar)
-{
-    const char *who = "sqphip_nlp_stream_set_data";
-    if (!h) return SQPHIP_EINVAL;
-    if (int rc = nlp_data_check(h, who, nullptr, nullptr, nullptr)) return rc;
-    if (!h->c.d.stream.val) { h->c.err = std::string(who) + ": no NLP queue (sqphip_nlp_stream_begin)"; return SQPHIP_EINVAL; }
-    if (scen < 0 || scen >= h->c.d.stream.M) {
-        h->c.err = std::string(who) + ": scenario " + std::to_string(scen) + " is outside the " + std::to_string(h->c.d.stream.M) + " of the queue";
-        return SQPHIP_EINVAL;
-    }
-    if (int rc = nlp_data_check(h, who, fshift, acoef, fpar)) return rc;
-    return guarded(h, [&](Ctx &C) {
-        nlp_data_upload(C, const_cast<double *>(C.d.stream.val) + (size_t)scen * C.nl_nv, fshift, acoef, fpar);
-        SQPHIP_HIP_OK(hipStreamSynchronize(C.stream));
         return SQPHIP_OK;
     });
 }

@@ -8,6 +8,7 @@
 #include "../../include/sqphip_test_hooks.h"
 #include "sqphip_internal.hpp"
 #include "sparse.hpp"
+#include "model_plans.hpp"
 
 namespace sqphip {
 
@@ -275,26 +276,10 @@ struct Ctx {
     long stg_doubles = 0;
     std::vector<int> h_kpos;    // host copy of DV::kpos (row -> kept position or -1)
     std::vector<int64_t> h_jrow, h_jcol, h_hrow, h_hcol;   // host copies of the COO structures of sqphip_create (1-based)
-    long qc_nv = 0;             // doubles per instance of an attached QCQP (DV::qcv; even: the blocks are 16-byte aligned) ...
-    long qc_off[7] = {};        // ... and where its parts start: f0, c, Q0, g0, A, Q, end
-    std::vector<double> h_qc_base;              // ... the values given to sqphip_qcqp_attach (NULL parts of a queue scenario)
-    long nl_nv = 0, nl_nfac = 0, nl_nterms = 0; // doubles per instance of an attached factorable NLP (DV::nlv: f0 | g0 | c, padded to even), its factors and terms
-    std::vector<double> h_nl_base;              // ... the values given to sqphip_nlp_attach (NULL parts of a queue scenario)
-    // sqphip_nlp_attach_data: the block goes on with b [nfac] | a [nargs] | p [nfac, with a POWR factor only] at nl_ob, nl_oa,
-    // nl_op (-1: no p); what the value checks of sqphip_nlp_set_instance_data / _stream_set_data need of the structure
-    bool nl_data = false;
-    long nl_ob = 0, nl_oa = 0, nl_op = -1, nl_nargs = 0;
-    std::vector<int> h_nl_tptr, h_nl_aptr, h_nl_kind;   // [nterms + 1], [nfac + 1], [nfac]
-    std::vector<int> h_nl_lin;                          // the terms of rows 1..num_linear
-    // sqphip_nlp_add_block: dense data blocks behind those segments, W_k [N_k] | S_k [N_k] each (S_k [Kf N_k] for a softmax block; nl_end: doubles in use before
-    // the padding to even); nl_ws: doubles of workspace per instance (DV::nlw); nl_started: a reset, run or queue has seen the
-    // layout, which is final from then on
-    struct NlBlock { long N, ow, os, nS; };      // nS: doubles of S (N; Kf N for a softmax block)
-    std::vector<NlBlock> nl_blk;
-    long nl_end = 0, nl_ws = 0;
-    bool nl_started = false;
+    QcqpHost qc;                // what sqphip_qcqp_attach keeps on the host (model_plans.hpp): the stride of DV::qcv, the parts of a block, the attach's values
+    NlpHost nl;                 // ... and sqphip_nlp_attach*: the stride of DV::nlv / DV::nlw, the layout with data and blocks, what the data checks need
     std::vector<double> h_xL, h_xU, h_gL, h_gU; // the bounds given to sqphip_create (NULL bounds of a queue scenario)
-    bool acopf_attached = false;
+    bool evaluator_attached = false;   // some *_attach has given the batched run! its device callbacks
     bool mf_big_lds = false;        // the multifrontal kernels were granted 160 KB of dynamic LDS on this context's device (mf_device_setup)
     bool stream_started = false;    // scenario queue: the slots have been armed (sqphip_sqp_stream_run / _run_some)
     // RCCL communicator for the status gather (comm.hip); null: single rank

@@ -23,7 +23,7 @@
 // slot, the neighbours or the instance groups.  They are not the bits of the same model written as per-point terms
 // (another order of the sums); tests/nlp_block_ref.py states the forward error bound both meet.
 // The function takes pointers and scalars only, never DV, and is out of line: the kernels that inline nlp_eval (k_sqp_begin,
-// k_sqp_stage, k_ipm_post_ride, k_armijo_nlp, k_acopf_eval_point) get one call behind a branch uniform over the launch.
+// k_sqp_stage, k_ipm_post_ride, k_armijo<ARMIJO_NLP>, k_acopf_eval_point) get one call behind a branch uniform over the launch.
 #pragma once
 // (NlpBlkDev: nlp_dev.hpp, in front of NlpDev, which holds the blocks)
 

@@ -47,9 +47,7 @@
 
 namespace sqphip {
 
-enum { NLP_POW = 0, NLP_SIN = 1, NLP_COS = 2, NLP_EXP = 3, NLP_LOG = 4,
-       NLP_SQRT = 5, NLP_TANH = 6, NLP_ATAN = 7, NLP_SIGMOID = 8, NLP_SOFTPLUS = 9, NLP_POWR = 10 };
-enum { NLP_KIND_BITS = 4, NLP_KIND_MASK = (1 << NLP_KIND_BITS) - 1 };     // fke = kind + 16 * (exponent + 32)
+// (the kinds NLP_POW .. NLP_POWR and NLP_KIND_BITS / _MASK: model_plans.hpp, shared with the host-side plan builder)
 enum { NLP_NONE = -(1 << 30), NLP_ARG = (1 << 28) - 1 };     // no factor of a term; the argument bits of a plan entry (nargs <= 2^28)
 
 // a dense data block of the objective (sqphip_nlp_add_block; evaluator: nlp_block_dev.hpp, included below)

@@ -342,8 +342,11 @@ __global__ __launch_bounds__(TPB) void k_merit_batch(DV d, const int *inst, int 
 // compute_alpha (sqp_line_search.jl:303-334) on the device: x and p of instance `inst` are staged in d.x / d.pstep;
 // out[0] = alpha, out[1] = is_valid, out[2] = merit evaluations.  One workgroup; the merit function is
 // compute_phi (sqp.jl:170-183) over the device callbacks, its norms reduced by wave butterflies + an LDS exchange.
-// (This kernel sits at the VGPR cap: with the QCQP branch of acopf_eval inlined it spilled more, so it evaluates through
-// the dedicated dispatch and k_armijo_qcqp / k_armijo_nlp below serve QCQP and factorable-NLP contexts)
+// (One body, three instantiations by evaluator: k_armijo<ARMIJO_DEDICATED> sits at the VGPR cap -- with the QCQP branch of
+// acopf_eval inlined it spilled more --, so it evaluates through the dedicated dispatch, and k_armijo<ARMIJO_QCQP> /
+// k_armijo<ARMIJO_NLP> serve QCQP (sqphip_qcqp_attach) and factorable-NLP (sqphip_nlp_attach) contexts)
+enum { ARMIJO_DEDICATED = 0, ARMIJO_QCQP = 1, ARMIJO_NLP = 2 };
+template <int KIND>
 __global__ __launch_bounds__(TPB) void k_armijo(DV d, int inst, double mu, double phi0, double D, double eta, double tau,
                                                 double min_alpha, int fr, double *out)
 {
@@ -356,61 +359,9 @@ __global__ __launch_bounds__(TPB) void k_armijo(DV d, int inst, double mu, doubl
         for (;;) {
             for (int j = threadIdx.x; j < d.n; j += TPB) tmpx[j] = x[j] + alpha * ps[j];
             __syncthreads();
-            acopf_eval_dedicated(d, inst, tmpx, 1.0, nullptr, &fsh, nullptr, tmpE, nullptr, nullptr);
-            __syncthreads();
-            const double v = viol1(d, tmpE, gL, gU, tmpx, xL, xU);
-            const double phi = fr ? v : fsh + mu * v;
-            ++nev;
-            if (!(phi > phi0 + eta * alpha * D)) break;
-            if (alpha < min_alpha) { valid = 0; break; }     // the step size can become too small
-            alpha *= tau;
-            __syncthreads();
-        }
-    }
-    if (threadIdx.x == 0) { out[0] = alpha; out[1] = valid; out[2] = nev; }
-}
-
-// the same on a QCQP context (sqphip_qcqp_attach)
-__global__ __launch_bounds__(TPB) void k_armijo_qcqp(DV d, int inst, double mu, double phi0, double D, double eta, double tau,
-                                                     double min_alpha, int fr, double *out)
-{
-    SQP_PTRS
-    const double pn = norm_inf(ps, d.n);
-    double alpha = 1.0;
-    int valid = 1, nev = 0;
-    if (!(pn <= d.tol_direction)) {
-        __shared__ double fsh;
-        for (;;) {
-            for (int j = threadIdx.x; j < d.n; j += TPB) tmpx[j] = x[j] + alpha * ps[j];
-            __syncthreads();
-            qcqp_eval(d, inst, tmpx, 1.0, nullptr, &fsh, nullptr, tmpE, nullptr, nullptr);
-            __syncthreads();
-            const double v = viol1(d, tmpE, gL, gU, tmpx, xL, xU);
-            const double phi = fr ? v : fsh + mu * v;
-            ++nev;
-            if (!(phi > phi0 + eta * alpha * D)) break;
-            if (alpha < min_alpha) { valid = 0; break; }     // the step size can become too small
-            alpha *= tau;
-            __syncthreads();
-        }
-    }
-    if (threadIdx.x == 0) { out[0] = alpha; out[1] = valid; out[2] = nev; }
-}
-
-// the same on a factorable-NLP context (sqphip_nlp_attach)
-__global__ __launch_bounds__(TPB) void k_armijo_nlp(DV d, int inst, double mu, double phi0, double D, double eta, double tau,
-                                                     double min_alpha, int fr, double *out)
-{
-    SQP_PTRS
-    const double pn = norm_inf(ps, d.n);
-    double alpha = 1.0;
-    int valid = 1, nev = 0;
-    if (!(pn <= d.tol_direction)) {
-        __shared__ double fsh;
-        for (;;) {
-            for (int j = threadIdx.x; j < d.n; j += TPB) tmpx[j] = x[j] + alpha * ps[j];
-            __syncthreads();
-            nlp_eval(d, inst, tmpx, 1.0, nullptr, &fsh, nullptr, tmpE, nullptr, nullptr);
+            if constexpr (KIND == ARMIJO_NLP) nlp_eval(d, inst, tmpx, 1.0, nullptr, &fsh, nullptr, tmpE, nullptr, nullptr);
+            else if constexpr (KIND == ARMIJO_QCQP) qcqp_eval(d, inst, tmpx, 1.0, nullptr, &fsh, nullptr, tmpE, nullptr, nullptr);
+            else acopf_eval_dedicated(d, inst, tmpx, 1.0, nullptr, &fsh, nullptr, tmpE, nullptr, nullptr);
             __syncthreads();
             const double v = viol1(d, tmpE, gL, gU, tmpx, xL, xU);
             const double phi = fr ? v : fsh + mu * v;
@@ -428,7 +379,7 @@ void armijo_eval(Ctx &C, int inst, double mu, double phi0, double D, double eta,
                  double *out3_host)
 {
     double *o = C.d.wN + (size_t)inst * C.d.Npad;     // scratch slots
-    hipLaunchKernelGGL(C.d.nlp ? k_armijo_nlp : C.d.qc ? k_armijo_qcqp : k_armijo, dim3(1), dim3(TPB), 0, C.stream, C.d, inst, mu, phi0, D, eta, tau,
+    hipLaunchKernelGGL(C.d.nlp ? k_armijo<ARMIJO_NLP> : C.d.qc ? k_armijo<ARMIJO_QCQP> : k_armijo<ARMIJO_DEDICATED>, dim3(1), dim3(TPB), 0, C.stream, C.d, inst, mu, phi0, D, eta, tau,
                        min_alpha, fr, o);
     SQPHIP_HIP_OK(hipMemcpyAsync(out3_host, o, 3 * sizeof(double), hipMemcpyDeviceToHost, C.stream));
     SQPHIP_HIP_OK(hipStreamSynchronize(C.stream));

@@ -1,4 +1,4 @@
-"""Cases for the general sparse QCQP path (sqphip_qcqp_attach, csrc/qcqp_dev.hpp qcqp_eval, k_armijo_qcqp and the device SQP
+"""Cases for the general sparse QCQP path (sqphip_qcqp_attach, csrc/qcqp_dev.hpp qcqp_eval, k_armijo<ARMIJO_QCQP> and the device SQP
 loop on a QCQP context) at the edges of the plan builder and past one stride of the 1024-thread workgroup.  Used by
 tests/test_qcqp_cases_cpu.py (no GPU) and tests/test_gpu_qcqp_cases.py.
 

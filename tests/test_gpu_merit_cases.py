@@ -1,6 +1,6 @@
 """The merit and line-search seat (`sqphip_norm_violations`, `_kt_residuals`, `_norm_complementarity`, `_compute_phi`,
 `_compute_qmodel`, `_compute_derivative`, `_compute_derivative_full`, `_compute_mu_rule_dev`, their `*_batch` forms and
-`sqphip_acopf_armijo`) on the structures of tests/merit_cases.py: k_merit, k_merit_batch, k_armijo / _qcqp / _nlp of
+`sqphip_acopf_armijo`) on the structures of tests/merit_cases.py: k_merit, k_merit_batch, the three k_armijo<KIND> of
 csrc/sqp.hip and k_seat_stage of csrc/api.hip at sizes around one wave (64), one workgroup (1024 threads, the stride of every
 loop of merit_body) and beyond two strides, with no rows, repeated COO entries, empty rows and columns, a completely dense
 Hessian, a null Hval, equal / one-sided / infinite bounds, values exactly on a bound and a staged field longer than one

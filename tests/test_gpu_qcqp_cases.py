@@ -1,4 +1,4 @@
-"""The general sparse QCQP path on the device (sqphip_qcqp_attach's plan builder, csrc/qcqp_dev.hpp qcqp_eval, k_armijo_qcqp,
+"""The general sparse QCQP path on the device (sqphip_qcqp_attach's plan builder, csrc/qcqp_dev.hpp qcqp_eval, k_armijo<ARMIJO_QCQP>,
 the SQP loop and the scenario queue on a QCQP context) on the cases of tests/qcqp_cases.py:
 
     plan edges      the hand-made edge model and its variants (no Q0 terms, no A terms, no Hessian structure), both
@@ -105,7 +105,7 @@ def _raw(ctx, inst, p, want, lam=True):
 
 def test_partial_outputs_are_the_bits_of_the_full_call(stride):
     """All outputs, all but the Hessian with lambda = NULL (the loop before its first multipliers) and f and g alone (what
-    k_armijo_qcqp asks of qcqp_eval).  An all-outputs call at another point goes before each, so that an entry a partial
+    k_armijo<ARMIJO_QCQP> asks of qcqp_eval).  An all-outputs call at another point goes before each, so that an entry a partial
     call failed to write shows as a value of the wrong point."""
     cs, ctx = stride
     p = cs.point
