@@ -560,12 +560,26 @@ __device__ __forceinline__ void wave_sync_lds()
     __builtin_amdgcn_wave_barrier();
 }
 
-// LDS of the static front kernel (doubles): [image R x R (LDSIMG), later the rows of L: 16 x R][scaled diagonal tile 256]
-// [4 x 10 block records][1 / D: R][one 64-entry scratch per wave]
-__host__ __device__ constexpr int mf_front_lds_doubles(int T, int NW, bool ldsimg)
+// LDS of the static front kernel (doubles): [image (LDSIMG), later the rows of L: 16 x R][scaled diagonal tile 256]
+// [4 x 10 block records][1 / D: R][one 64-entry scratch per wave].  The image is R x R, column-major, or -- PACKED, the level
+// launches' default (SQPHIP_MF_FRONT_PACKED=0: square) -- the T (T + 1) / 2 lower-triangular tiles in the layout of mf_pk: nothing
+// is assembled above the diagonal tiles and only those are loaded, a wave's tile load is 64 consecutive doubles per register
+// (no bank conflicts; col * R + row has 2- and 4-way ones at R = 64, 96, 128), and a CU holds more workgroups: 35.8 instead of
+// 56.3 KB at <5, 4>, 64.7 instead of 107.7 KB at <7, 8>.  The spine kernel keeps the square image.
+// mf_front_img_doubles: the first area, i.e. the offset of everything behind it -- the one place that knows it.
+__host__ __device__ constexpr int mf_front_img_doubles(int T, bool ldsimg, bool packed)
 {
-    const int R = 16 * T, u = (ldsimg ? R * R : 0) > 16 * R ? R * R : 16 * R;
-    return u + 256 + 40 + R + 64 * NW;
+    const int R = 16 * T, img = !ldsimg ? 0 : packed ? 128 * T * (T + 1) : R * R;
+    return img > 16 * R ? img : 16 * R;
+}
+// (the rows of L overlay the start of the image area: the packed image must hold them at every T)
+__host__ __device__ constexpr bool mf_front_img_holds_rows(int T) { return 128 * T * (T + 1) >= 16 * 16 * T; }
+static_assert(mf_front_img_holds_rows(1) && mf_front_img_holds_rows(2) && mf_front_img_holds_rows(3) && mf_front_img_holds_rows(4) &&
+              mf_front_img_holds_rows(5) && mf_front_img_holds_rows(6) && mf_front_img_holds_rows(7) && mf_front_img_holds_rows(8),
+              "packed image: 128 T (T + 1) >= 16 R for every T with an LDS image (equality at T = 1)");
+__host__ __device__ constexpr int mf_front_lds_doubles(int T, int NW, bool ldsimg, bool packed = false)
+{
+    return mf_front_img_doubles(T, ldsimg, packed) + 256 + 40 + 16 * T + 64 * NW;
 }
 
 // What wave W of NW does for one front of T tile rows, in three pieces over the same accumulator registers (the static
@@ -580,9 +594,10 @@ template <int T, int NW, int W> struct MfTileSet {
 // (the tiles travel between the pieces as a struct: a reference-to-array parameter of a vector type does not parse)
 template <int T, int NW, int W> struct MfAcc { d4 v[MfTileSet<T, NW, W>::NTILES]; };
 
-template <int T, int NW, int W, bool LDSIMG>
+template <int T, int NW, int W, bool LDSIMG, bool PACKED = false>
 __device__ __forceinline__ void mf_front_load(MfAcc<T, NW, W> &A, const double *F, int LD, int fs, int lane)
 {
+    static_assert(LDSIMG || !PACKED, "the packed layout is that of the LDS image");
     auto &acc = A.v;
     constexpr int NROWS = MfTileSet<T, NW, W>::NROWS;
     const int l15 = lane & 15, l4 = lane >> 4;
@@ -596,7 +611,7 @@ __device__ __forceinline__ void mf_front_load(MfAcc<T, NW, W> &A, const double *
             for (int rr = 0; rr < 4; ++rr) {
                 const int col = 16 * tj + l4 + 4 * rr, row = 16 * ti + l15;
                 const bool in = LDSIMG || (row <= fs && col < fs);
-                acc[o + tj][rr] = in ? F[col * LD + row] : 0.0;
+                acc[o + tj][rr] = in ? F[PACKED ? 256 * (ti * (ti + 1) / 2 + tj) + 64 * rr + lane : col * LD + row] : 0.0;
             }
         o += ti + 1;
     }
@@ -612,13 +627,12 @@ template <bool LDSBAR> __device__ __forceinline__ void mf_elim_barrier() { if co
 
 // L part (columns below nc) of tile column tk of this wave's tiles, out of the registers: final once step tk of the elimination
 // has solved the tiles below the diagonal tile (EARLY, below).  The expressions are those of mf_front_store.
-template <int T, int NW, int W, bool LDSIMG>
+template <int T, int NW, int W, bool LDSIMG, bool PACKED = false>
 __device__ __forceinline__ void mf_front_store_col(const MfAcc<T, NW, W> &A, int tk, double *G, int ld, int fs, int nc, int with_rhs,
                                                    const double *lds, double *vv, int lane)
 {
     const auto &acc = A.v;
-    constexpr int R = 16 * T;
-    constexpr int U = (LDSIMG ? R * R : 0) > 16 * R ? R * R : 16 * R;
+    constexpr int U = mf_front_img_doubles(T, LDSIMG, PACKED);
     constexpr int NROWS = MfTileSet<T, NW, W>::NROWS;
     const double *dl = lds + U + 256 + 40;
     const int l15 = lane & 15, l4 = lane >> 4;
@@ -654,13 +668,13 @@ __device__ __forceinline__ void mf_front_store_col(const MfAcc<T, NW, W> &A, int
 // in one burst behind the last step -- the stores (5 000 - 7 000 cycles of issue per 80-column front: cycle stamps) then overlap
 // with the remaining steps.  The barriers of the loop must then wait for LDS traffic only (a __syncthreads() waits for the
 // stores in flight too).  Same values to the same places.
-template <int T, int NW, int W, bool LDSIMG, bool LDSBAR = false, bool EARLY = false>
+template <int T, int NW, int W, bool LDSIMG, bool LDSBAR = false, bool EARLY = false, bool PACKED = false>
 __device__ __forceinline__ void mf_front_elim(MfAcc<T, NW, W> &A, int nc, double *lds, int lane, int trs, double *G = nullptr, int ld = 0,
                                               int fs = 0, int with_rhs = 0, double *vv = nullptr)
 {
     auto &acc = A.v;
     constexpr int R = 16 * T;
-    constexpr int U = (LDSIMG ? R * R : 0) > 16 * R ? R * R : 16 * R;
+    constexpr int U = mf_front_img_doubles(T, LDSIMG, PACKED);
     constexpr int NROWS = MfTileSet<T, NW, W>::NROWS;
     double *Lp = lds, *dtile = lds + U, *rec = dtile + 256, *dl = rec + 40, *dsc = dl + R + 64 * W;
     const int l15 = lane & 15, l4 = lane >> 4;
@@ -779,7 +793,7 @@ __device__ __forceinline__ void mf_front_elim(MfAcc<T, NW, W> &A, int nc, double
                 o += ti + 1;
             }
         }
-        if constexpr (EARLY) mf_front_store_col<T, NW, W, LDSIMG>(A, tk, G, ld, fs, nc, with_rhs, lds, vv, lane);
+        if constexpr (EARLY) mf_front_store_col<T, NW, W, LDSIMG, PACKED>(A, tk, G, ld, fs, nc, with_rhs, lds, vv, lane);
     }
 }
 
@@ -787,13 +801,12 @@ __device__ __forceinline__ void mf_front_elim(MfAcc<T, NW, W> &A, int nc, double
 // hands the block to the parent front in registers instead: mf_front_scatter)
 // CB / ldcb: where the contribution block goes -- entry (row, col) of the front to CB[col * ldcb + row]: the front's own
 // storage in the arena (CB = G, ldcb = ld), or the spine kernel's LDS staging area in block coordinates
-template <int T, int NW, int W, bool LDSIMG, bool EARLY = false>
+template <int T, int NW, int W, bool LDSIMG, bool EARLY = false, bool PACKED = false>
 __device__ __forceinline__ void mf_front_store(const MfAcc<T, NW, W> &A, double *G, int ld, int fs, int nc,
                                                int with_rhs, double *CB, int ldcb, const double *lds, double *dinv, double *vv, int lane)
 {
     const auto &acc = A.v;
-    constexpr int R = 16 * T;
-    constexpr int U = (LDSIMG ? R * R : 0) > 16 * R ? R * R : 16 * R;
+    constexpr int U = mf_front_img_doubles(T, LDSIMG, PACKED);
     constexpr int NROWS = MfTileSet<T, NW, W>::NROWS;
     const double *dl = lds + U + 256 + 40;
     const int l15 = lane & 15, l4 = lane >> 4;
@@ -836,37 +849,41 @@ __device__ __forceinline__ void mf_front_store(const MfAcc<T, NW, W> &A, double 
     if (W == 0) for (int k = lane; k < nc; k += 64) dinv[k] = dl[k];
 }
 
-template <int T, int NW, int W, bool LDSIMG, bool LDSBAR = false, bool EARLY = false>
+template <int T, int NW, int W, bool LDSIMG, bool LDSBAR = false, bool EARLY = false, bool PACKED = false>
 __device__ __forceinline__ void mf_front_wave(const double *F, int LD, double *G, int ld, int fs, int nc, int with_rhs,
                                               double *lds, double *dinv, double *vv, int lane, int trs, double *CB, int ldcb)
 {
     MF_TRW(0)
     MfAcc<T, NW, W> acc;
-    mf_front_load<T, NW, W, LDSIMG>(acc, F, LD, fs, lane);
+    mf_front_load<T, NW, W, LDSIMG, PACKED>(acc, F, LD, fs, lane);
     MF_TRW(1)
     // the image is dead from here on: its LDS carries the rows of L -- and, EARLY with the image in the arena, its storage the
     // columns of L: this barrier waits for the loads of the image too (the level kernels' __syncthreads())
     mf_elim_barrier<LDSBAR>();
     MF_TRW(2)
-    mf_front_elim<T, NW, W, LDSIMG, LDSBAR, EARLY>(acc, nc, lds, lane, trs, G, ld, fs, with_rhs, vv);
+    mf_front_elim<T, NW, W, LDSIMG, LDSBAR, EARLY, PACKED>(acc, nc, lds, lane, trs, G, ld, fs, with_rhs, vv);
     MF_TRW(7)
     mf_elim_barrier<LDSBAR || EARLY>();
     MF_TRW(8)
-    mf_front_store<T, NW, W, LDSIMG, EARLY>(acc, G, ld, fs, nc, with_rhs, CB, ldcb, lds, dinv, vv, lane);
+    mf_front_store<T, NW, W, LDSIMG, EARLY, PACKED>(acc, G, ld, fs, nc, with_rhs, CB, ldcb, lds, dinv, vv, lane);
     MF_TRW(10)
 }
 
-template <int T, int NW, int W, bool LDSIMG>
+template <int T, int NW, int W, bool LDSIMG, bool PACKED>
 __device__ __forceinline__ void mf_front_dispatch(int wave, const double *F, int LD, double *G, int ld, int fs, int nc,
                                                   int with_rhs, double *lds, double *dinv, double *vv, int lane, int trs)
 {
-    if (wave == W) mf_front_wave<T, NW, W, LDSIMG, false, (SQPHIP_MF_EARLY_STORE != 0 && T >= 5)>(F, LD, G, ld, fs, nc, with_rhs, lds, dinv, vv, lane, trs, G, ld);
-    else if constexpr (W + 1 < NW) mf_front_dispatch<T, NW, W + 1, LDSIMG>(wave, F, LD, G, ld, fs, nc, with_rhs, lds, dinv, vv, lane, trs);
+    if (wave == W) mf_front_wave<T, NW, W, LDSIMG, false, (SQPHIP_MF_EARLY_STORE != 0 && T >= 5), PACKED>(F, LD, G, ld, fs, nc, with_rhs, lds, dinv, vv, lane, trs, G, ld);
+    else if constexpr (W + 1 < NW) mf_front_dispatch<T, NW, W + 1, LDSIMG, PACKED>(wave, F, LD, G, ld, fs, nc, with_rhs, lds, dinv, vv, lane, trs);
 }
 
-template <int T, int NW, bool LDSIMG>
+// image index of entry (row, col) of the front: square (leading dimension LD: the LDS image or the front in the arena) or packed
+template <bool PACKED> __device__ __forceinline__ int mf_front_at(int row, int col, int LD) { return PACKED ? mf_pk(row, col) : col * LD + row; }
+
+template <int T, int NW, bool LDSIMG, bool PACKED = false>
 __global__ __launch_bounds__(64 * NW) void k_mf_front(DV d, int sbegin, int want, int with_rhs)
 {
+    static_assert(LDSIMG || !PACKED, "the packed layout is that of the LDS image");
     constexpr int NT = 64 * NW, R = 16 * T;
     int inst, cand;
     if (!mf_candidate(d, want, inst, cand)) return;
@@ -905,22 +922,24 @@ __global__ __launch_bounds__(64 * NW) void k_mf_front(DV d, int sbegin, int want
     }
     double brhs = 0.0;
     if (with_rhs && tid < nc) brhs = d.xv[(long)inst * d.Fpad + f0 + tid];
-    if (LDSIMG) for (int e = tid; e < R * R; e += NT) F[e] = 0.0;
+    // (PACKED: every tile of the kernel's T, also for a front shorter than its launch -- the load reads them all)
+    if (PACKED) for (int e = tid; e < 128 * T * (T + 1); e += NT) F[e] = 0.0;
+    else if (LDSIMG) for (int e = tid; e < R * R; e += NT) F[e] = 0.0;
     else for (int e = tid; e < ld * fs; e += NT) F[e] = 0.0;
     __syncthreads();
     MF_TR(1)
     {
         const double *vals = mf_vals(d, inst, cand);
 #pragma unroll
-        for (int k = 0; k < PV; ++k) if (vrc[k] >= 0) F[(vrc[k] >> 16) * LD + (vrc[k] & 0xffff)] = vval[k];
+        for (int k = 0; k < PV; ++k) if (vrc[k] >= 0) F[mf_front_at<PACKED>(vrc[k] & 0xffff, vrc[k] >> 16, LD)] = vval[k];
         for (int e = Fd.asm_begin + tid + PV * NT; e < Fd.asm_end; e += NT) {
             const int rc = M.dest_rc[e];
-            F[(rc >> 16) * LD + (rc & 0xffff)] = vals[e];
+            F[mf_front_at<PACKED>(rc & 0xffff, rc >> 16, LD)] = vals[e];
         }
         if (with_rhs) {
-            if (tid < nc) F[tid * LD + fs] = brhs;
+            if (tid < nc) F[mf_front_at<PACKED>(fs, tid, LD)] = brhs;
             const double *b = d.xv + (long)inst * d.Fpad + f0;
-            for (int j = tid + NT; j < nc; j += NT) F[j * LD + fs] = b[j];
+            for (int j = tid + NT; j < nc; j += NT) F[mf_front_at<PACKED>(fs, j, LD)] = b[j];
         }
     }
     __syncthreads();
@@ -930,19 +949,19 @@ __global__ __launch_bounds__(64 * NW) void k_mf_front(DV d, int sbegin, int want
         if (ew[k] >= 0) {
             double a = ea[k];
             for (int q = eb[k] + 1; q < ee[k]; ++q) a += arena[M.ea_src[q]];        // (most entries have one source)
-            F[(ew[k] >> 16) * LD + (ew[k] & 0xffff)] += a;
+            F[mf_front_at<PACKED>(ew[k] & 0xffff, ew[k] >> 16, LD)] += a;
         }
     for (int t = Fd.ea_begin + tid + PE * NT; t < Fd.ea_end; t += NT) {
         const MfGather g = M.ea_ent[t];
         double a = arena[g.src0];
         for (int q = g.src_begin + 1; q < g.src_end; ++q) a += arena[M.ea_src[q]];
         const int rc = g.where;
-        F[(rc >> 16) * LD + (rc & 0xffff)] += a;
+        F[mf_front_at<PACKED>(rc & 0xffff, rc >> 16, LD)] += a;
     }
     __syncthreads();
     MF_TR(3)
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    mf_front_dispatch<T, NW, 0, LDSIMG>(wave, F, LD, G, ld, fs, nc, with_rhs, mf_lds, mf_dinv(d, inst, cand) + f0,
+    mf_front_dispatch<T, NW, 0, LDSIMG, PACKED>(wave, F, LD, G, ld, fs, nc, with_rhs, mf_lds, mf_dinv(d, inst, cand) + f0,
                                         mf_vv(d, inst, cand) + f0, tid & 63, inst == 0 ? s : -1);
     MF_TR(4)
     MF_TR(5)
@@ -2112,6 +2131,10 @@ void mf_device_setup(Ctx &C)
     big(reinterpret_cast<const void *>(k_mf_front<6, 4, true>)); big(reinterpret_cast<const void *>(k_mf_front<7, 4, true>));
     big(reinterpret_cast<const void *>(k_mf_front<8, 4, true>)); big(reinterpret_cast<const void *>(k_mf_front<6, 8, true>));
     big(reinterpret_cast<const void *>(k_mf_front<7, 8, true>)); big(reinterpret_cast<const void *>(k_mf_front<8, 8, true>));
+    // (their packed instantiations: 50 / 65 / 81 KB at eight waves -- only eight tile rows still pass 64 KB; asked for all alike)
+    big(reinterpret_cast<const void *>(k_mf_front<6, 4, true, true>)); big(reinterpret_cast<const void *>(k_mf_front<7, 4, true, true>));
+    big(reinterpret_cast<const void *>(k_mf_front<8, 4, true, true>)); big(reinterpret_cast<const void *>(k_mf_front<6, 8, true, true>));
+    big(reinterpret_cast<const void *>(k_mf_front<7, 8, true, true>)); big(reinterpret_cast<const void *>(k_mf_front<8, 8, true, true>));
     big(reinterpret_cast<const void *>(k_mf_fwd2<true>)); big(reinterpret_cast<const void *>(k_mf_bwd2<true>));
     big(reinterpret_cast<const void *>(k_mf_fwd2<false>)); big(reinterpret_cast<const void *>(k_mf_bwd2<false>));
     big(reinterpret_cast<const void *>(k_mf_solve_top2));
@@ -2160,6 +2183,7 @@ void mf_factor(Ctx &C, int want, bool with_rhs, bool values_done)
     // static front kernels (k_mf_front<T, NW, LDSIMG>) unless SQPHIP_MF_STATIC=0 asks for the generic ones (cross-check)
     const bool stat = !(getenv("SQPHIP_MF_STATIC") && atoi(getenv("SQPHIP_MF_STATIC")) == 0);     // (read per call: tests flip it)
     const bool packed = !(getenv("SQPHIP_MF_F2_PACKED") && atoi(getenv("SQPHIP_MF_F2_PACKED")) == 0);   // (likewise) LDS image of the generic kernels as packed tiles
+    const bool fpacked = !(getenv("SQPHIP_MF_FRONT_PACKED") && atoi(getenv("SQPHIP_MF_FRONT_PACKED")) == 0);   // (likewise) ... and of the static front kernels
     // the levels below the spine as level launches, the spine (mfplan.hip: spine_level) by one workgroup per instance
     const bool spine = !v1 && d.mf.sp_n > 0 && C.mf_big_lds;
     int li = 0, cls_open = -1;        // (detail timers: one event pair around the launches below the narrow top, one around those of the top)
@@ -2175,7 +2199,10 @@ void mf_factor(Ctx &C, int want, bool with_rhs, bool values_done)
 #define MF_GENERIC(NW, MAXT, IMG) do { constexpr int kid_ = mf_factor2_kid(NW, MAXT, IMG); static_assert(kid_ >= 0, "census: no counter"); C.mf_census[kid_]++; \
         if (IMG && packed) hipLaunchKernelGGL((k_mf_factor2<NW, MAXT, IMG, IMG>), grid, dim3(64 * NW), 8 * mf_factor2_lds_doubles(T, IMG, true), s, d, L.begin, want, wr, T); \
         else hipLaunchKernelGGL((k_mf_factor2<NW, MAXT, IMG, false>), grid, dim3(64 * NW), 8 * mf_factor2_lds_doubles(T, IMG, false), s, d, L.begin, want, wr, T); } while (0)
-#define MF_STATIC(TT, NW, IMG) do { constexpr int kid_ = mf_front_kid(TT, NW, IMG); static_assert(kid_ >= 0, "census: no counter"); C.mf_census[kid_]++; hipLaunchKernelGGL((k_mf_front<TT, NW, IMG>), grid, dim3(64 * NW), 8 * (size_t)mf_front_lds_doubles(TT, NW, IMG), s, d, L.begin, want, wr); } while (0)
+        // static kernels with the image in LDS: packed tiles, or -- SQPHIP_MF_FRONT_PACKED=0 -- the square instantiation (same census entry)
+#define MF_STATIC(TT, NW, IMG) do { constexpr int kid_ = mf_front_kid(TT, NW, IMG); static_assert(kid_ >= 0, "census: no counter"); C.mf_census[kid_]++; \
+        if (IMG && fpacked) hipLaunchKernelGGL((k_mf_front<TT, NW, IMG, IMG>), grid, dim3(64 * NW), 8 * (size_t)mf_front_lds_doubles(TT, NW, IMG, IMG), s, d, L.begin, want, wr); \
+        else hipLaunchKernelGGL((k_mf_front<TT, NW, IMG, false>), grid, dim3(64 * NW), 8 * (size_t)mf_front_lds_doubles(TT, NW, IMG, false), s, d, L.begin, want, wr); } while (0)
         // ... from four tile rows on: below that the generic kernels are as fast per front and lighter (registers, code
         // size) where thousands of small fronts are in flight.  Measured (QP/s, static from T = 1 / from T = 4 / never):
         // 512 x IEEE-118 5565 / 5507 / 5259, 64 x IEEE-118 1372 / - / 1315, 9241 shape 20.6 / 24.3 / 23.4, IEEE-14 50.9 k /
@@ -2208,9 +2235,11 @@ void mf_factor(Ctx &C, int want, bool with_rhs, bool values_done)
         case 3: MF_STATIC(3, 1, true); break;
         case 4: if (nw4 & 1) MF_STATIC(4, 4, true); else MF_STATIC(4, 2, true); break;
         case 5: if (nw4 & 2) MF_STATIC(5, 4, true); else MF_STATIC(5, 2, true); break;
-        // (six to eight tile rows: the image fits the 160 KB of LDS of gfx950 too -- 74 / 100 / 131 KB -- once more than
+        // (six to eight tile rows: the image fits the 160 KB of LDS of gfx950 too -- 74 / 100 / 131 KB square, 43 / 57 / 74 KB packed -- once more than
         //  64 KB of dynamic LDS has been asked for; only for the handful of fronts of a level near the top of the tree, where
-        //  one workgroup per CU is all there is anyway: +0.3 % on 512 x IEEE-118; SQPHIP_MF_BIG_LDSIMG=0: image in the arena)
+        //  one workgroup of the square image per CU was all there was anyway: +0.3 % on 512 x IEEE-118; SQPHIP_MF_BIG_LDSIMG=0: image
+        //  in the arena.  With the packed image two workgroups of six or seven tile rows fit a CU, so the reason no longer binds
+        //  there; the rule stands until the wide launches have been measured with the image in LDS: DESIGN.md section 10)
         case 6: if (big_img && L.small) { if (nw8) MF_STATIC(6, 8, true); else MF_STATIC(6, 4, true); } else MF_STATIC(6, 4, false); break;
         case 7: if (big_img && L.small) { if (nw8) MF_STATIC(7, 8, true); else MF_STATIC(7, 4, true); } else MF_STATIC(7, 4, false); break;
         case 8: if (big_img && L.small) { if (nw8) MF_STATIC(8, 8, true); else MF_STATIC(8, 4, true); } else MF_STATIC(8, 4, false); break;
