@@ -104,19 +104,25 @@ static __device__ __noinline__ void nlp_kappa_wide(int kind, double a, double u,
         const double s = sqrt(u);
         r.k0 = s; r.k1 = 0.5 / s; r.k2 = -0.25 / (u * s);
     } else if (kind == NLP_TANH) {
-        const double t = tanh(u), d = 1.0 - t * t;
+        // sech^2 u = 4 e / (1 + e)^2 with e = exp(-2 |u|) <= 1: no 1 - t t, which cancels from |u| = 2 on and is 0 from 19.07 on
+        const double t = tanh(u), e = exp(-2.0 * fabs(u)), p = 1.0 + e, d = 4.0 * e / (p * p);
         r.k0 = t; r.k1 = d; r.k2 = -2.0 * t * d;
     } else if (kind == NLP_ATAN) {
+        // -2 (u q) q: q q underflows from |u| = 1e77 on, where -2 u q q is still a normal number
         const double q = 1.0 / (1.0 + u * u);
-        r.k0 = atan(u); r.k1 = q; r.k2 = -2.0 * u * (q * q);
+        r.k0 = atan(u); r.k1 = q; r.k2 = -2.0 * (u * q) * q;
     } else if (kind == NLP_POWR) {
         const double v = pow(u, pw);
         r.k0 = v; r.k1 = pw * v / u; r.k2 = pw * (pw - 1.0) * v / (u * u);
     } else {
-        // e = exp(-|u|) <= 1 never overflows; s and 1 - s both from e, none by cancellation
+        // e = exp(-|u|) <= 1 never overflows; s and 1 - s both from e, none by cancellation; (1 - s) - s = -+(1 - e) den
+        // through expm1, which does not cancel around u = 0 either
         const double e = exp(-fabs(u)), den = 1.0 / (1.0 + e);
         const double s = u < 0.0 ? e * den : den, sc = u < 0.0 ? den : e * den;
-        if (kind == NLP_SIGMOID) { r.k0 = s; r.k1 = s * sc; r.k2 = s * sc * (sc - s); }
+        if (kind == NLP_SIGMOID) {
+            const double dm = expm1(-fabs(u)) * den;
+            r.k0 = s; r.k1 = s * sc; r.k2 = s * sc * (u < 0.0 ? -dm : dm);
+        }
         else { r.k0 = fmax(u, 0.0) + log1p(e); r.k1 = s; r.k2 = s * sc; }
     }
     w[0] = r.k0;

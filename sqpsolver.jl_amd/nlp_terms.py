@@ -543,15 +543,18 @@ def _kappa3(kind, e, par, u):
             r = np.sqrt(u)
             return r, 0.5 / r, -0.25 / (u * r)
         if kind == TANH:
-            t = np.tanh(u)
-            return t, 1.0 - t * t, -2.0 * t * (1.0 - t * t)
+            # sech^2 u = 4 e / (1 + e)^2, e = exp(-2 |u|): the device's form (1 - t t cancels, and is 0 from |u| = 19.07 on)
+            t, e2 = np.tanh(u), np.exp(-2.0 * np.abs(u))
+            d = 4.0 * e2 / ((1.0 + e2) * (1.0 + e2))
+            return t, d, -2.0 * t * d
         if kind == ATAN:
             q = 1.0 / (1.0 + u * u)
-            return np.arctan(u), q, -2.0 * u * q * q
+            return np.arctan(u), q, -2.0 * (u * q) * q                 # (q q underflows from |u| = 1e77 on)
         e_ = np.exp(-np.abs(u))
         sg, sc = np.where(u < 0, e_ / (1.0 + e_), 1.0 / (1.0 + e_)), np.where(u < 0, 1.0 / (1.0 + e_), e_ / (1.0 + e_))
         if kind == SIGMOID:
-            return sg, sg * sc, sg * sc * (sc - sg)
+            dm = np.expm1(-np.abs(u)) / (1.0 + e_)                          # (1 - s) - s = -+(1 - e) den without cancellation at 0
+            return sg, sg * sc, sg * sc * np.where(u < 0, -dm, dm)
         if kind == SOFTPLUS:
             return np.maximum(u, 0.0) + np.log1p(e_), sg, sg * sc
     raise ValueError(f"unknown kind {kind}")

@@ -61,16 +61,17 @@ def kappa_mp(kind, e, par, u):
         r = mp.sqrt(u)
         return r, 1 / (2 * r), -1 / (4 * u * r)
     if kind == TANH:
-        t = mp.tanh(u)
-        return t, 1 - t * t, -2 * t * (1 - t * t)
+        t, e2 = mp.tanh(u), mp.exp(-2 * abs(u))
+        d = 4 * e2 / (1 + e2) ** 2                            # sech^2 u without 1 - t t
+        return t, d, -2 * t * d
     if kind == ATAN:
         q = 1 / (1 + u * u)
         return mp.atan(u), q, -2 * u * q * q
-    s = 1 / (1 + mp.exp(-u))
+    s, sc = 1 / (1 + mp.exp(-u)), 1 / (1 + mp.exp(u))     # the complement from e^u: 1 - s is wrong beyond u = 115 at 50 digits
     if kind == SIGMOID:
-        return s, s * (1 - s), s * (1 - s) * (1 - 2 * s)
+        return s, s * sc, -s * sc * mp.tanh(u / 2)        # (1 - s) - s = -tanh(u / 2)
     assert kind == SOFTPLUS
-    return mp.log(1 + mp.exp(u)), s, s * (1 - s)
+    return (u if u > 0 else 0) + mp.log1p(mp.exp(-abs(u))), s, s * sc
 
 
 def block_reference(b: NlpBlock, x, sigma):

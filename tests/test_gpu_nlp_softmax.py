@@ -307,11 +307,37 @@ def test_refusals():
 # ---- a context without a softmax block files the bytes it filed before the call existed: one generic case, recorded from the
 # parent library (tests/golden/nlp_softmax_parent_general_edge.npz)
 def test_a_context_without_a_softmax_block_files_the_parents_bytes():
-    gold = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "nlp_softmax_parent_general_edge.npz"))
+    """Two records of general_edge_model at one point: nlp_softmax_parent_general_edge.npz from the library before the softmax
+    blocks, nlp_exact_general_edge.npz from the library whose nlp_kappa_wide forms tanh', tanh'', sigmoid'' and atan'' without
+    cancellation.  Against the older record: bit equality on every entry that reads none of those four stored values (the
+    set comes from the model's plans); every entry under the exact bound of tests/nlp_exact.py; against the newer record: bit
+    equality on every entry."""
+    import nlp_exact as X
+    from sqpsolver_jl_amd.nlp_terms import ATAN, SIGMOID, TANH
+    here = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+    gold = np.load(os.path.join(here, "nlp_softmax_parent_general_edge.npz"))
+    rec = np.load(os.path.join(here, "nlp_exact_general_edge.npz"))
     p, lay = general_edge_model()
+    assert np.array_equal(gold["x"], rec["x"]) and np.array_equal(gold["lam"], rec["lam"])
     ctx = _ctx(lay, 1)
     ctx.nlp_attach(p, general=True); ctx.nlp_set_instance(0, p)
     ev = ctx.acopf_eval(0, gold["x"], 0.7, gold["lam"])
     ctx.close()
+    changed = lambda k, q: (p.fkind[k] == TANH and q >= 1) or (p.fkind[k] in (SIGMOID, ATAN) and q == 2)
+    same, moved = 0, 0
+    for key, entries in X.plans(p, lay).items():
+        got, old = np.atleast_1d(np.asarray(ev[key])), np.atleast_1d(gold[key])
+        for i, entry in enumerate(entries):
+            if not any(changed(k, q) for t, a, b, _, _, _ in entry for k, q in X._orders(p, t, a, b)):
+                assert got[i] == old[i], (key, i)
+                same += 1
+            else:
+                moved += 1
+    print("entries held to the older record's bits:", same, "others:", moved)
+    assert same > 100 and 0 < moved < 60
+    R = X.NlpExact(p)
+    val, bnd = R.want(gold["x"], 0.7, gold["lam"], lay)
+    X.check_entries(ev, val, bnd, R.exact, label="general_edge_model")
+    X.check_entries({k: gold[k] for k in X.KEYS}, val, bnd, R.exact, label="general_edge_model, the older record")
     for k in ("f", "grad", "g", "jval", "hval"):
-        assert np.array_equal(np.asarray(ev[k]), gold[k]), k
+        assert np.array_equal(np.asarray(ev[k]), rec[k]), k
