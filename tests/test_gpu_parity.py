@@ -1855,7 +1855,8 @@ def test_penalty_escalation_on_the_device():
         ro = q.solve(O.MODE_QP, np.zeros(1), delta, 1.0, np.array([c]), np.zeros(1), np.array([jv]), hv)
         assert rg["status"] == ro["status"] == want
         if want == O.MOI_LOCALLY_SOLVED:
-            assert abs(rg["p"][0] - 1000.0) < 0.1 and rel(rg["p"], ro["p"]) < 1e-6 and rel(rg["lam"], ro["lam"]) < 1e-6
+            # p* = 1000 (the row at its bound); the oracle ends 2.0e-8 away from it: 10 x that, rounded up to one digit
+            assert abs(rg["p"][0] - 1000.0) < 3e-7 and rel(rg["p"], ro["p"]) < 1e-6 and rel(rg["lam"], ro["lam"]) < 1e-6
         ctx.close()
 
 
