@@ -85,6 +85,14 @@ int sqphip_mf_plan_info(int64_t n, int64_t m, int64_t nnzJ, const int64_t *jrow,
                         const int64_t *hrow, const int64_t *hcol, const double *gL, const double *gU, int32_t condense,
                         int32_t batch, int32_t *fronts, int32_t cap_fronts, int32_t *n_fronts, int32_t *launches,
                         int32_t cap_launches, int32_t *n_launches, int64_t *top2_lds_bytes, int32_t *spine_fronts);
+/* Host-only (no GPU): what the factorisation launches for the same plan under the current environment --
+ * kernels[cap_launches][4], one row per row of `launches` above = (index in the census of sqphip_mf_census of the front kernel
+ * chosen for the launch, 1 when its instantiation with the packed LDS image runs, 1 when the spine kernel takes the launch
+ * instead, 1 when the launch held at most eight fronts before the deferral pass); big_lds: whether the device grants 160 KB of
+ * dynamic LDS (every MI355X does). */
+int sqphip_mf_factor_kernels(int64_t n, int64_t m, int64_t nnzJ, const int64_t *jrow, const int64_t *jcol, int64_t nnzH,
+                             const int64_t *hrow, const int64_t *hcol, const double *gL, const double *gU, int32_t condense,
+                             int32_t batch, int32_t big_lds, int32_t *kernels, int32_t cap_launches, int32_t *n_launches);
 /* Host-only (no GPU): where the deferral pass of the plan (SQPHIP_MF_DEFER) put the fronts of the same plan --
  * fronts[cap_fronts][3] = (factor launch the front runs in: a row of `launches` above, its launch in the schedule before the
  * pass, numbered in that schedule -- the rows of `launches` under SQPHIP_MF_DEFER=0 --, parent front or -1 for a root). */

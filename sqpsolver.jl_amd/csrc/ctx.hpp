@@ -9,6 +9,7 @@
 #include "sqphip_internal.hpp"
 #include "sparse.hpp"
 #include "model_plans.hpp"
+#include "mf_select.hpp"
 
 namespace sqphip {
 
@@ -26,15 +27,8 @@ enum { PH_IDLE = 0, PH_PREP = 1, PH_FACTOR = 2, PH_SOLVE = 3, PH_STEP = 4, PH_MP
 enum { ROW_FREE = 0, ROW_EQ = 1, ROW_INEQ = 2 };
 
 // Launch census of the multifrontal path: one host counter per kernel instantiation that mf_factor, mf_solve and the
-// inertia test can enqueue (Ctx::mf_census, incremented at enqueue; read by the test hook sqphip_mf_census, which names them
-// through mf_kernel_names, mfront.hip).  k_mf_front<T, NW, LDSIMG>: FRONT_<T>[_<NW>][_IMG] (T <= 3: one wave, image in LDS).
-enum MfKernel { MFK_VALUES, MFK_FACTOR_R1, MFK_F2_1_3, MFK_F2_2_5, MFK_F2_4_4, MFK_F2_4_9, MFK_F2_8_12,
-                MFK_FRONT_1, MFK_FRONT_2, MFK_FRONT_3, MFK_FRONT_4_2, MFK_FRONT_4_4, MFK_FRONT_5_2, MFK_FRONT_5_4,
-                MFK_FRONT_6_4, MFK_FRONT_6_4_IMG, MFK_FRONT_6_8_IMG, MFK_FRONT_7_4, MFK_FRONT_7_4_IMG, MFK_FRONT_7_8_IMG,
-                MFK_FRONT_8_4, MFK_FRONT_8_4_IMG, MFK_FRONT_8_8_IMG, MFK_FRONT_9, MFK_FRONT_10, MFK_FRONT_11, MFK_FRONT_12,
-                MFK_SPINE, MFK_SOLVE_INST, MFK_FWD, MFK_FWD2, MFK_FWD2_BIG, MFK_SOLVE_TOP, MFK_SOLVE_TOP2, MFK_BWD, MFK_BWD2,
-                MFK_BWD2_BIG, MFK_INERTIA, MFK_COUNT };
-extern const char *const mf_kernel_names[];        // [MFK_COUNT] (checked where it is defined)
+// inertia test can enqueue (Ctx::mf_census).  enum MfKernel, MFK_COUNT and mf_kernel_names come from the one list of
+// mf_kernels.hpp (through mf_select.hpp, which also holds the choice of instantiation per launch).
 
 struct IpmState {
     // request

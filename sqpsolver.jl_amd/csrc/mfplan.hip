@@ -6,7 +6,7 @@
 // The matrix is the (condensed) Newton matrix of ipm.hip:
 //     [ W + J_I' (D_I + reg)^-1 J_I    J_K' ]     W = hsc H + hd + sigp + (delta_w + reg) I,  K = rows kept in the matrix
 //     [ J_K                       -(D_K + reg) ]
-#include "sparse.hpp"
+#include "mf_select.hpp"
 #include "../../include/sqphip.h"
 #include "../../include/sqphip_test_hooks.h"
 #include <algorithm>
@@ -22,6 +22,7 @@ MfPlan mf_build_plan(int n, int m, const std::vector<int> &kpos, int mk, const s
                      const std::vector<int> &jrslot, const SymOptions &opt)
 {
     MfPlan P;
+    const MfPlanSwitches sw = mf_read_plan_switches();      // the experiment switches of the plan, read once (mf_select.hpp)
     std::vector<std::vector<int>> adj, before;
     kkt_graph(n, m, kpos, mk, hcolptr, hrowval, jrowptr, jrcol, adj, before);
     P.S = sparse_symbolic(n + mk, adj, before, opt);
@@ -112,15 +113,15 @@ MfPlan mf_build_plan(int n, int m, const std::vector<int> &kpos, int mk, const s
     // the top, ascending]: the last child inside the top is then the last term of every sum it contributes to, which lets
     // the spine kernel add it straight from its accumulator registers behind the terms that come from the arena, in the
     // order every other kernel (level launches, host reference) uses too.
-    const bool big_solve = !(getenv("SQPHIP_MF_BIG_SOLVE") && atoi(getenv("SQPHIP_MF_BIG_SOLVE")) == 0);   // experiment switch
+    const bool big_solve = sw.big_solve;
     P.top_level = S.nlevels;
-    if (big_solve && !(getenv("SQPHIP_MF_TOP") && atoi(getenv("SQPHIP_MF_TOP")) == 0)) {
+    if (big_solve && sw.top != 0) {
         // ... a level of up to four fronts joins the top as well when all of them are wave-sized (<= 64 rows): the four
         // waves of the instance's workgroup take one each, exactly what a level launch would do, one launch less per pass
         auto joins = [&](int lev) {
             const int cnt = S.level_ptr[lev + 1] - S.level_ptr[lev];
             if (cnt <= 2) return true;
-            if (cnt > 4 || getenv("SQPHIP_MF_TOP_NARROW")) return false;
+            if (cnt > 4 || sw.top_narrow) return false;
             for (int q = S.level_ptr[lev]; q < S.level_ptr[lev + 1]; ++q)
                 if (S.sn_nc[S.level_sn[q]] + S.sn_nr[S.level_sn[q]] > 64) return false;
             return true;
@@ -211,8 +212,8 @@ MfPlan mf_build_plan(int n, int m, const std::vector<int> &kpos, int mk, const s
         //  fronts it holds -- the small fronts then run in the kernel of the tallest)
         //  (measured, monotone sweep, QP/s without / with t = 4: 512 resident scenarios 8 995 / 8 517, 256: 6 570 / 6 285, 128: 4 309 / 4 321,
         //  64: 2 549 / 2 611, 32: 1 373 / 1 427 -- the caller asks for it up to 64 instances, SymOptions::merge_tiles)
-        const int merge_t = getenv("SQPHIP_MF_MERGE_T") ? atoi(getenv("SQPHIP_MF_MERGE_T")) : opt.merge_tiles;
-        const bool merge = ((cnt <= 8 && tmax <= 8) || tmax <= merge_t) && !getenv("SQPHIP_MF_NO_LEVEL_MERGE");
+        const int merge_t = sw.merge_t >= 0 ? sw.merge_t : opt.merge_tiles;
+        const bool merge = ((cnt <= 8 && tmax <= 8) || tmax <= merge_t) && !sw.no_level_merge;
         for (int c = 0; c < 10; ++c) {
             MfLaunch L{(int)P.sched.size(), 0, 0, 0, c, 0};
             L.level = l;
@@ -284,7 +285,7 @@ MfPlan mf_build_plan(int n, int m, const std::vector<int> &kpos, int mk, const s
     // of a top front is a top front).  One wave walks the fronts with everything it touches in LDS -- the factor image of
     // the front (prefetched by the other waves while the previous front is solved), the updates of the children, the
     // solution of the ancestors -- so a front costs its dependent arithmetic, not a chain of memory round trips.
-    if (P.top.count > 0 && !(getenv("SQPHIP_MF_TOP2") && atoi(getenv("SQPHIP_MF_TOP2")) == 0)) {
+    if (P.top.count > 0 && sw.top2) {
         std::vector<int> kof(S.ns, -1);
         bool ok = true;
         for (int s = 0; s < S.ns; ++s) {
@@ -338,7 +339,7 @@ MfPlan mf_build_plan(int n, int m, const std::vector<int> &kpos, int mk, const s
         // [buf0][buf1][128 doubles of slack][updates: n_ext + utotal][x: xtotal][D^-1 L^-1 b: xtotal][front records: 16 ints each]
         // [inertia test of k_mf_solve_top2: 16 doubles of exchange, the published decision; 24 doubles]
         const long lds = 8L * ((long)P.top_buf0 + P.top_buf1 + n_ext + P.top_utotal + 2L * P.top_xtotal + 128 + 8L * (long)P.top_fr.size() + 24);
-        if (getenv("SQPHIP_SYM_DUMP"))
+        if (sw.sym_dump)
             fprintf(stderr, "top (streamed): %d fronts from level %d, %d external + %d internal update entries, %d columns, LDS %ld bytes (buffers %d + %d doubles)%s\n",
                     (int)P.top_fr.size(), P.top_level, n_ext, P.top_utotal, P.top_xtotal, lds, P.top_buf0, P.top_buf1, ok ? "" : " -- a front of more than 128 rows: not used");
         if (ok && !P.top_fr.empty() && lds <= 160 * 1024 - 2048) P.top2_lds_bytes = lds;
@@ -348,7 +349,7 @@ MfPlan mf_build_plan(int n, int m, const std::vector<int> &kpos, int mk, const s
             // to level launches, which have the LDS-staged kernels for every level they fit -- k_mf_solve_top, one
             // workgroup per instance walking the fronts with the round-2 routines, is the slower of the two by now
             // (1354-bus shape: 495 -> 524 QP/s); SQPHIP_MF_TOP=1 keeps it
-            if (!(getenv("SQPHIP_MF_TOP") && atoi(getenv("SQPHIP_MF_TOP")) == 1)) { P.top_level = S.nlevels; build_solve_launches(); }
+            if (sw.top != 1) { P.top_level = S.nlevels; build_solve_launches(); }
         }
     }
     // packed records for the kernels
@@ -367,7 +368,7 @@ MfPlan mf_build_plan(int n, int m, const std::vector<int> &kpos, int mk, const s
         //  memory bus, but a front costs it what it costs a level launch -- 230 us for the 17 fronts of IEEE-118 against ~170 us
         //  of level launches, which run the two branches of the tree side by side -- and its 120 KB of LDS keeps every other
         //  kernel off its CU: 7 251 against 7 704 QP/s at 512 resident scenarios, 1 946 against 2 014 at 64.  Off unless asked for.)
-        bool ok = P.spine_level < S.nlevels && getenv("SQPHIP_MF_SPINE") && atoi(getenv("SQPHIP_MF_SPINE")) == 1;
+        bool ok = P.spine_level < S.nlevels && sw.spine;
         std::vector<int> sp;                             // spine fronts, ascending
         for (int s = 0; ok && s < S.ns; ++s)
             if (S.sn_level[s] >= P.spine_level) {
@@ -424,14 +425,14 @@ MfPlan mf_build_plan(int n, int m, const std::vector<int> &kpos, int mk, const s
             if (P.spine_lds_bytes > 160 * 1024 - 1024) ok = false;
         }
         if (!ok || P.sp_fr.empty()) { P.sp_fr.clear(); P.sp_ent.clear(); P.sp_src.clear(); P.sp_rel.clear(); P.spine_lds_bytes = 0; P.spine_level = S.nlevels; P.fac_below = (int)P.fac.size(); }
-        if (getenv("SQPHIP_SYM_DUMP"))
+        if (sw.sym_dump)
             for (const MfSpineFront &F : P.sp_fr) {
                 int hist[5] = {0, 0, 0, 0, 0};
                 for (int t = F.ea_begin; t < F.ea_end; ++t) hist[std::min(4, P.sp_ent[t].src_end - P.sp_ent[t].src_begin)]++;
                 fprintf(stderr, "  spine front %d: %d x %d, T %d, %d structural entries, %d receiving entries from the arena (1 / 2 / 3 / 4+ sources: %d / %d / %d / %d), handoff %d\n",
                         F.s, F.nc, F.nr, F.T, F.asm_end - F.asm_begin, F.ea_end - F.ea_begin, hist[1], hist[2], hist[3], hist[4], F.handoff);
             }
-        if (getenv("SQPHIP_SYM_DUMP"))
+        if (sw.sym_dump)
             fprintf(stderr, "spine (factorisation): %d fronts from level %d, tallest %d tiles, %zu arena gather entries, LDS %ld bytes\n",
                     (int)P.sp_fr.size(), P.spine_level, P.spine_T, P.sp_ent.size(), P.spine_lds_bytes);
     }
@@ -441,14 +442,14 @@ MfPlan mf_build_plan(int n, int m, const std::vector<int> &kpos, int mk, const s
     // launch consists of such fronts (a single leaf one row over a class boundary, two side branches of the upper tree) the
     // launch costs the chain its full latency for work that a later, equally shaped launch takes along almost free.
     // Nothing a front computes depends on the launch it is in: its kernel is the same (mf_same_selection: the rules live
-    // next to mf_factor), its children's blocks are complete, its arena slot is its own.  Launches keep level, tiles and class;
+    // next to the choice, mf_select.cpp), its children's blocks are complete, its arena slot is its own.  Launches keep level, tiles and class;
     // sn_level, the solve launches and the gather lists are untouched.  SQPHIP_MF_DEFER=0: the schedule as built above;
     // 1 (default): the latest launch allowed; 2: the destination whose own tallest front has the most columns -- a proxy for
     // the longest launch, behind which the guest hides --, ties to the latest (measured, 512 x IEEE-118, QP/s medians of five:
     // 10 279 without / 10 490 latest / 10 416 widest: DESIGN.md section 0d).  Not with a spine: fac_below cuts the launch
     // list by level.
     {
-        const int defer = getenv("SQPHIP_MF_DEFER") ? atoi(getenv("SQPHIP_MF_DEFER")) : 1;
+        const int defer = sw.defer;
         const int nl = (int)P.fac.size();
         std::vector<std::vector<int>> mem(nl);           // fronts per launch, guests behind the launch's own
         P.launch_of0.assign(S.ns, -1);
@@ -498,7 +499,7 @@ MfPlan mf_build_plan(int n, int m, const std::vector<int> &kpos, int mk, const s
         P.launch_of.assign(S.ns, -1);
         for (int k = 0; k < (int)P.fac.size(); ++k)
             for (int q = P.fac[k].begin; q < P.fac[k].begin + P.fac[k].count; ++q) P.launch_of[P.sched[q]] = k;
-        if (getenv("SQPHIP_SYM_DUMP")) {
+        if (sw.sym_dump) {
             for (int s = 0; s < S.ns; ++s)
                 if (alive[P.launch_of0[s]] == 0)
                     fprintf(stderr, "  deferred: front %d (%d x %d, level %d, parent's level %d) from launch %d to launch %d (level %d)\n", s, S.sn_nc[s],
@@ -833,6 +834,29 @@ extern "C" int sqphip_mf_plan_info(int64_t n, int64_t m, int64_t nnzJ, const int
     if (n_launches) *n_launches = (int32_t)P.fac.size();
     if (top2_lds_bytes) *top2_lds_bytes = P.top2_lds_bytes;
     if (spine_fronts) *spine_fronts = (int32_t)P.sp_fr.size();
+    return SQPHIP_OK;
+}
+
+// C-ABI test hook (host only, no GPU): what mf_factor launches for the same plan under the current environment, per factor
+// launch (census index of the kernel mf_select_front picks, packed LDS image, 1 when the spine kernel takes the launch
+// instead, MfLaunch::small); big_lds stands for Ctx::mf_big_lds.  cap_launches 0 asks for the count only.
+extern "C" int sqphip_mf_factor_kernels(int64_t n, int64_t m, int64_t nnzJ, const int64_t *jrow, const int64_t *jcol, int64_t nnzH,
+                                        const int64_t *hrow, const int64_t *hcol, const double *gL, const double *gU,
+                                        int32_t condense, int32_t batch, int32_t big_lds, int32_t *kernels, int32_t cap_launches,
+                                        int32_t *n_launches)
+{
+    if (n <= 0 || m < 0 || batch <= 0 || cap_launches < 0 || (cap_launches > 0 && !kernels)) return SQPHIP_EINVAL;
+    using namespace sqphip;
+    const SymOptions so = mf_sym_options(batch);
+    std::vector<double> jv, hv;
+    const MfPlan P = host_plan(n, m, nnzJ, jrow, jcol, nnzH, hrow, hcol, gL, gU, condense, so, nullptr, nullptr, jv, hv);
+    const MfSwitches sw = mf_read_switches();
+    const bool spine = mf_spine_runs(!P.sp_fr.empty(), big_lds != 0, sw);
+    for (int k = 0; k < (int)P.fac.size() && k < cap_launches; ++k) {
+        const MfFrontChoice ch = mf_select_launch(P.fac[k], P.narrow_level, big_lds != 0, sw);
+        kernels[4 * k] = ch.kid; kernels[4 * k + 1] = ch.packed; kernels[4 * k + 2] = spine && k >= P.fac_below; kernels[4 * k + 3] = P.fac[k].small;
+    }
+    if (n_launches) *n_launches = (int32_t)P.fac.size();
     return SQPHIP_OK;
 }
 

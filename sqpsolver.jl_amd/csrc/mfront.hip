@@ -1475,29 +1475,6 @@ __global__ __launch_bounds__(256) void k_mf_solve_top(DV d, int ibegin, int coun
     }
 }
 
-// whole solve of one instance by ONE workgroup of NWV waves: the waves deal out the fronts of a level, a workgroup
-// barrier closes the level (the vectors live in global memory, visible CU-wide after the barrier).  With hundreds of
-// instances in flight this fills the chip without a launch per level: 2 x levels launches become one.
-template <int NWV>
-__global__ __launch_bounds__(64 * NWV) void k_mf_solve_inst(DV d, int want, int do_fwd, int generic)
-{
-    const int inst = blockIdx.x;
-    if (d.phase[inst] != want) return;
-    const MfDev &M = d.mf;
-    extern __shared__ double mf_lds[];
-    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    double *y = mf_lds + (long)wave * M.max_front;
-    if (do_fwd)
-        for (int l = 0; l < M.nlevels; ++l) {
-            for (int q = M.level_ptr[l] + wave; q < M.level_ptr[l + 1]; q += NWV) mf_front_fwd(d, inst, M.level_sn[q], y, lane, generic);
-            __syncthreads();
-        }
-    for (int l = M.nlevels - 1; l >= 0; --l) {
-        for (int q = M.level_ptr[l] + wave; q < M.level_ptr[l + 1]; q += NWV) mf_front_bwd(d, inst, M.level_sn[q], y, lane, generic);
-        __syncthreads();
-    }
-}
-
 // ---------------------------------------------------------------------------------------------------------------
 // The top of the assembly tree, streamed (k_mf_solve_top2; plan: mfplan.hip, MfTopFront).  k_mf_solve_top spends ~12 us
 // per front and direction on a chain of dependent memory round trips and workgroup barriers (measured with the cycle
@@ -2086,38 +2063,9 @@ __global__ __launch_bounds__(256, HASBIG ? 4 : 5) void k_mf_bwd2(DV d, int ibegi
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-// launch census (ctx.hpp MfKernel): the names, and the counter of a front kernel instantiation
-const char *const mf_kernel_names[] = {
-    "k_mf_values", "k_mf_factor<256, true>", "k_mf_factor2<1, 3, true>", "k_mf_factor2<2, 5, true>", "k_mf_factor2<4, 4, true>",
-    "k_mf_factor2<4, 9, false>", "k_mf_factor2<8, 12, false>",
-    "k_mf_front<1, 1, true>", "k_mf_front<2, 1, true>", "k_mf_front<3, 1, true>", "k_mf_front<4, 2, true>", "k_mf_front<4, 4, true>",
-    "k_mf_front<5, 2, true>", "k_mf_front<5, 4, true>",
-    "k_mf_front<6, 4, false>", "k_mf_front<6, 4, true>", "k_mf_front<6, 8, true>",
-    "k_mf_front<7, 4, false>", "k_mf_front<7, 4, true>", "k_mf_front<7, 8, true>",
-    "k_mf_front<8, 4, false>", "k_mf_front<8, 4, true>", "k_mf_front<8, 8, true>",
-    "k_mf_front<9, 8, false>", "k_mf_front<10, 8, false>", "k_mf_front<11, 8, false>", "k_mf_front<12, 8, false>",
-    "k_mf_spine", "k_mf_solve_inst<16>", "k_mf_fwd", "k_mf_fwd2<false>", "k_mf_fwd2<true>", "k_mf_solve_top", "k_mf_solve_top2",
-    "k_mf_bwd", "k_mf_bwd2<false>", "k_mf_bwd2<true>", "k_inertia" };
-static_assert(sizeof(mf_kernel_names) / sizeof(mf_kernel_names[0]) == MFK_COUNT, "a name per MfKernel entry");
-// -1: an instantiation the census has no counter for (the launch macros of mf_factor refuse to compile it)
-static constexpr int mf_front_kid(int T, int NW, bool IMG)
-{
-    return T >= 1 && T <= 3 ? (NW == 1 && IMG ? MFK_FRONT_1 + T - 1 : -1)
-         : T <= 5 ? ((NW == 2 || NW == 4) && IMG ? MFK_FRONT_4_2 + 2 * (T - 4) + (NW == 4) : -1)
-         : T <= 8 ? (NW == 4 ? MFK_FRONT_6_4 + 3 * (T - 6) + (IMG ? 1 : 0) : NW == 8 && IMG ? MFK_FRONT_6_4 + 3 * (T - 6) + 2 : -1)
-         : T <= 12 ? (NW == 8 && !IMG ? MFK_FRONT_9 + T - 9 : -1) : -1;
-}
-static constexpr int mf_factor2_kid(int NW, int MAXT, bool IMG)
-{
-    return NW == 1 && MAXT == 3 && IMG ? MFK_F2_1_3 : NW == 2 && MAXT == 5 && IMG ? MFK_F2_2_5 : NW == 4 && MAXT == 4 && IMG ? MFK_F2_4_4
-         : NW == 4 && MAXT == 9 && !IMG ? MFK_F2_4_9 : NW == 8 && MAXT == 12 && !IMG ? MFK_F2_8_12 : -1;
-}
-
-static int mf_generic_solves()
-{
-    static const int g = getenv("SQPHIP_MF_GENERIC") ? atoi(getenv("SQPHIP_MF_GENERIC")) : 0;
-    return g;
-}
+// The host side: which kernel a launch runs is decided in mf_select.cpp (pure functions of the launch and the switches, read
+// once per call); here the switches are read, the functions asked, the census counted, the timers opened and closed, and the
+// kernels launched.  The instantiations come from the one list of mf_kernels.hpp.
 
 // Kernels that ask for more than 64 KB of dynamic LDS need the attribute set on the device they run on: done for every
 // context at creation, on the context's device (a process may hold contexts on several devices; the attribute is per
@@ -2128,13 +2076,12 @@ void mf_device_setup(Ctx &C)
     std::lock_guard<std::mutex> lk(mu);
     bool ok = true;
     auto big = [&](const void *f) { ok &= hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess; };
-    big(reinterpret_cast<const void *>(k_mf_front<6, 4, true>)); big(reinterpret_cast<const void *>(k_mf_front<7, 4, true>));
-    big(reinterpret_cast<const void *>(k_mf_front<8, 4, true>)); big(reinterpret_cast<const void *>(k_mf_front<6, 8, true>));
-    big(reinterpret_cast<const void *>(k_mf_front<7, 8, true>)); big(reinterpret_cast<const void *>(k_mf_front<8, 8, true>));
-    // (their packed instantiations: 50 / 65 / 81 KB at eight waves -- only eight tile rows still pass 64 KB; asked for all alike)
-    big(reinterpret_cast<const void *>(k_mf_front<6, 4, true, true>)); big(reinterpret_cast<const void *>(k_mf_front<7, 4, true, true>));
-    big(reinterpret_cast<const void *>(k_mf_front<8, 4, true, true>)); big(reinterpret_cast<const void *>(k_mf_front<6, 8, true, true>));
-    big(reinterpret_cast<const void *>(k_mf_front<7, 8, true, true>)); big(reinterpret_cast<const void *>(k_mf_front<8, 8, true, true>));
+    // the static front kernels of six tile rows on with the image in LDS, square and packed (packed: 50 / 65 / 81 KB at eight
+    // waves -- only eight tile rows still pass 64 KB; asked for all alike)
+#define MF_BIG_FRONT(id, T, NW, IMG) \
+    if (IMG && T >= 6) { big(reinterpret_cast<const void *>(k_mf_front<T, NW, IMG, false>)); big(reinterpret_cast<const void *>(k_mf_front<T, NW, IMG, IMG>)); }
+    MF_KERNEL_LIST(MF_ROW_SKIP, MF_ROW_SKIP, MF_BIG_FRONT)
+#undef MF_BIG_FRONT
     big(reinterpret_cast<const void *>(k_mf_fwd2<true>)); big(reinterpret_cast<const void *>(k_mf_bwd2<true>));
     big(reinterpret_cast<const void *>(k_mf_fwd2<false>)); big(reinterpret_cast<const void *>(k_mf_bwd2<false>));
     big(reinterpret_cast<const void *>(k_mf_solve_top2));
@@ -2150,42 +2097,25 @@ void mf_values(Ctx &C, int want)
 {
     const DV &d = C.d;
     hipStream_t s = C.stream;
+    const MfSwitches sw = mf_read_switches();
     const int nb = d.mf.fronts1 && d.spec_mode != 0 ? 2 * d.B : d.B;
-    const bool serial = d.mf.nvblk == 0 || (getenv("SQPHIP_MF_VALUES_SERIAL") && atoi(getenv("SQPHIP_MF_VALUES_SERIAL")) != 0);     // (read per call: tests flip it)
     C.tm.open(s); C.mf_census[MFK_VALUES]++;
-    if (serial) hipLaunchKernelGGL(k_mf_values_serial, dim3((d.mf.nnzK + 255) / 256, nb), dim3(256), 0, s, d, want);
+    if (d.mf.nvblk == 0 || sw.values_serial) hipLaunchKernelGGL(k_mf_values_serial, dim3((d.mf.nnzK + 255) / 256, nb), dim3(256), 0, s, d, want);
     else hipLaunchKernelGGL(k_mf_values, dim3(d.mf.nvblk, nb), dim3(MF_VBLK_ITEMS), 0, s, d, want);
     C.tm.close(KC_VALUES, s);
-}
-
-// What mf_factor's choice of instantiation takes from the launch itself, besides the switches it reads per call: the tiles of
-// its kernel, whether it was a launch of at most eight fronts when the schedule was built (MfLaunch::small: stat_min, nw4, the
-// LDS image of six to eight tiles) and whether its level belongs to the narrow top of the tree (stat_min).  The last one
-// decides nothing from four tiles on: stat_min is then 1 or 4 by default, and a SQPHIP_MF_STATIC_MIN holds for every launch
-// alike.  The deferral pass of mf_build_plan moves a front only between launches this function calls equal, so no front
-// changes kernel; whoever adds an input to the choice below adds it here.
-static inline bool mf_launch_narrow(const MfLaunch &L, int narrow_level) { return L.level >= narrow_level; }
-bool mf_same_selection(const MfLaunch &a, const MfLaunch &b, int narrow_level)
-{
-    return a.tiles == b.tiles && a.small == b.small &&
-           (a.tiles >= 4 || mf_launch_narrow(a, narrow_level) == mf_launch_narrow(b, narrow_level));
 }
 
 void mf_factor(Ctx &C, int want, bool with_rhs, bool values_done)
 {
     const DV &d = C.d;
     hipStream_t s = C.stream;
-    static const bool v1 = getenv("SQPHIP_MF_V1") != nullptr;      // cross-check: the plain rank-1 kernel for every front
+    const MfSwitches sw = mf_read_switches();
     const int wr = (int)with_rhs;
     const int nb = d.mf.fronts1 && d.spec_mode != 0 ? 2 * d.B : d.B;         // with the second candidate the factor side runs over 2 B "instances"
     // (values_done: the stage kernel that built the right-hand sides has assembled the values too: mf_values_block)
-    if (!v1 && !values_done) mf_values(C, want);
-    // static front kernels (k_mf_front<T, NW, LDSIMG>) unless SQPHIP_MF_STATIC=0 asks for the generic ones (cross-check)
-    const bool stat = !(getenv("SQPHIP_MF_STATIC") && atoi(getenv("SQPHIP_MF_STATIC")) == 0);     // (read per call: tests flip it)
-    const bool packed = !(getenv("SQPHIP_MF_F2_PACKED") && atoi(getenv("SQPHIP_MF_F2_PACKED")) == 0);   // (likewise) LDS image of the generic kernels as packed tiles
-    const bool fpacked = !(getenv("SQPHIP_MF_FRONT_PACKED") && atoi(getenv("SQPHIP_MF_FRONT_PACKED")) == 0);   // (likewise) ... and of the static front kernels
+    if (!sw.v1 && !values_done) mf_values(C, want);
     // the levels below the spine as level launches, the spine (mfplan.hip: spine_level) by one workgroup per instance
-    const bool spine = !v1 && d.mf.sp_n > 0 && C.mf_big_lds;
+    const bool spine = mf_spine_runs(d.mf.sp_n > 0, C.mf_big_lds, sw);
     int li = 0, cls_open = -1;        // (detail timers: one event pair around the launches below the narrow top, one around those of the top)
     for (const MfLaunch &L : C.mfp().fac) {
         if (spine && li++ >= C.mfp().fac_below) break;
@@ -2193,130 +2123,76 @@ void mf_factor(Ctx &C, int want, bool with_rhs, bool values_done)
         if (cls != cls_open) { if (cls_open >= 0) C.tm.close(cls_open, s); C.tm.open(s); cls_open = cls; }
         const dim3 grid(L.count, nb);
         const int T = L.tiles;
-        if (v1 || T > 13) { C.mf_census[MFK_FACTOR_R1]++; hipLaunchKernelGGL((k_mf_factor<256, true>), grid, dim3(256), 0, s, d, L.begin, want, wr); continue; }
+        const MfFrontChoice ch = mf_select_launch(L, C.mfp().narrow_level, C.mf_big_lds, sw);
+        C.mf_census[ch.kid]++;
+        switch (ch.kid) {
         // generic kernels: dynamic LDS = [image (16 T)^2 when it lives in LDS][panel X and L: 2 x 4 x 16 T][4 x 4 block][1 / D: 16 T];
         // packed image (k_mf_factor2, PACKED): the larger of the T (T + 1) / 2 tiles and the panel buffers
-#define MF_GENERIC(NW, MAXT, IMG) do { constexpr int kid_ = mf_factor2_kid(NW, MAXT, IMG); static_assert(kid_ >= 0, "census: no counter"); C.mf_census[kid_]++; \
-        if (IMG && packed) hipLaunchKernelGGL((k_mf_factor2<NW, MAXT, IMG, IMG>), grid, dim3(64 * NW), 8 * mf_factor2_lds_doubles(T, IMG, true), s, d, L.begin, want, wr, T); \
-        else hipLaunchKernelGGL((k_mf_factor2<NW, MAXT, IMG, false>), grid, dim3(64 * NW), 8 * mf_factor2_lds_doubles(T, IMG, false), s, d, L.begin, want, wr, T); } while (0)
-        // static kernels with the image in LDS: packed tiles, or -- SQPHIP_MF_FRONT_PACKED=0 -- the square instantiation (same census entry)
-#define MF_STATIC(TT, NW, IMG) do { constexpr int kid_ = mf_front_kid(TT, NW, IMG); static_assert(kid_ >= 0, "census: no counter"); C.mf_census[kid_]++; \
-        if (IMG && fpacked) hipLaunchKernelGGL((k_mf_front<TT, NW, IMG, IMG>), grid, dim3(64 * NW), 8 * (size_t)mf_front_lds_doubles(TT, NW, IMG, IMG), s, d, L.begin, want, wr); \
-        else hipLaunchKernelGGL((k_mf_front<TT, NW, IMG, false>), grid, dim3(64 * NW), 8 * (size_t)mf_front_lds_doubles(TT, NW, IMG, false), s, d, L.begin, want, wr); } while (0)
-        // ... from four tile rows on: below that the generic kernels are as fast per front and lighter (registers, code
-        // size) where thousands of small fronts are in flight.  Measured (QP/s, static from T = 1 / from T = 4 / never):
-        // 512 x IEEE-118 5565 / 5507 / 5259, 64 x IEEE-118 1372 / - / 1315, 9241 shape 20.6 / 24.3 / 23.4, IEEE-14 50.9 k /
-        // 55.4 k / 53.9 k.  SQPHIP_MF_STATIC_MIN moves the threshold (tests run it at 1 to cover every instantiation).
-        // (round 4: on a narrow level -- a handful of fronts, i.e. the levels the spine kernel takes over -- the static
-        //  kernels run every front: the level-launch build, SQPHIP_MF_SPINE=0, then gives the bits of the spine kernel)
-        const int stat_min = getenv("SQPHIP_MF_STATIC_MIN") ? atoi(getenv("SQPHIP_MF_STATIC_MIN")) : (L.small && mf_launch_narrow(L, C.mfp().narrow_level) ? 1 : 4);
-        // four waves instead of two for fronts of four (bit 0) / five (bit 1) tile rows on the levels near the top of the
-        // tree (a handful of fronts: latency, not occupancy, is what counts there): 512 x IEEE-118 7 100 -> 7 154 / 7 297 / 7 326
-        // QP/s with bit 0 / bit 1 / both, same bits (SQPHIP_MF_NW4=0: two waves everywhere)
-        // ... and eight instead of four for six to eight tile rows there: 7 323 -> 7 403 QP/s, same bits (SQPHIP_MF_NW8=0: four)
-        const bool nw8 = !(getenv("SQPHIP_MF_NW8") && atoi(getenv("SQPHIP_MF_NW8")) == 0);
-        const int nw4 = L.small ? (getenv("SQPHIP_MF_NW4") ? atoi(getenv("SQPHIP_MF_NW4")) : 3) : 0;
-        const bool big_img = C.mf_big_lds && !(getenv("SQPHIP_MF_BIG_LDSIMG") && atoi(getenv("SQPHIP_MF_BIG_LDSIMG")) == 0);     // (read per call: tests flip it)
-        // (round 4: nine to twelve tile rows too -- the fronts of 129 .. 192 rows of the 1354- and 9241-bus shapes --, eight waves,
-        //  image in the arena: 1354 buses 549 -> 557 QP/s, 9241 buses 28.5 -> 29.2; SQPHIP_MF_STATIC_MAX = 8 gives them back to the
-        //  generic kernel)
-        static const int stat_max = getenv("SQPHIP_MF_STATIC_MAX") ? atoi(getenv("SQPHIP_MF_STATIC_MAX")) : 12;
-        if (!stat || T > stat_max || T > 12 || T < stat_min) {
-            if (T <= 2) MF_GENERIC(1, 3, true);
-            else if (T <= 4) MF_GENERIC(2, 5, true);
-            else if (T <= 5) MF_GENERIC(4, 4, true);
-            else if (T <= 8) MF_GENERIC(4, 9, false);
-            else MF_GENERIC(8, 12, false);
-            continue;
+#define MF_LAUNCH_F2(id, NW, MAXT, IMG) case id: \
+            if (IMG && ch.packed) hipLaunchKernelGGL((k_mf_factor2<NW, MAXT, IMG, IMG>), grid, dim3(64 * NW), 8 * mf_factor2_lds_doubles(T, IMG, true), s, d, L.begin, want, wr, T); \
+            else hipLaunchKernelGGL((k_mf_factor2<NW, MAXT, IMG, false>), grid, dim3(64 * NW), 8 * mf_factor2_lds_doubles(T, IMG, false), s, d, L.begin, want, wr, T); \
+            break;
+        // static kernels with the image in LDS: packed tiles, or the square instantiation (same census entry)
+#define MF_LAUNCH_FRONT(id, TT, NW, IMG) case id: \
+            if (IMG && ch.packed) hipLaunchKernelGGL((k_mf_front<TT, NW, IMG, IMG>), grid, dim3(64 * NW), 8 * (size_t)mf_front_lds_doubles(TT, NW, IMG, IMG), s, d, L.begin, want, wr); \
+            else hipLaunchKernelGGL((k_mf_front<TT, NW, IMG, false>), grid, dim3(64 * NW), 8 * (size_t)mf_front_lds_doubles(TT, NW, IMG, false), s, d, L.begin, want, wr); \
+            break;
+        MF_KERNEL_LIST(MF_ROW_SKIP, MF_LAUNCH_F2, MF_LAUNCH_FRONT)
+#undef MF_LAUNCH_F2
+#undef MF_LAUNCH_FRONT
+        case MFK_FACTOR_R1: hipLaunchKernelGGL((k_mf_factor<256, true>), grid, dim3(256), 0, s, d, L.begin, want, wr); break;
+        default: throw std::string("sqphip: mf_factor: mf_select_front named a kernel that is no front kernel");
         }
-        switch (T) {
-        case 1: MF_STATIC(1, 1, true); break;
-        case 2: MF_STATIC(2, 1, true); break;
-        case 3: MF_STATIC(3, 1, true); break;
-        case 4: if (nw4 & 1) MF_STATIC(4, 4, true); else MF_STATIC(4, 2, true); break;
-        case 5: if (nw4 & 2) MF_STATIC(5, 4, true); else MF_STATIC(5, 2, true); break;
-        // (six to eight tile rows: the image fits the 160 KB of LDS of gfx950 too -- 74 / 100 / 131 KB square, 43 / 57 / 74 KB packed -- once more than
-        //  64 KB of dynamic LDS has been asked for; only for the handful of fronts of a level near the top of the tree, where
-        //  one workgroup of the square image per CU was all there was anyway: +0.3 % on 512 x IEEE-118; SQPHIP_MF_BIG_LDSIMG=0: image
-        //  in the arena.  With the packed image two workgroups of six or seven tile rows fit a CU, so the reason no longer binds
-        //  there; the rule stands until the wide launches have been measured with the image in LDS: DESIGN.md section 10)
-        case 6: if (big_img && L.small) { if (nw8) MF_STATIC(6, 8, true); else MF_STATIC(6, 4, true); } else MF_STATIC(6, 4, false); break;
-        case 7: if (big_img && L.small) { if (nw8) MF_STATIC(7, 8, true); else MF_STATIC(7, 4, true); } else MF_STATIC(7, 4, false); break;
-        case 8: if (big_img && L.small) { if (nw8) MF_STATIC(8, 8, true); else MF_STATIC(8, 4, true); } else MF_STATIC(8, 4, false); break;
-        case 9: MF_STATIC(9, 8, false); break;
-        case 10: MF_STATIC(10, 8, false); break;
-        case 11: MF_STATIC(11, 8, false); break;
-        default: MF_STATIC(12, 8, false); break;
-        }
-#undef MF_GENERIC
-#undef MF_STATIC
     }
     if (cls_open >= 0) C.tm.close(cls_open, s);
     if (spine) { C.tm.open(s); C.mf_census[MFK_SPINE]++; hipLaunchKernelGGL(k_mf_spine, dim3(1, nb), dim3(MF_SP_NT), (size_t)C.mfp().spine_lds_bytes, s, d, want, wr); C.tm.close(KC_FRONTS_TOP, s); }
     C.mf_factor_launches += spine ? (long)C.mfp().fac_below + 1 : (long)C.mfp().fac.size();
 }
 
-bool mf_solve_tests_inertia(const Ctx &C)
-{
-    static const bool off = getenv("SQPHIP_MF_INERTIA_KERNEL") != nullptr;      // experiment switch: keep k_inertia
-    return !off && C.d.sparse && C.d.mf.top_n > 0 && !mf_generic_solves() && !(C.d.B >= (getenv("SQPHIP_MF_INST_SOLVE_MIN") ? atoi(getenv("SQPHIP_MF_INST_SOLVE_MIN")) : (1 << 30)));
-}
+bool mf_solve_tests_inertia(const Ctx &C) { return mf_top_tests_inertia(C.d.sparse != 0, C.d.mf.top_n, mf_read_switches()); }
 
 // x (d.xv) <- K^-1 x through the factors; skip_fwd: d.vv already holds D^-1 L^-1 b (fused into mf_factor)
 // also (-1: none; needs the streamed top): a second phase served by the same top and backward launches, with forward level
 // launches of its own ahead of the top -- one launch group per timing class and census entry, whichever phases it serves
+// A launch per level, one wave per (front, instance): the LDS-staged kernels where every front of the level fits them
+// (mfplan.hip: L.wimg >= 0).
 void mf_solve(Ctx &C, int want, bool skip_fwd, bool inertia, int also)
 {
     const DV &d = C.d;
     hipStream_t s = C.stream;
-    const int generic = mf_generic_solves();
-    // a launch per level, one wave per (front, instance).  The alternative -- ONE workgroup of 16 waves per instance
-    // walking all levels behind workgroup barriers (k_mf_solve_inst, batch >= SQPHIP_MF_INST_SOLVE_MIN) -- saves the
-    // 2 x levels launches but caps the parallelism at 16 waves per instance: measured 5306 against 5948 QP/s on
-    // 512 x IEEE-118, so it is off unless asked for.
-    static const int inst_min = getenv("SQPHIP_MF_INST_SOLVE_MIN") ? atoi(getenv("SQPHIP_MF_INST_SOLVE_MIN")) : (1 << 30);
-    if (d.B >= inst_min && d.mf.max_front * 8 * 16 <= 64 * 1024) {
-        C.mf_census[MFK_SOLVE_INST]++;
-        hipLaunchKernelGGL(k_mf_solve_inst<16>, dim3(d.B), dim3(1024), (size_t)d.mf.max_front * 8 * 16, s, d, want, skip_fwd ? 0 : 1, generic);
-        return;
-    }
-    // level launches: the LDS-staged kernels where every front of the level fits them (mfplan.hip: L.wimg >= 0)
-    const bool lvl2 = !(getenv("SQPHIP_MF_LEVEL2") && atoi(getenv("SQPHIP_MF_LEVEL2")) == 0);      // (read per call: tests flip it)
+    const MfSwitches sw = mf_read_switches();
+    const int generic = sw.generic;
     if (!C.mf_big_lds) throw std::string("sqphip: the solve kernels could not be granted 160 KB of dynamic LDS on this device (mf_device_setup)");
-    if (also >= 0 && !(skip_fwd && d.mf.top_n > 0 && !generic && d.B < inst_min)) throw std::string("sqphip: mf_solve: a second phase needs the streamed top behind a fused forward pass");
+    if (also >= 0 && !(skip_fwd && d.mf.top_n > 0 && !generic)) throw std::string("sqphip: mf_solve: a second phase needs the streamed top behind a fused forward pass");
     const int fwant = also >= 0 ? also : want;        // (the forward level launches serve one phase: `want` has its forward half behind it when `also` is given)
     const bool run_fwd = !skip_fwd || also >= 0;
     if (run_fwd && !C.mfp().fwd.empty()) C.tm.open(s);
     if (run_fwd)
         for (const MfLaunch &L : C.mfp().fwd) {
-            C.mf_census[lvl2 && !generic && L.wimg >= 0 ? (L.hasbig ? MFK_FWD2_BIG : MFK_FWD2) : MFK_FWD]++;
-            if (lvl2 && !generic && L.wimg >= 0) {
-                if (L.hasbig) hipLaunchKernelGGL(k_mf_fwd2<true>, dim3(L.count, d.B), dim3(256), L.lds2, s, d, L.begin, fwant, L.wimg);
-                else hipLaunchKernelGGL(k_mf_fwd2<false>, dim3(L.count, d.B), dim3(256), L.lds2, s, d, L.begin, fwant, L.wimg);
-            }
+            const MfKernel k = mf_select_solve_level(L.wimg, L.hasbig != 0, sw);
+            C.mf_census[k]++;
+            if (k == MFK_FWD2_BIG) hipLaunchKernelGGL(k_mf_fwd2<true>, dim3(L.count, d.B), dim3(256), L.lds2, s, d, L.begin, fwant, L.wimg);
+            else if (k == MFK_FWD2) hipLaunchKernelGGL(k_mf_fwd2<false>, dim3(L.count, d.B), dim3(256), L.lds2, s, d, L.begin, fwant, L.wimg);
             else hipLaunchKernelGGL(k_mf_fwd, dim3(L.count, d.B), dim3(256), L.lds_bytes, s, d, L.begin, fwant, generic, L.tiles, L.cls, L.lds_bytes / 8 - L.cls);
         }
     if (run_fwd && !C.mfp().fwd.empty()) C.tm.close(KC_SOLVE_LEVELS, s);
-    const bool has_top = (d.mf.top_n > 0 && !generic) || C.mfp().top.count > 0;
-    if (has_top) C.tm.open(s);
-    if (d.mf.top_n > 0 && !generic) {
-        const size_t lds = (size_t)C.mfp().top2_lds_bytes;
-        C.mf_census[MFK_SOLVE_TOP2]++;
-        const char *ser = getenv("SQPHIP_INERTIA_SERIAL");      // (read per call: tests flip it) the former counting loop and order
-        hipLaunchKernelGGL(k_mf_solve_top2, dim3(d.B), dim3(256), lds, s, d, want, skip_fwd ? 0 : 1, inertia ? (ser && atoi(ser) ? 2 : 1) : 0, also);
-    } else if (const MfLaunch &T = C.mfp().top; T.count > 0) {
-        C.mf_census[MFK_SOLVE_TOP]++;
+    const MfKernel top = mf_select_top(d.mf.top_n, C.mfp().top.count, sw);
+    if (top != MFK_COUNT) { C.tm.open(s); C.mf_census[top]++; }
+    if (top == MFK_SOLVE_TOP2) {
+        hipLaunchKernelGGL(k_mf_solve_top2, dim3(d.B), dim3(256), (size_t)C.mfp().top2_lds_bytes, s, d, want, skip_fwd ? 0 : 1,
+                           inertia ? (sw.inertia_serial ? 2 : 1) : 0, also);
+    } else if (top == MFK_SOLVE_TOP) {
+        const MfLaunch &T = C.mfp().top;
         hipLaunchKernelGGL(k_mf_solve_top, dim3(d.B), dim3(256), T.lds_bytes, s, d, T.begin, T.count, want, skip_fwd ? 0 : 1, generic,
                            T.tiles, T.cls, T.lds_bytes / 8 - T.cls);
     }
-    if (has_top) C.tm.close(KC_SOLVE_TOP, s);
+    if (top != MFK_COUNT) C.tm.close(KC_SOLVE_TOP, s);
     if (!C.mfp().bwd.empty()) C.tm.open(s);
     for (const MfLaunch &L : C.mfp().bwd) {
-        C.mf_census[lvl2 && !generic && L.wimg >= 0 ? (L.hasbig ? MFK_BWD2_BIG : MFK_BWD2) : MFK_BWD]++;
-        if (lvl2 && !generic && L.wimg >= 0) {
-            if (L.hasbig) hipLaunchKernelGGL(k_mf_bwd2<true>, dim3(L.count, d.B), dim3(256), L.lds2, s, d, L.begin, want, L.wimg, also);
-            else hipLaunchKernelGGL(k_mf_bwd2<false>, dim3(L.count, d.B), dim3(256), L.lds2, s, d, L.begin, want, L.wimg, also);
-        }
+        const MfKernel k = mf_bwd_of(mf_select_solve_level(L.wimg, L.hasbig != 0, sw));
+        C.mf_census[k]++;
+        if (k == MFK_BWD2_BIG) hipLaunchKernelGGL(k_mf_bwd2<true>, dim3(L.count, d.B), dim3(256), L.lds2, s, d, L.begin, want, L.wimg, also);
+        else if (k == MFK_BWD2) hipLaunchKernelGGL(k_mf_bwd2<false>, dim3(L.count, d.B), dim3(256), L.lds2, s, d, L.begin, want, L.wimg, also);
         else hipLaunchKernelGGL(k_mf_bwd, dim3(L.count, d.B), dim3(256), L.lds_bytes, s, d, L.begin, want, generic, L.tiles, L.cls, L.lds_bytes / 8 - L.cls, also);
     }
     if (!C.mfp().bwd.empty()) C.tm.close(KC_SOLVE_LEVELS, s);

@@ -114,11 +114,9 @@ struct MfGather { int where, src_begin, src_end, src0; };
 // Solve launches also carry what the LDS-staged kernels (k_mf_fwd2 / k_mf_bwd2) need: wimg = doubles of a wave's image
 // buffer (-1: a front of the level does not fit them), lds2 = their dynamic LDS.
 // Factor launches: small = the launch held at most eight fronts when the schedule was built, before the deferral pass of
-// mf_build_plan handed it fronts of dissolved launches: mf_factor chooses the instantiation from it, not from `count`, so a
-// launch that gains fronts keeps its kernel.
+// mf_build_plan handed it fronts of dissolved launches: the instantiation is chosen from it (mf_select.hpp), not from `count`,
+// so a launch that gains fronts keeps its kernel.
 struct MfLaunch { int begin, count, threads, lds_bytes, cls, tiles; int wimg = -1, lds2 = 0, hasbig = 1; int level = 0; int small = 0; };
-// Two factor launches run the same instantiation under every setting of mf_factor's switches (mfront.hip, next to the choice)
-bool mf_same_selection(const MfLaunch &a, const MfLaunch &b, int narrow_level);
 
 // One front of the narrow top of the assembly tree as the streaming solve kernel (k_mf_solve_top2, mfront.hip) sees it:
 // where its factor lives in the arena, the leading dimension of its LDS image (odd: the transposed reads of the

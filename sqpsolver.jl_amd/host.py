@@ -154,6 +154,23 @@ def mf_front_launches(n, m, jrow, jcol, hrow, hcol, gL, gU, condense=1, batch=1)
     return fr
 
 
+def mf_factor_kernels(n, m, jrow, jcol, hrow, hcol, gL, gU, condense=1, batch=1, big_lds=1):
+    """What the factorisation launches for the plan of `mf_plan_info` under the current environment
+    (`sqphip_mf_factor_kernels`, host only): an (nl, 4) array, one row per factor launch, of (index of the chosen front kernel
+    in the census of `Context.mf_census`, packed LDS image, the spine kernel takes the launch instead, the launch held at most
+    eight fronts before the deferral pass)."""
+    L = _lib.lib()
+    jr, jc, hr, hc = (np.ascontiguousarray(a, dtype=np.int64) for a in (jrow, jcol, hrow, hcol))
+    nl = C.c_int32()
+    args = (n, m, len(jr), _l(jr), _l(jc), len(hr), _l(hr), _l(hc), _d(_f(gL)), _d(_f(gU)), int(condense), int(batch), int(big_lds))
+    if L.sqphip_mf_factor_kernels(*args, None, 0, C.byref(nl)) != 0:
+        raise SqpHipError("sqphip_mf_factor_kernels failed")
+    ker = np.zeros((nl.value, 4), dtype=np.int32)
+    if L.sqphip_mf_factor_kernels(*args, _i(ker), nl.value, C.byref(nl)) != 0:
+        raise SqpHipError("sqphip_mf_factor_kernels failed")
+    return ker
+
+
 def mf_values_blocks(n, m, jrow, jcol, hrow, hcol, gL, gU, condense=1, values=None):
     """Blocks of the item-parallel values kernel (`sqphip_mf_values_blocks`, host only): a dict with blocks ((nb, 4): first
     destination, first item, destinations, items; nb = 0: the plan keeps the one-thread-per-destination kernel) and item_ptr;

@@ -17,10 +17,8 @@ pytestmark = pytest.mark.gpu
 FAMILIES = {S.name: S for S in MS.families()}
 B, IDLE = 5, 3                       # odd batch, one idle instance: the candidate grid (2 B) and the early returns
 CENSUS = {}                          # launches seen by the contexts of this module, summed (test_census_saw_every_kernel)
-# kernels no test can reach by environment switches read per call, with the reason
-CENSUS_EXCLUDED = {
-    "k_mf_solve_inst<16>": "behind SQPHIP_MF_INST_SOLVE_MIN, read once per process through a static const",
-}
+# kernels no test can reach by environment switches, with the reason: none -- every switch is read per call
+CENSUS_EXCLUDED = {}
 # the switches of test_gpu_parity.py::test_every_front_kernel_variant_matches_the_host_reference, and the spine
 ENV_VARIANTS = [{}, {"SQPHIP_MF_STATIC_MIN": "1"}, {"SQPHIP_MF_STATIC": "0"},
                 {"SQPHIP_MF_TOP2": "0", "SQPHIP_MF_LEVEL2": "0", "SQPHIP_MF_BIG_LDSIMG": "0"},
@@ -219,6 +217,34 @@ def test_kernel_variants_on_the_families(env, monkeypatch):
         monkeypatch.setenv(k, v)
     for i, name in enumerate(CENSUS_FAMILIES):
         _run_family(FAMILIES[name], "well", 1, seed=40 + i)
+
+
+@pytest.mark.parametrize("env", ENV_VARIANTS, ids=lambda e: ",".join(f"{k}={v}" for k, v in e.items()) or "default")
+def test_the_factor_census_of_a_sweep_is_the_predicted_choice(env, monkeypatch):
+    """What the factorisation of a sweep launched, by the census, against what the host-only hook sqphip_mf_factor_kernels
+    predicts for the plan under the same switches (big_lds = 1: the device grants 160 KB of LDS): the factor-side entries
+    -- rank-1, generic and static front kernels, spine -- equal the predicted launches per kernel times one common integer
+    >= 1, the mf_factor calls of the sweep; an entry predicted zero is zero."""
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)
+    names = _census_names()
+    factor_side = [k for k in names if k.startswith(("k_mf_factor", "k_mf_front", "k_mf_spine"))]
+    assert len(factor_side) == 27
+    for i, name in enumerate(CENSUS_FAMILIES):
+        S = FAMILIES[name]
+        before = dict(CENSUS)
+        _run_family(S, "well", 1, seed=120 + i)
+        seen = {k: CENSUS.get(k, 0) - before.get(k, 0) for k in factor_side}
+        ker = pkg.mf_factor_kernels(S.n, S.m, S.jrow, S.jcol, S.hrow, S.hcol, S.gL, S.gU, 1, B, 1)
+        want = dict.fromkeys(factor_side, 0)
+        for kid, _packed, spine, _small in ker.tolist():
+            if not spine:
+                want[names[kid]] += 1
+        want["k_mf_spine"] += int(ker[:, 2].any())
+        print(name, {k: (seen[k], want[k]) for k in factor_side if seen[k] or want[k]})
+        calls = {seen[k] // want[k] for k in factor_side if want[k]}
+        assert len(calls) == 1 and min(calls) >= 1, (name, env, seen, want)
+        assert all(seen[k] == want[k] * min(calls) for k in factor_side), (name, env, seen, want)
 
 
 def test_census_saw_every_factor_and_solve_kernel(monkeypatch):
