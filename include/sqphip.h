@@ -562,6 +562,40 @@ int sqphip_nlp_add_softmax_block(sqphip_ctx *ctx, int64_t N, int32_t d, int32_t 
                                  const int64_t *cols /* [Kf][d] 1-based */, const double *A /* [N][d] row-major */,
                                  const int32_t *labels /* [N] 0-based */, const double *shift /* [Kf][N] or NULL: zeros */,
                                  const double *weight /* [N] or NULL: ones */, int32_t *blk_out /* 0-based block number, or NULL */);
+/* Dense data blocks with several outputs: one design matrix, R weight vectors, a target row each.  Output r adds
+ *     sum_{i < N} W[r][i] kappa(sum_{j < d} A[i][j] x_{cols[j]} + S[i])
+ * to row rows[r]; row 0 is the objective, row i >= 1 a nonlinear constraint row (i > num_linear).  Constraints on the data the
+ * objective is fitted to: a mean loss of one class below a level (Neyman-Pearson), a calibration or parity equality, an
+ * entropic-risk budget, moment constraints.  Kinds, exp, par and the limits on d (1..128), N and N d are those of
+ * sqphip_nlp_add_block; 1 <= R <= 8, the rows are distinct.  A, cols, the kind, rows and R are shared by the batch; W [R][N]
+ * and S [N] belong to the instance.  The block counts among the four blocks of a context and is evaluated in block order with
+ * the others, behind the same barrier.
+ * State rules and re-lay as for sqphip_nlp_add_block (SQPHIP_ESTATE once the layout is final); the instance's block grows by
+ *     W [R][N] | S [N]                                                            (padded to an even count)
+ * sqphip_nlp_set_instance_block and sqphip_nlp_stream_set_block serve the block with a weight array of R N entries;
+ * sqphip_nlp_stream_set restores the data of this call.
+ * The Jacobian COO of sqphip_create must hold (i, cols[j]) for every target row i >= 1 and every column; unless nnzH = 0 the
+ * Hessian COO must hold the lower entry of every pair of columns.  The first COO copy of a slot owns it.
+ * SQPHIP_EINVAL, with sqphip_last_error naming the block and the 1-based output, column or entry: everything
+ * sqphip_nlp_add_block refuses, R outside 1..8, null rows, a row outside 0..m, a row twice, a row in 1..num_linear, a missing
+ * Jacobian entry (row and column named).
+ * Evaluation (one workgroup per instance; every sum in an order that depends on N, d and R only, no atomics):
+ *   points    u_i as in sqphip_nlp_add_block; kappa, kappa', kappa'' once per point;
+ *   values    output r: thread t sums W[r][i] kappa_i over i = t, t + 1024, ..., the xor butterfly 32 .. 1 within a wave,
+ *             thread 0 adds the 16 wave sums in wave order; the result is added to f (row 0) or g[row - 1];
+ *   first derivatives  the pairs (r, j), numbered r d + j, are dealt to the waves; lane l sums (W[r][i] kappa'_i) A[i][j] over
+ *             i = l, l + 64, ..., the same butterfly, added to grad[cols[j]] (row 0) or the Jacobian slot of (rows[r], cols[j]);
+ *   Hessian   e_i = 0, e_i = fma(mu_r, W[r][i], e_i) for r = 0 .. R - 1, mu_r = sigma (row 0) or lambda[row - 1];
+ *             z_i = e_i kappa''_i; then the lower 16 x 16 tiles of sqphip_nlp_add_block with the operand z_p A[p][r] (one
+ *             rounding), and the sum is added as it is to the entry's COO slot: one MFMA pass whatever R is.
+ * Results are bit-reproducible and independent of slot, neighbours and instance groups.  A context without such a block
+ * files the bits it filed before this call existed; a block with R = 1 on row 0 need not file the bits of
+ * sqphip_nlp_add_block (the Hessian weight enters in another place). */
+int sqphip_nlp_add_row_block(sqphip_ctx *ctx, int32_t kind, int32_t exp, double par, int64_t N, int32_t d,
+                             const int64_t *cols /* [d] 1-based */, const double *A /* [N][d] row-major */,
+                             int32_t R, const int64_t *rows /* [R] 0: objective, i: row i */,
+                             const double *shift /* [N] or NULL: zeros */,
+                             const double *weight /* [R][N] or NULL: ones */, int32_t *blk_out);
 /* Per-instance values (f0 one value, g0 [m], tcoef [nterms] in the term order of the attach) and the start x0 [n];
  * any pointer may be NULL: keep.  Bounds go through sqphip_set_bounds. */
 int sqphip_nlp_set_instance(sqphip_ctx *ctx, int32_t inst, const double *f0, const double *g0,

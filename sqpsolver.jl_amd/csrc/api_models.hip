@@ -453,15 +453,15 @@ static int nlp_block_begin(sqphip_ctx *h, const std::string &who, int &kb, std::
     return SQPHIP_OK;
 }
 
-// Re-lays the instances' blocks of doubles behind what they hold with W [N] | S [nS] of block kb (weight NULL: ones, shift
+// Re-lays the instances' blocks of doubles behind what they hold with W [nW] | S [nS] of block kb (weight NULL: ones, shift
 // NULL: zeros), uploads A [N][d] and its transpose, cv and hs, and files the block K (ke, par, K, Kf, y: the caller's; wsz:
 // its doubles of workspace) in the context's NlpDev.
-static int nlp_block_commit(sqphip_ctx *h, const std::string &blk, int kb, long N, int d, long nS, long wsz, const double *A,
+static int nlp_block_commit(sqphip_ctx *h, const std::string &blk, int kb, long N, int d, long nW, long nS, long wsz, const double *A,
                             const std::vector<int> &cv, const std::vector<int> &hs, const double *weight, const double *shift,
                             NlpBlkDev K, int32_t *blk_out)
 {
     Ctx &C0 = h->c;
-    const long ow = C0.nl.end, os = ow + N, end = os + nS, nv = (end + 1) & ~1L;
+    const long ow = C0.nl.end, os = ow + nW, end = os + nS, nv = (end + 1) & ~1L;
     const long wz = C0.nl.ws + (kb == 0 ? TPB / 64 + 3 * TPB : 0), ws = wz + wsz;
     if (nv > INT32_MAX || ws > INT32_MAX) { C0.err = blk + ": too many values per instance"; return SQPHIP_EINVAL; }
     return guarded(h, [&](Ctx &C) {
@@ -474,7 +474,7 @@ static int nlp_block_commit(sqphip_ctx *h, const std::string &blk, int kb, long 
         SQPHIP_HIP_OK(hipMemcpyAsync(&P, dv.nlp, sizeof(NlpDev), hipMemcpyDeviceToHost, C.stream));
         SQPHIP_HIP_OK(hipStreamSynchronize(C.stream));
         auto fill = [&](double *v) {
-            for (long i = 0; i < N; ++i) v[ow + i] = weight ? weight[i] : 1.0;
+            for (long i = 0; i < nW; ++i) v[ow + i] = weight ? weight[i] : 1.0;
             for (long i = 0; i < nS; ++i) v[os + i] = shift ? shift[i] : 0.0;
         };
         for (long b = 0; b < B; ++b) {
@@ -496,11 +496,26 @@ static int nlp_block_commit(sqphip_ctx *h, const std::string &blk, int kb, long 
         SQPHIP_HIP_OK(hipMemcpyAsync(const_cast<NlpDev *>(dv.nlp), &P, sizeof(NlpDev), hipMemcpyHostToDevice, C.stream));
         SQPHIP_HIP_OK(hipStreamSynchronize(C.stream));
         C.nl.nv = nv; C.nl.end = end; C.nl.ws = ws;
-        C.nl.blk.push_back(NlpHost::Block{N, ow, os, nS});
+        C.nl.blk.push_back(NlpHost::Block{N, ow, os, nS, nW});
         make_lanes(C);
         if (blk_out) *blk_out = kb;
         return SQPHIP_OK;
     });
+}
+
+// what sqphip_nlp_add_block and sqphip_nlp_add_row_block refuse of the shape and the menu entry; e: the exponent in use
+static std::string nlp_block_menu(int32_t kind, int32_t exp, double par, int64_t N, int32_t d, const int64_t *cols, const double *A, int &e)
+{
+    if (d < 1 || d > NLP_BLOCK_MAX_D) return "d = " + std::to_string(d) + " columns (1.." + std::to_string((int)NLP_BLOCK_MAX_D) + ")";
+    if (N < 1) return "N = " + std::to_string(N) + " points (at least 1)";
+    if (N > INT32_MAX / d) return "N d = " + std::to_string(N) + " x " + std::to_string(d) + " is too large (N d < 2^31)";
+    if (!cols || !A) return "null cols or A";
+    if (kind < NLP_POW || kind > NLP_POWR) return "unknown kind " + std::to_string(kind);
+    e = kind == NLP_POW ? exp : 1;
+    if (kind == NLP_POW && e == 1) return "a plain linear block (POW, e = 1) belongs in the terms";
+    if (e == 0 || e > 32 || e < -32) return "exponent " + std::to_string(e) + " (1 <= |e| <= 32)";
+    if (kind == NLP_POWR && (!std::isfinite(par) || par == 0.0)) return "real exponent " + std::to_string(par) + " (finite and not 0)";
+    return "";
 }
 
 extern "C" int sqphip_nlp_add_block(sqphip_ctx *h, int32_t kind, int32_t exp, double par, int64_t N, int32_t d, const int64_t *cols,
@@ -512,22 +527,44 @@ extern "C" int sqphip_nlp_add_block(sqphip_ctx *h, int32_t kind, int32_t exp, do
     int kb; std::string blk;
     if (int rc = nlp_block_begin(h, who, kb, blk)) return rc;
     auto fail = [&](const std::string &msg) { C0.err = blk + ": " + msg; return (int)SQPHIP_EINVAL; };
-    if (d < 1 || d > NLP_BLOCK_MAX_D) return fail("d = " + std::to_string(d) + " columns (1.." + std::to_string((int)NLP_BLOCK_MAX_D) + ")");
-    if (N < 1) return fail("N = " + std::to_string(N) + " points (at least 1)");
-    if (N > INT32_MAX / d) return fail("N d = " + std::to_string(N) + " x " + std::to_string(d) + " is too large (N d < 2^31)");
-    if (!cols || !A) return fail("null cols or A");
-    if (kind < NLP_POW || kind > NLP_POWR) return fail("unknown kind " + std::to_string(kind));
-    const int e = kind == NLP_POW ? exp : 1;
-    if (kind == NLP_POW && e == 1) return fail("a plain linear block (POW, e = 1) belongs in the terms");
-    if (e == 0 || e > 32 || e < -32) return fail("exponent " + std::to_string(e) + " (1 <= |e| <= 32)");
-    if (kind == NLP_POWR && (!std::isfinite(par) || par == 0.0)) return fail("real exponent " + std::to_string(par) + " (finite and not 0)");
+    int e;
+    if (const std::string bad = nlp_block_menu(kind, exp, par, N, d, cols, A, e); !bad.empty()) return fail(bad);
     std::vector<int> hs, cv;
     const std::string bad = nlp_block_columns(C0.nl.slots, d, cols, cv, hs);
     if (!bad.empty()) return fail(bad);
     NlpBlkDev K = {};
     K.ke = kind + (e + 32) * (1 << NLP_KIND_BITS);
     K.par = kind == NLP_POWR ? par : 0.0;
-    return nlp_block_commit(h, blk, kb, (long)N, d, (long)N, 2 * (long)N, A, cv, hs, weight, shift, K, blk_out);
+    return nlp_block_commit(h, blk, kb, (long)N, d, (long)N, (long)N, 2 * (long)N, A, cv, hs, weight, shift, K, blk_out);
+}
+
+// a block with several outputs (nlp_rowblock_dev.hpp): the checks of sqphip_nlp_add_block, then the rows and their Jacobian slots
+extern "C" int sqphip_nlp_add_row_block(sqphip_ctx *h, int32_t kind, int32_t exp, double par, int64_t N, int32_t d, const int64_t *cols,
+                                        const double *A, int32_t R, const int64_t *rows, const double *shift, const double *weight,
+                                        int32_t *blk_out)
+{
+    const std::string who = "sqphip_nlp_add_row_block";
+    if (!h) return SQPHIP_EINVAL;
+    Ctx &C0 = h->c;
+    int kb; std::string blk;
+    if (int rc = nlp_block_begin(h, who, kb, blk)) return rc;
+    auto fail = [&](const std::string &msg) { C0.err = blk + ": " + msg; return (int)SQPHIP_EINVAL; };
+    int e;
+    if (const std::string bad = nlp_block_menu(kind, exp, par, N, d, cols, A, e); !bad.empty()) return fail(bad);
+    if (R < 1 || R > NLP_BLOCK_MAX_R) return fail("R = " + std::to_string(R) + " outputs (1.." + std::to_string((int)NLP_BLOCK_MAX_R) + ")");
+    if (!rows) return fail("null rows");
+    if (N > INT32_MAX / R) return fail("R N = " + std::to_string(R) + " x " + std::to_string(N) + " is too large (R N < 2^31)");
+    std::vector<int> hs, cv;
+    if (const std::string bad = nlp_block_columns(C0.nl.slots, d, cols, cv, hs); !bad.empty()) return fail(bad);
+    NlpBlkDev K = {};
+    std::vector<int> js;
+    if (const std::string bad = nlp_block_rows(C0.nl.slots, C0.d.m, C0.d.nlin, R, rows, cv, K.row, js); !bad.empty()) return fail(bad);
+    K.ke = kind + (e + 32) * (1 << NLP_KIND_BITS);
+    K.par = kind == NLP_POWR ? par : 0.0;
+    K.R = R;
+    const int rc = guarded(h, [&](Ctx &C) { K.js = C.upload(js); return SQPHIP_OK; });
+    if (rc) return rc;
+    return nlp_block_commit(h, blk, kb, (long)N, d, (long)R * N, (long)N, 3 * (long)N, A, cv, hs, weight, shift, K, blk_out);
 }
 
 // a multinomial (softmax) block (nlp_softmax_dev.hpp)
@@ -559,7 +596,7 @@ extern "C" int sqphip_nlp_add_softmax_block(sqphip_ctx *h, int64_t N, int32_t d,
     Kb.K = K; Kb.Kf = Kf;
     const int rc = guarded(h, [&](Ctx &C) { Kb.y = C.upload(std::vector<int>(labels, labels + N)); return SQPHIP_OK; });
     if (rc) return rc;
-    return nlp_block_commit(h, blk, kb, (long)N, d, (long)Kf * N, (long)Kf * N, A, cv, hs, weight, shift, Kb, blk_out);
+    return nlp_block_commit(h, blk, kb, (long)N, d, (long)N, (long)Kf * N, (long)Kf * N, A, cv, hs, weight, shift, Kb, blk_out);
 }
 
 // weight / shift of block blk into the block of values v (of an instance or of a scenario of the queue); NULL: kept
@@ -567,7 +604,7 @@ static int nlp_block_put(sqphip_ctx *h, double *v, int32_t blk, const double *we
 {
     return guarded(h, [&](Ctx &C) {
         const NlpHost::Block &K = C.nl.blk[blk];
-        h2d(C, v + K.ow, weight, (size_t)K.N); h2d(C, v + K.os, shift, (size_t)K.nS);
+        h2d(C, v + K.ow, weight, (size_t)K.nW); h2d(C, v + K.os, shift, (size_t)K.nS);
         SQPHIP_HIP_OK(hipStreamSynchronize(C.stream));
         return SQPHIP_OK;
     });

@@ -323,4 +323,24 @@ std::string nlp_block_columns(const StructureSlots &S, int D, const int64_t *col
     return "";
 }
 
+std::string nlp_block_rows(const StructureSlots &S, int64_t m, int64_t nlin, int R, const int64_t *rows, const std::vector<int> &cv,
+                           int *row, std::vector<int> &js)
+{
+    const int d = (int)cv.size();
+    js.assign((size_t)R * d, -1);
+    for (int r = 0; r < R; ++r) {
+        const std::string out = "output " + std::to_string(r + 1) + ": row " + std::to_string(rows[r]);
+        if (rows[r] < 0 || rows[r] > m) return out + " outside 0.." + std::to_string(m);
+        for (int r2 = 0; r2 < r; ++r2)
+            if (rows[r2] == rows[r]) return out + " twice (outputs " + std::to_string(r2 + 1) + " and " + std::to_string(r + 1) + ")";
+        if (rows[r] >= 1 && rows[r] <= nlin) return out + " is one of the num_linear = " + std::to_string(nlin) + " linear rows";
+        row[r] = (int)rows[r];
+        for (int j = 0; rows[r] >= 1 && j < d; ++j)
+            if ((js[(size_t)r * d + j] = S.jfind(rows[r] - 1, cv[j])) < 0)
+                return out + ", column " + std::to_string(j + 1) + " needs the Jacobian entry (" + std::to_string(rows[r]) + ", " +
+                       std::to_string(cv[j] + 1) + ") that the structure of sqphip_create lacks";
+    }
+    return "";
+}
+
 }  // namespace sqphip

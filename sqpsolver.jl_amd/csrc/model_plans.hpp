@@ -57,7 +57,8 @@ int build_qcqp_plan(const StructureSlots &S, int64_t m, int64_t nlin, const char
 
 // What a context keeps of an attached factorable NLP (empty, nv = 0: none).  Values of an instance: f0 | g0 | c, with data
 // | b [nfac] | a [nargs] | p [nfac, with a POWR factor only] at ob, oa, op (-1: no p), then W_k [N_k] | S_k [nS_k] of every
-// dense data block (sqphip_nlp_add_block; nS: N, Kf N for a softmax block), padded to even.
+// dense data block (sqphip_nlp_add_block; nS: N, Kf N for a softmax block; nW: N, R N for a block with R outputs,
+// sqphip_nlp_add_row_block), padded to even.
 struct NlpHost {
     long nv = 0, nfac = 0, nterms = 0, nargs = 0;
     long end = 0, ws = 0;                 // doubles in use before the padding; doubles of workspace per instance (DV::nlw)
@@ -66,7 +67,7 @@ struct NlpHost {
     std::vector<double> base;             // [nv] the values given to the attach (NULL parts of a queue scenario)
     std::vector<int> tptr, aptr, kind;    // [nterms + 1], [nfac + 1], [nfac]: what nlp_data_check needs of the structure
     std::vector<int> lin_terms;           // the terms of rows 1..num_linear
-    struct Block { long N, ow, os, nS; };
+    struct Block { long N, ow, os, nS, nW; };
     std::vector<Block> blk;
     bool started = false;                 // a reset, run or queue has seen the layout, which is final from then on
     StructureSlots slots;                 // for the columns of the blocks
@@ -93,5 +94,11 @@ std::string nlp_data_check(const NlpHost &H, int64_t nlin, const char *who, cons
 // cols [D] 1-based, in range and distinct, to cv (0-based), and the COO slot of every lower entry (r, c) of a block's
 // D x D Hessian to hs (-1 throughout when nnzH = 0).  Returns the complaint, empty when there is none.
 std::string nlp_block_columns(const StructureSlots &S, int D, const int64_t *cols, std::vector<int> &cv, std::vector<int> &hs);
+
+// rows [R] of a block with several outputs (0: the objective, i: row i, distinct, none of the rows 1..nlin) to row, and the
+// Jacobian COO slot of every (rows[r], cv[j]) to js [R][d] (-1 for an output on row 0).  Returns the complaint, empty when
+// there is none.
+std::string nlp_block_rows(const StructureSlots &S, int64_t m, int64_t nlin, int R, const int64_t *rows, const std::vector<int> &cv,
+                           int *row, std::vector<int> &js);
 
 }  // namespace sqphip

@@ -40,6 +40,10 @@
 // sqphip_nlp_add_softmax_block: multinomial blocks sum_i W_i [log sum_k exp(u_ik) - u_{i, y_i}] count among the same four
 // blocks; nlp_eval's one call for blocks is nlp_blocks_eval (nlp_softmax_dev.hpp), which walks the blocks in block order and
 // hands each to nlp_block_eval or nlp_softmax_eval.
+// sqphip_nlp_add_row_block: a block with R <= 8 outputs, one weight vector and one target row each (row 0: the objective), on
+// one design matrix: sum_i W_r[i] kappa(A_i'x + S_i) is added to row r's value, A'(W_r kappa') to its Jacobian row and
+// A' diag(kappa'' sum_r mu_r W_r) A to the Hessian of the Lagrangian in one MFMA pass (nlp_rowblock_dev.hpp).  It counts among
+// the same four blocks and adds to gv and jv behind the plan passes as the others add to f, grad and hv.
 #pragma once
 #include "ctx.hpp"
 #include "dev_util.hpp"
@@ -51,7 +55,7 @@ namespace sqphip {
 enum { NLP_NONE = -(1 << 30), NLP_ARG = (1 << 28) - 1 };     // no factor of a term; the argument bits of a plan entry (nargs <= 2^28)
 
 // a dense data block of the objective (sqphip_nlp_add_block; evaluator: nlp_block_dev.hpp, included below)
-enum { NLP_MAX_BLOCKS = 4, NLP_BLOCK_MAX_D = 128, NLP_SOFTMAX_MAX_K = 64 };
+enum { NLP_MAX_BLOCKS = 4, NLP_BLOCK_MAX_D = 128, NLP_SOFTMAX_MAX_K = 64, NLP_BLOCK_MAX_R = 8 };
 
 struct NlpBlkDev {
     int ke, N, d;                         // kind + 16 * (exponent + 32) as NlpDev::fke; points; columns
@@ -65,6 +69,11 @@ struct NlpBlkDev {
     // carry variables; col [Kf d] and hs over the flat index k d + j; S [Kf][N] at os; wz: P [Kf][N]
     int K, Kf;
     const int *y;                         // [N] label of a point, 0 .. K - 1
+    // a block with several outputs (sqphip_nlp_add_row_block; nlp_rowblock_dev.hpp): R != 0, K = 0.  W [R][N] at ow; wz: kappa [N] |
+    // kappa' [N] | z2 [N]
+    int R;
+    int row[NLP_BLOCK_MAX_R];             // [R] target of an output: 0 the objective, i row i (1-based)
+    const int *js;                        // [R][d] Jacobian COO slot of (row[r], col[j]); unread for an output on row 0
 };
 
 struct NlpDev {
@@ -89,7 +98,7 @@ struct NlpDev {
     const double *fpar;                   // [nfac] real exponent of a POWR factor (loaded for that kind only)
     int data;                             // sqphip_nlp_attach_data: b, a, p are the instance's, in its block of DV::nlv at ...
     int ob, oa, op;                       // ... ob [nfac], oa [nargs], op [nfac] (op: with a POWR factor only); fab, acoef, aw, fpar unread
-    int ws;                               // doubles of workspace per instance (DV::nlw): 3 nfac, with blocks + TPB / 64 wave sums + 3 TPB kappa values + 2 sum N_k
+    int ws;                               // doubles of workspace per instance (DV::nlw): 3 nfac, with blocks + TPB / 64 wave sums + 3 TPB kappa values + a block's own (2 N, Kf N, 3 N)
     int nblk;                             // dense data blocks of the objective (sqphip_nlp_add_block, nlp_block_dev.hpp); uniform over the launch
     NlpBlkDev blk[NLP_MAX_BLOCKS];
 };
@@ -191,6 +200,7 @@ static __device__ __forceinline__ void nlp_factor(int ke, double a, double u, do
 
 }  // namespace sqphip
 #include "nlp_block_dev.hpp"
+#include "nlp_rowblock_dev.hpp"
 #include "nlp_softmax_dev.hpp"
 namespace sqphip {
 
@@ -289,7 +299,7 @@ static __device__ __forceinline__ void nlp_eval(const DV &d, int inst, const dou
         }
     }
     // dense data blocks of either sort, in block order behind a barrier each: one out-of-line call (nlp_softmax_dev.hpp)
-    if (q.nblk != 0) nlp_blocks_eval(q.blk, q.nblk, val, w, w + 3 * nf, x, sigma, f_out, grad, hv);
+    if (q.nblk != 0) nlp_blocks_eval(q.blk, q.nblk, val, w, w + 3 * nf, x, sigma, lam, f_out, grad, gv, jv, hv);
 }
 
 }  // namespace sqphip

@@ -6,7 +6,8 @@
 //     gradient  g_q    = sum_i W_i (p_ik - [y_i = k]) A_ij
 //     Hessian   H_qq'  = sum_i W_i p_ik ([k = l] - p_il) A_ij A_ij'           (q' = l d + j')
 // nlp_blocks_eval (below) is the one call site for blocks of the kernels that inline nlp_eval: it walks the blocks in block
-// order behind a barrier each and hands a softmax block (NlpBlkDev::K != 0) to nlp_softmax_eval, any other to nlp_block_eval.
+// order behind a barrier each and hands a softmax block (NlpBlkDev::K != 0) to nlp_softmax_eval, a block with several outputs
+// (NlpBlkDev::R != 0) to nlp_rowblock_eval (nlp_rowblock_dev.hpp), any other to nlp_block_eval.
 // One call of nlp_softmax_eval, by every thread of the workgroup:
 //   1. points: thread i % TPB computes u_ik as the scalar blocks do (u = 0, u = fma(At[j][i], x_{col[k][j]}, u) for j rising,
 //      u += S[k][i]) for k = 0 .. Kf - 1 and the maximum m of the logits (the pinned class enters with 0, last); then, with
@@ -169,13 +170,16 @@ static __device__ __noinline__ void nlp_softmax_eval(const NlpBlkDev *bp_, const
 // f, grad and hv entries that this block adds to from other threads.  Out of line, pointers and scalars only: the kernels that
 // inline nlp_eval carry one call for all blocks of either sort.
 static __device__ __noinline__ void nlp_blocks_eval(const NlpBlkDev *blk_, int nblk_, const double *val_, double *wsp_, double *part_,
-                                                    const double *x_, double sigma_, double *f_out_, double *grad_, double *hv_)
+                                                    const double *x_, double sigma_, const double *lam_, double *f_out_, double *grad_,
+                                                    double *gv_, double *jv_, double *hv_)
 {
     // the arguments are the same in every lane: in scalar registers they cross the calls below without a frame of saved
     // vector registers (80 B per lane otherwise, which every kernel that inlines nlp_eval would carry)
     const NlpBlkDev *blk = nlp_uniform(blk_);
     const double *val = nlp_uniform(val_), *x = nlp_uniform(x_);
     double *wsp = nlp_uniform(wsp_), *part = nlp_uniform(part_), *f_out = nlp_uniform(f_out_), *grad = nlp_uniform(grad_), *hv = nlp_uniform(hv_);
+    const double *lam = nlp_uniform(lam_);
+    double *gv = nlp_uniform(gv_), *jv = nlp_uniform(jv_);      // (read and written by a block with several outputs only)
     const int nblk = __builtin_amdgcn_readfirstlane(nblk_);
     const unsigned long sb = (unsigned long)__double_as_longlong(sigma_);
     const double sigma = __longlong_as_double((long long)(((unsigned long)(unsigned)__builtin_amdgcn_readfirstlane((unsigned)(sb >> 32)) << 32) |
@@ -184,6 +188,7 @@ static __device__ __noinline__ void nlp_blocks_eval(const NlpBlkDev *blk_, int n
     for (int k = 0; k < nblk; ++k) {
         __syncthreads();
         if (__builtin_amdgcn_readfirstlane(blk[k].K) != 0) nlp_softmax_eval(blk + k, val, wsp, part, x, sigma, f_out, grad, hv);      // uniform over the launch
+        else if (__builtin_amdgcn_readfirstlane(blk[k].R) != 0) nlp_rowblock_eval(blk + k, val, wsp, part, x, sigma, lam, f_out, grad, gv, jv, hv);
         else nlp_block_eval(blk + k, val, wsp, part, x, sigma, f_out, grad, hv);
     }
 }

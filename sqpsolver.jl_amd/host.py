@@ -548,8 +548,20 @@ class Context:
     def nlp_add_block(self, b) -> int:
         """One dense data block of the objective (sqphip_nlp_add_block; b: nlp_terms.NlpBlock); before the first sqp_reset,
         sqp_run or nlp_stream_begin.  Returns its number.  An nlp_terms.NlpSoftmaxBlock goes through
-        sqphip_nlp_add_softmax_block."""
-        from .nlp_terms import NlpSoftmaxBlock
+        sqphip_nlp_add_softmax_block, an nlp_terms.NlpRowBlock (several outputs, constraint rows) through
+        sqphip_nlp_add_row_block."""
+        from .nlp_terms import NlpRowBlock, NlpSoftmaxBlock
+        if isinstance(b, NlpRowBlock):
+            if not hasattr(self.L, "sqphip_nlp_add_row_block"):
+                raise SqpHipError("libsqphip.so lacks sqphip_nlp_add_row_block: rebuild it")
+            A = _f(np.atleast_2d(b.A))
+            rows = np.ascontiguousarray(b.rows, dtype=np.int64)
+            out = C.c_int32(-1)
+            self._ck(self.L.sqphip_nlp_add_row_block(self.h, int(b.kind), int(b.exp), float(b.par), A.shape[0], A.shape[1],
+                                                     _l(np.ascontiguousarray(b.cols, dtype=np.int64)), _d(A), len(rows), _l(rows),
+                                                     _d(None if b.shift is None else _f(b.shift)),
+                                                     _d(None if b.weight is None else _f(b.weight).ravel()), C.byref(out)))
+            return out.value
         if isinstance(b, NlpSoftmaxBlock):
             if not hasattr(self.L, "sqphip_nlp_add_softmax_block"):
                 raise SqpHipError("libsqphip.so lacks sqphip_nlp_add_softmax_block: rebuild it")
@@ -574,7 +586,8 @@ class Context:
     @staticmethod
     def _nlp_block_data(who, p, values):
         """[(block, weight or None, shift or None)] of p's blocks and of the keywords weight / shift, which override: an array
-        for block 0, or a list or dict of arrays by block (None: keep).  The keywords leave `values`."""
+        for block 0, or a list or dict of arrays by block (None: keep).  The keywords leave `values`.  The weights of a block
+        with R outputs are [R, N] and travel flattened."""
         per = {}
         for k, b in enumerate(getattr(p, "blocks", None) or []):
             per[k] = [b.weight, b.shift]
@@ -585,24 +598,25 @@ class Context:
             if isinstance(v, dict):
                 items = v.items()
             elif isinstance(v, (list, tuple)) and (len(v) == 0 or v[0] is None or np.ndim(v[0]) > 0):
-                items = enumerate(v)
+                items = enumerate(v)              # (a [R, N] array is an ndarray, not a list: it is block 0's)
             else:
                 items = [(0, v)]
             for k, a in items:
                 if a is not None:
                     per.setdefault(int(k), [None, None])[pos] = a
-        return [(k, None if w is None else _f(np.atleast_1d(w)), None if s is None else _f(np.atleast_1d(s)))
+        return [(k, None if w is None else _f(np.atleast_1d(w)).ravel(), None if s is None else _f(np.atleast_1d(s)).ravel())
                 for k, (w, s) in sorted(per.items()) if w is not None or s is not None]
 
     def nlp_set_instance_block(self, inst, blk, weight=None, shift=None):
-        """weight / shift of block blk of one instance (sqphip_nlp_set_instance_block); None: keep."""
-        self._ck(self.L.sqphip_nlp_set_instance_block(self.h, int(inst), int(blk), _d(None if weight is None else _f(weight)),
-                                                      _d(None if shift is None else _f(shift))))
+        """weight / shift of block blk of one instance (sqphip_nlp_set_instance_block); None: keep.  A block with R outputs
+        takes [R, N] weights."""
+        self._ck(self.L.sqphip_nlp_set_instance_block(self.h, int(inst), int(blk), _d(None if weight is None else _f(weight).ravel()),
+                                                      _d(None if shift is None else _f(shift).ravel())))
 
     def nlp_stream_set_block(self, scen, blk, weight=None, shift=None):
         """weight / shift of block blk of one scenario of the queue (sqphip_nlp_stream_set_block), after nlp_stream_set."""
-        self._ck(self.L.sqphip_nlp_stream_set_block(self.h, int(scen), int(blk), _d(None if weight is None else _f(weight)),
-                                                    _d(None if shift is None else _f(shift))))
+        self._ck(self.L.sqphip_nlp_stream_set_block(self.h, int(scen), int(blk), _d(None if weight is None else _f(weight).ravel()),
+                                                    _d(None if shift is None else _f(shift).ravel())))
 
     def nlp_attach(self, p, general=None, instance_data=False):
         """Structure of the batch and the values every instance starts with; p: nlp_terms.NlpTerms.  A p with argument arrays

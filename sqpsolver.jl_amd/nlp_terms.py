@@ -39,7 +39,12 @@ plain affine factors.  Twice inside one factor stays an error.  SQRT and POWR ne
                          columns and the kind are shared by the batch, the weights and shifts belong to the instance
     NlpSoftmaxBlock      a multinomial (softmax) data block, sum_i w_i [log sum_k exp(u_ik) - u_{i, y_i}] with
                          u_ik = A_i'x_cols[k] + shift_ki (sqphip_nlp_add_softmax_block); it sits in NlpTerms.blocks beside NlpBlock
+    NlpRowBlock          a dense data block with several outputs: one A, R <= 8 weight vectors with a target row each (row 0:
+                         the objective), sum_i w_ri kappa(A_i'x_cols + b_i) added to row r (sqphip_nlp_add_row_block)
     block_eval           value, gradient and dense Hessian of the blocks of a problem in numpy
+    row_block_eval       ... of its blocks with several outputs: the rows' values and Jacobian rows too, the Hessian of the
+                         Lagrangian with sigma and lam
+    neyman_pearson_model, rate_constrained_logistic_model     constraints on the data the objective is fitted to, as row blocks
     multinomial_block_model  ridge-regularised K-class logistic regression as one softmax block plus terms
     logistic_block_model, poisson_block_model, least_squares_block_model     data fits of any size as one block plus terms
     fold_weights         the k training folds of N points as 0 / 1 weight vectors (logistic_fold_indices)
@@ -60,6 +65,7 @@ MAX_ARGS = 8
 MAX_BLOCKS = 4
 MAX_BLOCK_COLS = 128
 MAX_SOFTMAX_CLASSES = 64
+MAX_BLOCK_ROWS = 8
 
 
 @dataclasses.dataclass
@@ -123,6 +129,36 @@ class NlpSoftmaxBlock:
 
 
 @dataclasses.dataclass
+class NlpRowBlock:
+    """Output r adds sum_{i < N} weight[r, i] kappa(sum_j A[i, j] x_{cols[j]} + shift_i) to row rows[r] (0: the objective, i: row
+    i, a nonlinear one): one design matrix, R = len(rows) <= 8 distinct target rows.  kind, cols, A, exp, par as in NlpBlock;
+    shift [N] None: zeros, weight [R, N] None: ones."""
+    kind: int
+    cols: np.ndarray
+    A: np.ndarray
+    rows: np.ndarray
+    shift: np.ndarray | None = None
+    weight: np.ndarray | None = None
+    exp: int = 1
+    par: float = 0.0
+
+    def __post_init__(self):
+        self.cols = _i64(np.atleast_1d(self.cols))
+        self.A = _f64(np.atleast_2d(self.A))
+        self.rows = _i64(np.atleast_1d(self.rows))
+        N, R = self.A.shape[0], len(self.rows)
+        if not 1 <= R <= MAX_BLOCK_ROWS:
+            raise ValueError(f"R = {R} outputs (1..{MAX_BLOCK_ROWS})")
+        if len(np.unique(self.rows)) != R:
+            raise ValueError("a row is the target of two outputs of the block")
+        self.shift = np.zeros(N) if self.shift is None else _f64(self.shift)
+        self.weight = np.ones((R, N)) if self.weight is None else _f64(self.weight)
+        if self.weight.size != R * N:
+            raise ValueError(f"weight holds {self.weight.size} values, not R N = {R} x {N}")
+        self.weight = self.weight.reshape(R, N)
+
+
+@dataclasses.dataclass
 class NlpTerms:
     n: int
     m: int
@@ -148,7 +184,7 @@ class NlpTerms:
     fpar: np.ndarray | None = None     # [nfac] real exponent of a POWR factor (0 elsewhere); None: no POWR factor
     general: bool = False              # written for sqphip_nlp_attach_general (make_nlp_terms: needs_general); False: a model
                                        # of the older calls, which keep refusing what they refuse
-    blocks: list = dataclasses.field(default_factory=list)     # NlpBlock, NlpSoftmaxBlock: dense data blocks of the objective (at most 4)
+    blocks: list = dataclasses.field(default_factory=list)     # NlpBlock, NlpSoftmaxBlock, NlpRowBlock: dense data blocks (at most 4)
 
     @property
     def affine(self) -> bool:
@@ -221,8 +257,13 @@ def make_nlp_terms(n, m, num_linear, terms, g0=None, f0=0.0, xL=None, xU=None, g
     if len(p.blocks) > MAX_BLOCKS:
         raise ValueError(f"{len(p.blocks)} blocks (at most {MAX_BLOCKS})")
     for k, b in enumerate(p.blocks):
-        if isinstance(b, NlpSoftmaxBlock) and (b.cols.min() < 1 or b.cols.max() > n):
+        if isinstance(b, (NlpSoftmaxBlock, NlpRowBlock)) and (b.cols.min() < 1 or b.cols.max() > n):
             raise ValueError(f"block {k + 1}: a column outside 1..{n}")
+        if isinstance(b, NlpRowBlock):
+            if b.rows.min() < 0 or b.rows.max() > m:
+                raise ValueError(f"block {k + 1}: a row outside 0..{m}")
+            if np.any((b.rows >= 1) & (b.rows <= num_linear)):
+                raise ValueError(f"block {k + 1}: a row among the num_linear = {num_linear} linear rows")
     return p
 
 
@@ -234,14 +275,18 @@ def nlp_terms_layout(p: NlpTerms) -> NlpTermsLayout:
     """Jacobian COO: (i, v) of every argument of every factor of a term of row i, row-major; Hessian COO: the lower entry
     (v, w) of every two distinct variables of one term -- except two arguments of one plain linear factor (POW, e = 1) --
     and (v, v) of every argument of a factor that is not plain linear, column-major; every pair of columns of a block,
-    the diagonal included.  Each once."""
+    the diagonal included; (i, v) of every column v of a block with an output on row i >= 1.  Each once."""
     n = p.n
     aptr, avar, _ = nlp_terms_args(p)
     nargs = np.diff(aptr)
     fa = np.repeat(np.arange(len(p.fkind), dtype=np.int64), nargs)      # factor of an argument
     rows = p.trow[_term_of_factor(p)][fa]
     inrow = rows > 0
-    jkey = np.unique((rows[inrow] - 1) * n + (avar[inrow] - 1))
+    jk = [(rows[inrow] - 1) * n + (avar[inrow] - 1)]
+    for b in getattr(p, "blocks", []):
+        if isinstance(b, NlpRowBlock):
+            jk += [(i - 1) * n + (b.cols - 1) for i in b.rows.tolist() if i >= 1]
+    jkey = np.unique(np.concatenate(jk))
     hk = []
     curved = ~((p.fkind == POW) & (p.fexp == 1))
     ca = curved[fa]
@@ -587,10 +632,12 @@ def _softmax_eval(b: NlpSoftmaxBlock, x):
 
 def block_eval(p: NlpTerms, x, blocks=None):
     """(f, grad [n], H [n, n]) of the blocks of p at x: sum_i w_i kappa(u_i), A'(w kappa'), A' diag(w kappa'') A scattered to
-    the blocks' columns."""
+    the blocks' columns.  Blocks with several outputs (NlpRowBlock) are row_block_eval's, not counted here."""
     x = _f64(x)
     f, g, H = 0.0, np.zeros(p.n), np.zeros((p.n, p.n))
     for b in (p.blocks if blocks is None else blocks):
+        if isinstance(b, NlpRowBlock):
+            continue
         if isinstance(b, NlpSoftmaxBlock):
             fb, gb, Hb = _softmax_eval(b, x)
             c = b.cols.ravel() - 1
@@ -604,6 +651,31 @@ def block_eval(p: NlpTerms, x, blocks=None):
         np.add.at(g, c, b.A.T @ (b.weight * k1))
         H[np.ix_(c, c)] += b.A.T @ ((b.weight * k2)[:, None] * b.A)
     return f, g, H
+
+
+def row_block_eval(p: NlpTerms, x, sigma=1.0, lam=None, blocks=None):
+    """(f, grad [n], g [m], J [m, n], H [n, n]) of the blocks with several outputs of p at x: what they add to the objective,
+    its gradient, the rows' values and Jacobian rows, and to the Hessian of the Lagrangian,
+    A' diag(kappa'' (sum_r mu_r w_r)) A with mu_r = sigma for row 0 and lam[i - 1] for row i (lam None: zeros)."""
+    x = _f64(x)
+    lam = np.zeros(p.m) if lam is None else _f64(lam)
+    f, g, gv, J, H = 0.0, np.zeros(p.n), np.zeros(p.m), np.zeros((p.m, p.n)), np.zeros((p.n, p.n))
+    for b in (p.blocks if blocks is None else blocks):
+        if not isinstance(b, NlpRowBlock):
+            continue
+        c = b.cols - 1
+        k0, k1, k2 = _kappa3(b.kind, b.exp, b.par, b.A @ x[c] + b.shift)
+        e = np.zeros(len(k0))
+        for r, i in enumerate(b.rows.tolist()):
+            if i == 0:
+                f += float(b.weight[r] @ k0)
+                np.add.at(g, c, b.A.T @ (b.weight[r] * k1))
+            else:
+                gv[i - 1] += float(b.weight[r] @ k0)
+                np.add.at(J[i - 1], c, b.A.T @ (b.weight[r] * k1))
+            e += (float(sigma) if i == 0 else lam[i - 1]) * b.weight[r]
+        H[np.ix_(c, c)] += b.A.T @ ((e * k2)[:, None] * b.A)
+    return f, g, gv, J, H
 
 
 def fold_weights(N: int, k: int) -> np.ndarray:
@@ -640,6 +712,36 @@ def multinomial_block_model(X, y, K, reg, pinned=True, weight=None) -> NlpTerms:
     n = Kf * d
     blk = NlpSoftmaxBlock(np.arange(1, n + 1).reshape(Kf, d), X, y, K, pinned, None, weight)
     return make_nlp_terms(n, 0, 0, _ridge(n, reg), xL=np.full(n, -50.0), xU=np.full(n, 50.0), x0=np.zeros(n), blocks=[blk])
+
+
+def neyman_pearson_model(X, y, alpha, reg, weight=None) -> NlpTerms:
+    """Neyman-Pearson classification, labels y in {0, 1}: the logistic loss on the positives under a level on the mean loss of
+    the negatives,
+        min  sum_{y_i = 1} w_i [softplus(X_i'b) - X_i'b] + reg / 2 |b|^2   s.t.  sum_{y_i = 0} w_i softplus(X_i'b) / sum_{y_i = 0} w_i <= alpha
+    as one SOFTPLUS block on X with rows = [0, 1] plus the linear and ridge terms.  weight None: ones; the folds or resamples
+    of one dataset differ in the two weight vectors and the coefficients of the linear terms.  -50 <= b <= 50, from b = 0."""
+    X, y = np.atleast_2d(_f64(X)), _f64(y)
+    N, n = X.shape
+    w = np.ones(N) if weight is None else _f64(weight)
+    w1, w0 = w * (y == 1), w * (y == 0)
+    blk = NlpRowBlock(SOFTPLUS, np.arange(1, n + 1), X, [0, 1], None, np.stack([w1, w0 / w0.sum()]))
+    terms = [(0, -float(w1 @ X[:, j]), [(j + 1, POW)]) for j in range(n)] + _ridge(n, reg)
+    return make_nlp_terms(n, 1, 0, terms, xL=np.full(n, -50.0), xU=np.full(n, 50.0), gL=[-np.inf], gU=[float(alpha)], x0=np.zeros(n),
+                          blocks=[blk])
+
+
+def rate_constrained_logistic_model(X, y, group, reg, tol) -> NlpTerms:
+    """Logistic regression under a bound on the difference of the mean predicted rates of two groups (group in {0, 1}):
+    logistic_block_model's block in the objective, and one row
+        -tol <= mean_{group = 1} sigmoid(X_i'b) - mean_{group = 0} sigmoid(X_i'b) <= tol
+    as a SIGMOID block with one output on row 1 (tol = 0: an equality).  Not convex.  -50 <= b <= 50, from b = 0."""
+    X, y, gr = np.atleast_2d(_f64(X)), _f64(y), _f64(group)
+    N, n = X.shape
+    cols = np.arange(1, n + 1)
+    w = (gr == 1) / (gr == 1).sum() - (gr == 0) / (gr == 0).sum()
+    blocks = [NlpBlock(SOFTPLUS, cols, (1.0 - 2.0 * y)[:, None] * X), NlpRowBlock(SIGMOID, cols, X, [1], None, w[None, :])]
+    return make_nlp_terms(n, 1, 0, _ridge(n, reg), xL=np.full(n, -50.0), xU=np.full(n, 50.0), gL=[-float(tol)], gU=[float(tol)],
+                          x0=np.zeros(n), blocks=blocks)
 
 
 def poisson_block_model(X, counts, reg, weight=None) -> NlpTerms:

@@ -1,0 +1,329 @@
+"""Dense data blocks with several outputs in the batched device SQP loop (sqphip_nlp_add_row_block, csrc/nlp_rowblock_dev.hpp):
+the evaluator against the 50-digit reference and its forward error bound (tests/nlp_rowblock_ref.py) at the shape edges, a row
+block beside an objective block on overlapping columns, the Neyman-Pearson model against scipy and the oracle, four folds and
+levels in one batch, the sigmoid equality model, the scenario queue against the batch, slot independence and every refusal.
+tests/test_nlp_rowblock_cpu.py holds scipy's and the oracle's word for the solved cases."""
+import ctypes as C
+import dataclasses
+import itertools
+import os
+import sys
+
+import numpy as np
+import pytest
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+
+import sqpsolver_jl_amd as pkg                                        # noqa: E402
+from sqpsolver_jl_amd.nlp_terms import POW, POWR, SOFTPLUS, NlpRowBlock, make_nlp_terms, nlp_terms_layout   # noqa: E402
+from oracle import oracle as O                                        # noqa: E402
+from nlp_rowblock_ref import (EDGE_CASES, EDGE_LAM, NP_ALPHA, NP_OPTS, NP_REG, SQP_TIGHT, NlpRowBlockRef, OracleRowBlockTerms,   # noqa: E402
+                              check_outputs, edge_row_model, np_case, np_fold_models, np_scipy, overlap_model, rate_case, with_block)
+
+pytestmark = pytest.mark.gpu
+TOL = 1e-8
+EINVAL, ESTATE = -1, -4
+FULL = ("x", "g", "mult_g", "mult_x_L", "mult_x_U")
+_dp = C.POINTER(C.c_double)
+
+
+def rel(a, b):
+    return float(np.abs(np.asarray(a) - np.asarray(b)).max() / max(1.0, np.abs(np.asarray(b)).max()))
+
+
+def _decisions(tr):
+    return [(t["iter"], t["accepted"], t["fr"], t["sub_status"]) for t in tr]
+
+
+def _ipm_counts_close(ro, tr):
+    return all(abs(a["ipm_iters"] - t["ipm_iters"]) <= max(2, (0.5 if t["fr"] else 0.25) * a["ipm_iters"])
+               for a, t in zip(ro["trace"], tr))
+
+
+def _ctx(lay, batch, **kw):
+    return pkg.Context(lay.n, lay.m, lay.num_linear, lay.jrow, lay.jcol, lay.hrow, lay.hcol, lay.xL, lay.xU, lay.gL, lay.gU,
+                       pkg.default_options(**kw), batch=batch)
+
+
+def _lin(kkt_mode):
+    return dict(kkt_mode=2) if kkt_mode == 2 else dict(kkt_mode=1, kkt_tile_order=1)
+
+
+def _d(a):
+    return None if a is None else a.ctypes.data_as(_dp)
+
+
+def _fg_only(ctx, inst, x):
+    """the f / g-only call: gradient, Jacobian and Hessian pointers NULL"""
+    f = C.c_double(); g = np.zeros(ctx.m); xx = np.ascontiguousarray(x, dtype=np.float64)
+    ctx._ck(ctx.L.sqphip_acopf_eval(ctx.h, inst, _d(xx), 1.0, None, C.byref(f), None, _d(g), None, None))
+    return f.value, g
+
+
+def _same_result(ra, rb, where):
+    for k in FULL:
+        assert np.array_equal(ra[k], rb[k]), (where, k)
+    assert (ra["obj_val"], ra["status"], ra["iter"]) == (rb["obj_val"], rb["status"], rb["iter"]), where
+
+
+def _against_oracle(rg, tr, ro, where):
+    """status, iteration count and decisions equal; x and objective at 1e-8, multipliers at 1e-6 (the suite's tolerances)"""
+    print(where, "status", rg["status"], ro["status"], "iter", rg["iter"], ro["iter"], "x", rel(rg["x"], ro["x"]),
+          "obj", abs(rg["obj_val"] - ro["obj_val"]), "multipliers", [rel(rg[k], ro[k]) for k in FULL[2:]])
+    assert ro["status"] == 0
+    assert (rg["status"], rg["iter"]) == (ro["status"], ro["iter"]), where
+    assert _decisions(ro["trace"]) == _decisions(tr) and _ipm_counts_close(ro, tr), where
+    assert rel(rg["x"], ro["x"]) < TOL and abs(rg["obj_val"] - ro["obj_val"]) <= TOL * max(1.0, abs(ro["obj_val"])), where
+    assert all(rel(rg[k], ro[k]) <= 1e-6 for k in FULL[2:]), where
+
+
+# ---- 1. the evaluator at the shape edges
+@pytest.mark.parametrize("N,d,rows,kind,e", EDGE_CASES, ids=[f"N{N}-d{d}-R{len(r)}-k{k}e{e}" for N, d, r, k, e in EDGE_CASES])
+def test_evaluator_at_the_shape_edges(N, d, rows, kind, e):
+    p, lay, inst = edge_row_model(N, d, rows, kind, e)
+    ctx = _ctx(lay, 3)
+    ctx.nlp_attach(p)
+    for b, (w, s) in enumerate(inst):
+        ctx.nlp_set_instance(b, p, weight=w, shift=s)
+    x = np.random.default_rng(N + d).uniform(0.6, 1.4, p.n)
+    gs = []
+    for b, (w, s) in enumerate(inst):
+        sigma = 0.0 if b == 2 else 0.7
+        ev = ctx.acopf_eval(b, x, sigma, EDGE_LAM)
+        val, bnd = NlpRowBlockRef(with_block(p, 0, w, s)).want(x, sigma, EDGE_LAM, lay)
+        check_outputs(ev, val, bnd, f"(N, d, rows, kind, e) = {(N, d, rows, kind, e)} instance {b} sigma {sigma}")
+        assert np.all(ev["hval"][-2:] == 0.0) and np.all(ev["jval"][-2:] == 0.0)     # the copies of a slot: the first copy owns the entry
+        f, g = _fg_only(ctx, b, x)
+        assert f == ev["f"] and np.array_equal(g, ev["g"])
+        gs.append(tuple(ev["g"]))
+    assert len(set(gs)) == 3                                          # every slot reads its own weights and shifts
+    ctx.close()
+
+
+# ---- 2. an objective block and a row block on overlapping columns
+def test_objective_block_and_row_block_on_overlapping_columns_share_slots_and_gradient_entries():
+    p, lay = overlap_model()
+    rng = np.random.default_rng(2)
+    w1, s0 = rng.uniform(0.0, 1.0, (2, 22)), 0.1 * rng.standard_normal(37)
+    ctx = _ctx(lay, 2)
+    ctx.nlp_attach(p)
+    ctx.nlp_set_instance(1, p, weight={1: w1}, shift={0: s0})
+    x = rng.uniform(-1.0, 1.0, p.n); lam = np.array([0.3, -0.6])
+    for b, q in enumerate((p, with_block(with_block(p, 1, weight=w1), 0, shift=s0))):
+        ev = ctx.acopf_eval(b, x, 1.3, lam)
+        val, bnd = NlpRowBlockRef(q).want(x, 1.3, lam, lay)
+        check_outputs(ev, val, bnd, f"two blocks, instance {b}")
+    # each block alone visibly moves the shared gradient entries and Hessian slots: both contribute
+    R = NlpRowBlockRef(q)
+    shared = [2, 4, 6]
+    hs = [s for s, (r, c) in enumerate(zip(lay.hrow - 1, lay.hcol - 1)) if r in shared and c in shared]
+    for alone in (q.blocks[:1], q.blocks[1:]):
+        only = R.want(x, 1.3, lam, lay, blocks=alone)[0]
+        assert np.abs(only["grad"][shared] - ev["grad"][shared]).min() > 1e-3
+        assert np.abs(only["hval"][hs] - ev["hval"][hs]).min() > 1e-3
+    ctx.close()
+
+
+# ---- 3. Neyman-Pearson, solved
+def test_neyman_pearson_reaches_the_scipy_optimum_and_matches_the_oracle():
+    X, y, p = np_case()
+    lay = nlp_terms_layout(p)
+    want = np_scipy(X, y, NP_ALPHA, NP_REG)[1]
+    ctx = _ctx(lay, 1, kkt_mode=2, **NP_OPTS)
+    ctx.nlp_attach(p); ctx.nlp_set_instance(0, p)
+    ctx.sqp_reset(); ctx.sqp_run(0)
+    rg, tr = ctx.sqp_get(0), ctx.sqp_trace(0)
+    ctx.close()
+    print("status", rg["status"], "iter", rg["iter"], "x", np.abs(rg["x"] - want).max(), "multiplier", rg["mult_g"])
+    assert rg["status"] == 0 and np.abs(rg["x"] - want).max() <= 1e-6
+    try:
+        ro = O.sqp_solve(OracleRowBlockTerms(p, lay), O.default_options(kkt_mode=2, **NP_OPTS))
+    finally:
+        O.set_kkt_order(None)
+    _against_oracle(rg, tr, ro, "neyman-pearson")
+    assert abs(rg["mult_g"][0]) > 1.0 and abs(rg["g"][0] - NP_ALPHA) <= 1e-8        # the row is active
+
+
+# ---- 4. four folds and four levels in one batch
+@pytest.mark.parametrize("kkt_mode", [1, 2])
+def test_four_folds_and_levels_in_one_batch(kkt_mode):
+    ps = np_fold_models()
+    lay = nlp_terms_layout(ps[0])
+    ctx = _ctx(lay, 4, **_lin(kkt_mode), **NP_OPTS)
+    ctx.nlp_attach(ps[0])
+    for b in range(4):
+        ctx.nlp_set_instance(b, ps[b])                                # weights [2, N], linear coefficients and the level (set_bounds)
+    ctx.sqp_reset(); ctx.sqp_run(0)
+    out = [(ctx.sqp_get(b), ctx.sqp_trace(b)) for b in range(4)]
+    ctx.close()
+    try:
+        for b in range(4):
+            ro = O.sqp_solve(OracleRowBlockTerms(ps[b], nlp_terms_layout(ps[b])), O.default_options(**_lin(kkt_mode), **NP_OPTS))
+            _against_oracle(out[b][0], out[b][1], ro, ("fold", b))
+            assert abs(out[b][0]["g"][0] - ps[b].gU[0]) <= 1e-8 and out[b][0]["mult_g"][0] != 0.0
+    finally:
+        O.set_kkt_order(None)
+    assert min(np.abs(a[0]["x"] - b[0]["x"]).max() for a, b in itertools.combinations(out, 2)) > 1e-3
+
+
+# ---- 5. the sigmoid equality model (not convex)
+def test_rate_equality_model_matches_the_oracle():
+    X, y, group, p = rate_case()
+    lay = nlp_terms_layout(p)
+    ctx = _ctx(lay, 1, kkt_mode=2, **SQP_TIGHT)
+    ctx.nlp_attach(p); ctx.nlp_set_instance(0, p)
+    ctx.sqp_reset(); ctx.sqp_run(0)
+    rg, tr = ctx.sqp_get(0), ctx.sqp_trace(0)
+    ctx.close()
+    try:
+        ro = O.sqp_solve(OracleRowBlockTerms(p, lay), O.default_options(kkt_mode=2, **SQP_TIGHT))
+    finally:
+        O.set_kkt_order(None)
+    _against_oracle(rg, tr, ro, "rate equality")
+    s = 1.0 / (1.0 + np.exp(-(X @ rg["x"])))
+    assert abs(s[group == 1].mean() - s[group == 0].mean()) <= 1e-8 and abs(rg["mult_g"][0]) > 1.0
+
+
+# ---- 6. the scenario queue: six scenarios on two slots
+def test_queue_of_six_scenarios_equals_the_batch():
+    ps = np_fold_models(extra=2)
+    p0 = ps[5]                                                        # unit weights: what the add call sets
+    lay = nlp_terms_layout(p0)
+    ctx = _ctx(lay, 2, kkt_mode=2, **NP_OPTS)
+    ctx.nlp_attach(p0)
+    ctx.nlp_stream_begin(6, keep_multipliers=True)
+    for s in range(6):
+        ctx.nlp_stream_set(s, tcoef=ps[s].tcoef, gU=ps[s].gU, x0=p0.x0)
+        ctx.nlp_stream_set_block(s, 0, weight=ps[s].blocks[0].weight)
+    ctx.nlp_stream_set(3, gU=ps[3].gU, x0=p0.x0)                      # alone: the add call's weights and coefficients are back
+    ctx.stream_run()
+    got = [ctx.stream_get_full(s) for s in range(6)]
+    ctx.close()
+    restored = with_block(ps[5], 0)
+    restored.gU = ps[3].gU.copy()
+    assert np.abs(got[3]["x"] - got[5]["x"]).max() > 1e-3             # (the level differs: scenario 3 is not scenario 5)
+    ps[3] = restored
+    ref = _ctx(lay, 2, kkt_mode=2, **NP_OPTS)
+    ref.nlp_attach(p0)
+    for s0 in (0, 2, 4):
+        for b in range(2):
+            ref.nlp_set_instance(b, ps[s0 + b])
+        ref.sqp_reset(); ref.sqp_run(0)
+        for b in range(2):
+            s = s0 + b
+            r = ref.sqp_get(b)
+            print("scenario", s, "status", got[s]["status"], "iter", got[s]["iter"])
+            _same_result(got[s], r, ("scenario", s))
+            assert got[s]["status"] == 0, s
+    ref.close()
+
+
+# ---- 7. slot independence
+def test_an_instance_does_not_depend_on_its_slot_its_neighbours_the_run_or_the_groups():
+    ps = np_fold_models()
+    lay = nlp_terms_layout(ps[0])
+    order = (0, 1, 2, 0)                                              # slots 0 and 3: the same instance, other neighbours
+
+    def run(ctx):
+        ctx.sqp_reset(); ctx.sqp_run(0)
+        return [(ctx.sqp_get(b), ctx.sqp_trace(b)) for b in range(4)]
+
+    def make():
+        ctx = _ctx(lay, 4, kkt_mode=2, **NP_OPTS)
+        ctx.nlp_attach(ps[0])
+        for b, f in enumerate(order):
+            ctx.nlp_set_instance(b, ps[f])
+        return ctx
+
+    ctx = make()
+    runs = [run(ctx), run(ctx)]
+    assert ctx.counters()["n_groups"] == 1
+    ctx.close()
+    assert all(r[0]["status"] == 0 for r in runs[0])
+    _same_result(runs[0][0][0], runs[0][3][0], "slots 0 and 3")
+    assert runs[0][0][1] == runs[0][3][1]
+    assert not np.array_equal(runs[0][0][0]["x"], runs[0][1][0]["x"])
+    for b in range(4):
+        _same_result(runs[0][b][0], runs[1][b][0], ("second run", b))
+        assert runs[0][b][1] == runs[1][b][1]
+    os.environ["SQPHIP_GROUPS"] = "2"
+    try:
+        ctx = make()
+        grouped = run(ctx)
+        assert ctx.counters()["n_groups"] == 2
+        ctx.close()
+    finally:
+        del os.environ["SQPHIP_GROUPS"]
+    for b in range(4):
+        _same_result(runs[0][b][0], grouped[b][0], ("two groups", b))
+        assert runs[0][b][1] == grouped[b][1]
+
+
+# ---- 8. refusals
+def _expect(rc, code, words, ctx):
+    msg = ctx.L.sqphip_last_error(ctx.h).decode()
+    assert rc == code, (rc, msg)
+    assert all(w in msg for w in words), msg
+
+
+def test_refusals():
+    n, m = 6, 3                                                       # row 1 linear, rows 2 and 3 nonlinear; row 3 lacks (3, 5)
+    terms = [(0, 1.0, [(j + 1, POW, 2)]) for j in range(n)] + [(1, 1.0, [(1, POW)]), (2, 1.0, [(1, POW, 2)])]
+    terms += [(3, 1.0, [(j, POW, 2)]) for j in (2, 4)]
+    p = make_nlp_terms(n, m, 1, terms, xL=np.full(n, -1.0), xU=np.ones(n), gL=np.full(m, -9.0), gU=np.full(m, 9.0),
+                       blocks=[NlpRowBlock(SOFTPLUS, [2, 4, 5], np.ones((4, 3)), [0, 2])])
+    lay = nlp_terms_layout(p)
+    who = "sqphip_nlp_add_row_block"
+    A = np.ones((4, 3)); cols = np.array([2, 4, 5], dtype=np.int64)
+    lp = lambda a: a.ctypes.data_as(C.POINTER(C.c_int64))
+
+    def add(ctx, kind=9, e=1, par=0.0, N=4, d=3, c=cols, a=A, R=None, rows=(0, 2)):
+        r = None if rows is None else np.ascontiguousarray(rows, dtype=np.int64)
+        return ctx.L.sqphip_nlp_add_row_block(ctx.h, kind, e, par, N, d, lp(np.ascontiguousarray(c, dtype=np.int64)), _d(a),
+                                              (0 if r is None else len(r)) if R is None else R, None if r is None else lp(r), None, None, None)
+
+    ctx = _ctx(lay, 2)
+    _expect(add(ctx), EINVAL, [who, "no factorable NLP"], ctx)       # before any attach
+    ctx.nlp_attach(dataclasses.replace(p, blocks=[]))
+    big = np.ones((1, 129))
+    # everything sqphip_nlp_add_block refuses
+    _expect(add(ctx, d=0), EINVAL, [who, "block 1", "d = 0"], ctx)
+    _expect(add(ctx, d=129, c=np.arange(1, 130), a=big), EINVAL, [who, "block 1", "d = 129"], ctx)
+    _expect(add(ctx, N=0), EINVAL, [who, "block 1", "N = 0"], ctx)
+    _expect(add(ctx, N=2 ** 31 // 3 + 1), EINVAL, [who, "block 1", "too large"], ctx)
+    _expect(add(ctx, c=[2, 7, 5]), EINVAL, [who, "block 1", "column 2", "variable 7", "out of range"], ctx)
+    _expect(add(ctx, c=[2, 4, 2]), EINVAL, [who, "block 1", "column 3", "variable 2", "twice"], ctx)
+    _expect(add(ctx, kind=11), EINVAL, [who, "block 1", "kind 11"], ctx)
+    _expect(add(ctx, kind=0, e=1), EINVAL, [who, "block 1", "plain linear"], ctx)
+    _expect(add(ctx, kind=0, e=0), EINVAL, [who, "block 1", "exponent 0"], ctx)
+    _expect(add(ctx, kind=0, e=33), EINVAL, [who, "block 1", "exponent 33"], ctx)
+    _expect(add(ctx, kind=POWR, par=0.0), EINVAL, [who, "block 1", "real exponent"], ctx)
+    _expect(add(ctx, kind=POWR, par=float("inf")), EINVAL, [who, "block 1", "real exponent"], ctx)
+    _expect(add(ctx, c=[2, 4, 6]), EINVAL, [who, "block 1", "entry (3, 1)", "Hessian entry (6, 2)"], ctx)
+    _expect(ctx.L.sqphip_nlp_add_row_block(ctx.h, 9, 1, 0.0, 4, 3, None, _d(A), 1, lp(np.zeros(1, np.int64)), None, None, None),
+            EINVAL, [who, "block 1", "null cols or A"], ctx)
+    # the rows
+    _expect(add(ctx, R=0), EINVAL, [who, "block 1", "R = 0"], ctx)
+    _expect(add(ctx, R=9, rows=np.arange(9)), EINVAL, [who, "block 1", "R = 9"], ctx)
+    _expect(add(ctx, R=2, rows=None), EINVAL, [who, "block 1", "null rows"], ctx)
+    _expect(add(ctx, rows=(0, 4)), EINVAL, [who, "block 1", "output 2", "row 4", "outside 0..3"], ctx)
+    _expect(add(ctx, rows=(-1,)), EINVAL, [who, "block 1", "output 1", "row -1", "outside 0..3"], ctx)
+    _expect(add(ctx, rows=(2, 0, 2)), EINVAL, [who, "block 1", "output 3", "row 2", "twice", "outputs 1 and 3"], ctx)
+    _expect(add(ctx, rows=(0, 1)), EINVAL, [who, "block 1", "output 2", "row 1", "num_linear = 1"], ctx)
+    _expect(add(ctx, rows=(2, 3)), EINVAL, [who, "block 1", "output 2", "row 3", "column 3", "Jacobian entry (3, 5)"], ctx)
+    for k in range(4):
+        assert add(ctx) == 0
+    _expect(add(ctx), EINVAL, [who, "block 5", "at most 4"], ctx)
+    w = np.ones(8)
+    assert ctx.L.sqphip_nlp_set_instance_block(ctx.h, 1, 3, _d(w), None) == 0
+    ctx.nlp_stream_begin(3)
+    assert ctx.L.sqphip_nlp_stream_set_block(ctx.h, 2, 0, _d(w), None) == 0
+    _expect(add(ctx), ESTATE, [who, "sqphip_nlp_stream_begin"], ctx)  # the queue has seen the layout
+    ctx.close()
+    # after sqphip_sqp_reset
+    ctx = _ctx(lay, 1)
+    ctx.nlp_attach(p)
+    ctx.sqp_reset()
+    _expect(add(ctx), ESTATE, [who, "sqphip_sqp_reset"], ctx)
+    ctx.close()
