@@ -70,6 +70,31 @@ int sqphip_mf_values_blocks(int64_t n, int64_t m, int64_t nnzJ, const int64_t *j
                             const int32_t *rtype, double hsc, double dw, int32_t *blocks, int32_t cap_blocks,
                             int32_t *n_blocks, int32_t *item_ptr, int64_t cap_dest, int64_t *n_dest, int64_t *n_items,
                             double *vals_list, double *vals_block);
+/* Host-only (no GPU): what sqphip_create sets up for the dense path (kkt_mode = 1, or 0 where it selects it) of the structure
+ * under options.kkt_condense / kkt_tile_order, by the same functions (kkt_row_is_kept, kkt_order, kkt_pair_lists).  pos[nu]:
+ * unknown (variable, or n + index among the rows that stay in the matrix) -> position in the factorised matrix; info[6] = nu,
+ * Ts (independent leading tile columns), Tr (remainder tiles), Nf (positions in use), Fpad = 64 (Ts + Tr), and 1 when the
+ * coupling mask is handed to the kernels (Ts > 0, Tr > 0, SQPHIP_NO_TILE_MASK unset).  tmask[Tr][max(Ts, 1)], pair_ptr[Tr (Tr + 1)
+ * / 2 + 1], pair_k[*n_k]: the mask and the pair lists (all zero / empty where the kernels get none); each is written when
+ * its capacity suffices (cap_mask, cap_ptr, cap_k entries). */
+int sqphip_kkt_order_info(int64_t n, int64_t m, int64_t nnzJ, const int64_t *jrow, const int64_t *jcol, int64_t nnzH,
+                          const int64_t *hrow, const int64_t *hcol, const double *gL, const double *gU, int32_t condense,
+                          int32_t tile_order, int32_t *pos, int32_t *info, uint8_t *tmask, int32_t cap_mask, int32_t *pair_ptr,
+                          int32_t cap_ptr, int32_t *pair_k, int32_t cap_k, int32_t *n_k);
+/* Dense twin of sqphip_mf_batch_test, on a context that uses the dense solver (SQPHIP_ESTATE otherwise).  Inputs per instance,
+ * back to back as there; rhs[B][n + m]: a full-length right-hand side [g; b].  Every instance's xv, vv and dinv are preset to
+ * `sentinel`; the working vector of the solves is built twice from rhs -- by k_sp_load_xv (mode 0) and by load_solve_vector --
+ * and *xv_mismatch counts the entries whose bits differ between the two; then k_kkt_assemble, and what a sweep does on the dense
+ * path: ldlt_factor with the right-hand side fused in, the inertia test, the backward solve of the instances that passed.
+ * Outputs (any may be null): K_assembled[B][Fpad * Fpad] (column-major in factorised order, as the device holds it behind the
+ * assembly) and xv_loaded[B][Fpad]; sol / dinv[B][nu] in unknown order; dinv_pad[B][Fpad] as the device holds it; decision[B][4]
+ * = outcome (0 idle, 1 another shift needed, 2 passed, 3 given up), sel, n_factor, fac_attempt; dw_out[B].  Leaves every
+ * instance idle. */
+int sqphip_kkt_dense_test(sqphip_ctx *ctx, const int32_t *active, const double *Jval, const double *Hval, const double *Dd,
+                          const double *sigp, const double *hd, const int32_t *rtype, const double *hsc, const double *dw,
+                          const double *dw_last, const int32_t *fac_attempt, const double *rhs, double sentinel,
+                          double *K_assembled, double *xv_loaded, int32_t *xv_mismatch, double *sol, double *dinv,
+                          double *dinv_pad, int32_t *decision, double *dw_out);
 /* Launch census of the multifrontal path: launches enqueued per kernel instantiation (factor, solve, inertia test) since the
  * context was created.  counts[cap]; names (may be null): cap x 64 characters; *n_kernels = number of instantiations. */
 int sqphip_mf_census(const sqphip_ctx *ctx, int64_t *counts, char *names, int32_t cap, int32_t *n_kernels);

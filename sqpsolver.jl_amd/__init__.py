@@ -9,6 +9,6 @@ from . import qcqp  # noqa: F401
 from . import nlp_terms  # noqa: F401
 from . import _lib  # noqa: F401
 from . import host  # noqa: F401
-from .host import (Context, QpData, QpHip, default_options, SqpHipError, kkt_order,  # noqa: F401
+from .host import (Context, QpData, QpHip, default_options, SqpHipError, kkt_order, kkt_order_info,  # noqa: F401
                    kkt_symbolic, mf_host_solve, mf_host_top2_err, mf_host_spine_err, mf_plan_info, mf_front_launches, mf_factor_kernels,
                    mf_values_blocks)

@@ -748,6 +748,92 @@ extern "C" int sqphip_mf_values_test(sqphip_ctx *h, const int32_t *active, const
     });
 }
 
+// Dense twin of sqphip_mf_batch_test: every instance with active[b] != 0 gets its own values and interior-point state; the
+// working vector of the solves is built from the full-length right-hand side by both routines (k_sp_load_xv and
+// load_solve_vector: *xv_mismatch counts entries whose bits differ), the Newton matrix is assembled (k_kkt_assemble) and read
+// back, and the instance goes through what one sweep does on the dense path (ipm.hip, ipm_sweep): ldlt_factor with the
+// right-hand side fused in, k_inertia, the backward solve of the instances that passed.  xv, vv and dinv of every instance
+// are preset to `sentinel`: what an inactive instance must come back with.  Leaves every instance idle.
+extern "C" int sqphip_kkt_dense_test(sqphip_ctx *h, const int32_t *active, const double *Jval, const double *Hval,
+                                     const double *Dd, const double *sigp, const double *hd, const int32_t *rtype,
+                                     const double *hsc, const double *dw, const double *dw_last, const int32_t *fac_attempt,
+                                     const double *rhs, double sentinel, double *K_assembled, double *xv_loaded,
+                                     int32_t *xv_mismatch, double *sol, double *dinv, double *dinv_pad, int32_t *decision,
+                                     double *dw_out)
+{
+    if (!h || !active || !Jval || !Dd || !sigp || !hd || !rtype || !hsc || !dw || !dw_last || !fac_attempt || !rhs)
+        return SQPHIP_EINVAL;
+    if (h->c.d.sparse) { h->c.err = "sqphip_kkt_dense_test: the context uses the sparse solver"; return SQPHIP_ESTATE; }
+    return guarded(h, [&](Ctx &C) {
+        DV &d = C.d;
+        const int B = d.B, nu = d.condense ? d.n + d.mk : d.N;
+        const size_t BF = (size_t)B * d.Fpad;
+        for (int b = 0; b < B; ++b) {
+            const size_t on = (size_t)b * d.n, om = (size_t)b * d.m;
+            h2d(C, d.jcoo + (size_t)b * d.nnzj_coo, Jval + (size_t)b * d.nnzj_coo, d.nnzj_coo);
+            if (Hval) h2d(C, d.hcoo + (size_t)b * d.nnzh_coo, Hval + (size_t)b * d.nnzh_coo, d.nnzh_coo);
+            else SQPHIP_HIP_OK(hipMemsetAsync(d.hcoo + (size_t)b * d.nnzh_coo, 0, sizeof(double) * (size_t)d.nnzh_coo, C.stream));
+            h2d(C, d.Dd + om, Dd + om, d.m); h2d(C, d.sigp + on, sigp + on, d.n); h2d(C, d.hd + on, hd + on, d.n);
+            SQPHIP_HIP_OK(hipMemcpyAsync(d.rtype + om, rtype + om, sizeof(int) * (size_t)d.m, hipMemcpyHostToDevice, C.stream));
+            h2d(C, d.rhs + (size_t)b * d.Npad, rhs + (size_t)b * d.N, d.N);
+            hipLaunchKernelGGL(k_mf_inst_set, dim3(1), dim3(64), 0, C.stream, d, b, active[b] ? 1 : 0, (int)PH_IDLE, 0.0, 0.0, 0.0, 0);
+        }
+        launch_qp_gather(C);                       // COO -> CSC values of the active instances (start flag set, stage 0)
+        for (int b = 0; b < B; ++b)
+            hipLaunchKernelGGL(k_mf_inst_set, dim3(1), dim3(64), 0, C.stream, d, b, 0, active[b] ? (int)PH_FACTOR : (int)PH_IDLE,
+                               hsc[b], dw[b], dw_last[b], (int)fac_attempt[b]);
+        const std::vector<double> fill(BF, sentinel);
+        std::vector<double> xa(BF), xb(BF), out(BF), dv(BF);
+        std::vector<int> upos(nu);
+        SQPHIP_HIP_OK(hipMemcpyAsync(upos.data(), d.upos, sizeof(int) * (size_t)nu, hipMemcpyDeviceToHost, C.stream));
+        h2d(C, d.vv, fill.data(), BF); h2d(C, d.dinv, fill.data(), BF);
+        // the working vector twice: the flat kernel, then (last, so that it is what the factorisation consumes) the routine of
+        // the one-workgroup stages
+        h2d(C, d.xv, fill.data(), BF);
+        launch_load_xv_test(C, true);
+        d2h(C, xa.data(), d.xv, BF);
+        h2d(C, d.xv, fill.data(), BF);
+        launch_load_xv_test(C, false);
+        d2h(C, xb.data(), d.xv, BF);
+        launch_kkt_assemble(C);
+        if (K_assembled) d2h(C, K_assembled, d.K, (size_t)B * d.ld * d.Fpad);
+        // what the sweep does on the dense path (ipm_sweep): factorise with xv / vv fused in, test the inertia, solve backward
+        ldlt_factor(C.plan, d.K, d.dinv, d.phase, PH_FACTOR, &C.tm, d.xv, d.vv);
+        launch_inertia(C);
+        ldlt_solve(C.plan, d.K, d.dinv, d.xv, d.vv, d.phase, PH_SOLVE, true);
+        d2h(C, out.data(), d.xv, BF); d2h(C, dv.data(), d.dinv, BF);
+        std::vector<IpmState> st(B);
+        std::vector<int> ph(B);
+        SQPHIP_HIP_OK(hipMemcpyAsync(st.data(), d.ist, sizeof(IpmState) * (size_t)B, hipMemcpyDeviceToHost, C.stream));
+        SQPHIP_HIP_OK(hipMemcpyAsync(ph.data(), d.phase, sizeof(int) * (size_t)B, hipMemcpyDeviceToHost, C.stream));
+        for (int b = 0; b < B; ++b)
+            hipLaunchKernelGGL(k_mf_inst_set, dim3(1), dim3(64), 0, C.stream, d, b, 0, (int)PH_IDLE, 0.0, 0.0, 0.0, 0);
+        SQPHIP_HIP_OK(hipStreamSynchronize(C.stream));
+        SQPHIP_HIP_OK(hipGetLastError());
+        if (xv_mismatch) {
+            int bad = 0;
+            for (size_t k = 0; k < BF; ++k) bad += std::memcmp(&xa[k], &xb[k], sizeof(double)) != 0;
+            *xv_mismatch = bad;
+        }
+        if (xv_loaded) std::copy(xb.begin(), xb.end(), xv_loaded);
+        if (dinv_pad) std::copy(dv.begin(), dv.end(), dinv_pad);
+        for (int b = 0; b < B; ++b) {
+            const size_t f = (size_t)b * d.Fpad, o = (size_t)b * nu;
+            for (int u = 0; u < nu; ++u) {
+                if (sol) sol[o + u] = out[f + upos[u]];
+                if (dinv) dinv[o + u] = dv[f + upos[u]];
+            }
+            if (decision) {
+                int32_t *r = decision + 4 * (size_t)b;
+                r[0] = !active[b] ? 0 : ph[b] == PH_FACTOR ? 1 : ph[b] == PH_SOLVE ? 2 : 3;
+                r[1] = st[b].sel; r[2] = st[b].n_factor; r[3] = st[b].fac_attempt;
+            }
+            if (dw_out) dw_out[b] = st[b].dw;
+        }
+        return SQPHIP_OK;
+    });
+}
+
 // Launch census of the multifrontal path: launches enqueued per kernel instantiation since the context was created, summed
 // over its instance groups.  counts[cap]; names (may be null): cap x 64 characters, NUL-terminated; *n_kernels = how many
 // there are (fewer than cap: the first cap).

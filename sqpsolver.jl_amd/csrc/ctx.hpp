@@ -313,6 +313,8 @@ void sqp_stage_kernels(Ctx &C, hipStream_t s, const DV &d);      // sqp.hip: SQP
 void sqp_stream_arm(Ctx &C);          // scenario queue: every slot draws its first scenario in the first sweep
 void sqp_stream_rearm(Ctx &C);        // ... slots that found the queue empty look again (ids were appended)
 void launch_qp_gather(Ctx &C);       // COO -> CSC for instances with start set (stage 0)
+void launch_kkt_assemble(Ctx &C);     // k_kkt_assemble over the batch (dense path: the sweep and sqphip_kkt_dense_test)
+void launch_load_xv_test(Ctx &C, bool flat_kernel);   // test hook: the working vector of the solves by k_sp_load_xv or by load_solve_vector
 // comm.hip
 void comm_release(Ctx &C);
 // mfront.hip

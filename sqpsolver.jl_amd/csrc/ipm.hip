@@ -616,6 +616,14 @@ __device__ __forceinline__ void load_solve_vector(const DV &d, int inst, const d
     const int *rt = d.rtype + (long)inst * d.m;
     for (int p = threadIdx.x; p < d.Fpad; p += TPB) xv[p] = solve_vector_at(d, jv, Dd, rt, src, p);
 }
+// test hook (sqphip_kkt_dense_test): the working vector of every instance about to be factorised, by the routine of the
+// one-workgroup stages (k_sp_load_xv, below, is the flat twin)
+__global__ __launch_bounds__(TPB) void k_load_solve_vector_test(DV d)
+{
+    const int inst = blockIdx.x;
+    if (d.phase[inst] != PH_FACTOR) return;
+    load_solve_vector(d, inst, d.rhs + (long)inst * d.Npad, d.xv + (long)inst * d.Fpad);
+}
 
 // Newton right-hand side for centring target tgt (minus the second-order terms when soc), its working copy xv
 // for the triangular solves, sol = 0.  Returns max |rhs| (block-wide).
@@ -1293,6 +1301,20 @@ void launch_inertia(Ctx &C)
     hipLaunchKernelGGL(k_inertia, dim3(C.d.B), dim3(TPB), 0, C.stream, C.d, e && atoi(e) ? 1 : 0);
 }
 
+// the dense Newton matrix of every instance in PH_FACTOR: one workgroup per column of the factorised matrix
+void launch_kkt_assemble(Ctx &C)
+{
+    hipLaunchKernelGGL(k_kkt_assemble, dim3(C.d.Fpad, C.d.B), dim3(128), 0, C.stream, C.d);
+}
+
+// test hook (sqphip_kkt_dense_test): the working vector of the PH_FACTOR instances from d.rhs, by the flat kernel
+// (k_sp_load_xv, mode 0) or by the routine of the one-workgroup stages
+void launch_load_xv_test(Ctx &C, bool flat_kernel)
+{
+    if (flat_kernel) hipLaunchKernelGGL(k_sp_load_xv, dim3((C.d.Fpad + 255) / 256, C.d.B), dim3(256), 0, C.stream, C.d, 0);
+    else hipLaunchKernelGGL(k_load_solve_vector_test, dim3(C.d.B), dim3(TPB), 0, C.stream, C.d);
+}
+
 void launch_qp_gather(Ctx &C)
 {
     hipLaunchKernelGGL(k_qp_gather, dim3(C.d.B), dim3(TPB), 0, C.stream, C.d);
@@ -1387,7 +1409,7 @@ bool ipm_sweep(Ctx &C, bool sqp_level, int *host_slot)
         C.tm.close(KC_TRANS, s);
     } else if (!(mono && d.sparse)) hipLaunchKernelGGL(k_ipm_rhs, gB, bT, vlds, s, d);
     if (d.flat && (trans || !mono)) hipLaunchKernelGGL(k_sp_load_xv, gX, b256, 0, s, d, 0);
-    if (!d.sparse) hipLaunchKernelGGL(k_kkt_assemble, dim3(d.Fpad, d.B), dim3(128), 0, s, d);
+    if (!d.sparse) launch_kkt_assemble(C);
     std::pair<hipEvent_t, hipEvent_t> ev;
     if (C.tm.enabled) { ev = C.tm.get(); hipEventRecord(ev.first, s); }
     // assembly + factorisation, with the forward elimination of xv fused in

@@ -229,39 +229,94 @@ KktOrder kkt_order(int n, int m, const std::vector<int> &kpos, int mk, const std
 }  // namespace sqphip
 
 // C-ABI: pure host computation (no GPU needed), 1-based COO structures as in sqphip_create
+namespace {
+
+// the patterns kkt_order takes, from the COO structure: H as a full symmetric CSC, J as a CSR (columns ascending, duplicates
+// merged) -- what sqphip_create gets from its own pattern builder -- and the rows that stay in the factorised matrix
+struct OrderInput {
+    std::vector<int> kpos, hcolptr, hrowval, jrowptr, jrcol;
+    int mk = 0;
+};
+
+bool order_input(int64_t n, int64_t m, int64_t nnzJ, const int64_t *jrow, const int64_t *jcol, int64_t nnzH, const int64_t *hrow,
+                 const int64_t *hcol, const double *gL, const double *gU, bool condense, OrderInput &in)
+{
+    in.kpos.assign(m > 0 ? m : 1, -1);
+    in.mk = 0;
+    std::vector<std::vector<int>> hc(n), jr(m);
+    for (int64_t k = 0; k < nnzH; ++k) {
+        const int r = (int)hrow[k] - 1, c = (int)hcol[k] - 1;
+        if (r < 0 || r >= n || c < 0 || c >= n) return false;
+        hc[c].push_back(r); if (r != c) hc[r].push_back(c);
+    }
+    for (int64_t k = 0; k < nnzJ; ++k) {
+        const int r = (int)jrow[k] - 1, c = (int)jcol[k] - 1;
+        if (r < 0 || r >= m || c < 0 || c >= n) return false;
+        jr[r].push_back(c);
+    }
+    in.hcolptr.assign(n + 1, 0); in.hrowval.clear(); in.jrowptr.assign(m + 1, 0); in.jrcol.clear();
+    for (int j = 0; j < n; ++j) {
+        std::sort(hc[j].begin(), hc[j].end()); hc[j].erase(std::unique(hc[j].begin(), hc[j].end()), hc[j].end());
+        in.hrowval.insert(in.hrowval.end(), hc[j].begin(), hc[j].end()); in.hcolptr[j + 1] = (int)in.hrowval.size();
+    }
+    for (int i = 0; i < m; ++i) {
+        std::sort(jr[i].begin(), jr[i].end()); jr[i].erase(std::unique(jr[i].begin(), jr[i].end()), jr[i].end());
+        in.jrcol.insert(in.jrcol.end(), jr[i].begin(), jr[i].end()); in.jrowptr[i + 1] = (int)in.jrcol.size();
+    }
+    for (int64_t i = 0; i < m; ++i)
+        if (!condense || sqphip::kkt_row_is_kept(gL[i], gU[i], in.jrowptr[i + 1] - in.jrowptr[i])) in.kpos[i] = in.mk++;
+    return true;
+}
+
+}  // namespace
+
 extern "C" int sqphip_kkt_order(int64_t n, int64_t m, int64_t nnzJ, const int64_t *jrow, const int64_t *jcol,
                                 int64_t nnzH, const int64_t *hrow, const int64_t *hcol, const double *gL,
                                 const double *gU, int32_t rows_last, int32_t *pos, int32_t *n_lead_tiles,
                                 int32_t *order_out)
 {
     if (n <= 0 || m < 0 || !pos) return SQPHIP_EINVAL;
-    std::vector<int> kpos(m > 0 ? m : 1, -1);
-    int mk = 0;
-    std::vector<std::vector<int>> hc(n), jr(m);
-    for (int64_t k = 0; k < nnzH; ++k) {
-        const int r = (int)hrow[k] - 1, c = (int)hcol[k] - 1;
-        if (r < 0 || r >= n || c < 0 || c >= n) return SQPHIP_EINVAL;
-        hc[c].push_back(r); if (r != c) hc[r].push_back(c);
-    }
-    for (int64_t k = 0; k < nnzJ; ++k) {
-        const int r = (int)jrow[k] - 1, c = (int)jcol[k] - 1;
-        if (r < 0 || r >= m || c < 0 || c >= n) return SQPHIP_EINVAL;
-        jr[r].push_back(c);
-    }
-    std::vector<int> hcolptr(n + 1, 0), hrowval, jrowptr(m + 1, 0), jrcol;
-    for (int j = 0; j < n; ++j) {
-        std::sort(hc[j].begin(), hc[j].end()); hc[j].erase(std::unique(hc[j].begin(), hc[j].end()), hc[j].end());
-        hrowval.insert(hrowval.end(), hc[j].begin(), hc[j].end()); hcolptr[j + 1] = (int)hrowval.size();
-    }
-    for (int i = 0; i < m; ++i) {
-        std::sort(jr[i].begin(), jr[i].end()); jr[i].erase(std::unique(jr[i].begin(), jr[i].end()), jr[i].end());
-        jrcol.insert(jrcol.end(), jr[i].begin(), jr[i].end()); jrowptr[i + 1] = (int)jrcol.size();
-    }
-    for (int64_t i = 0; i < m; ++i)
-        if (sqphip::kkt_row_is_kept(gL[i], gU[i], jrowptr[i + 1] - jrowptr[i])) kpos[i] = mk++;
-    sqphip::KktOrder o = sqphip::kkt_order((int)n, (int)m, kpos, mk, hcolptr, hrowval, jrowptr, jrcol, rows_last != 0);
-    for (int u = 0; u < (int)n + mk; ++u) pos[u] = o.pos[u];
+    OrderInput in;
+    if (!order_input(n, m, nnzJ, jrow, jcol, nnzH, hrow, hcol, gL, gU, true, in)) return SQPHIP_EINVAL;
+    sqphip::KktOrder o = sqphip::kkt_order((int)n, (int)m, in.kpos, in.mk, in.hcolptr, in.hrowval, in.jrowptr, in.jrcol, rows_last != 0);
+    for (int u = 0; u < (int)n + in.mk; ++u) pos[u] = o.pos[u];
     if (n_lead_tiles) *n_lead_tiles = o.Ts;
     if (order_out) *order_out = o.Nf;
+    return SQPHIP_OK;
+}
+
+// Test hook (include/sqphip_test_hooks.h): the order, tiles and coupling masks sqphip_create sets up for the dense path of
+// the structure under the two options -- the same kkt_row_is_kept / kkt_order / kkt_pair_lists, the same choice between the
+// tile order and the plain one, the same condition for handing the masks to the kernels.
+extern "C" int sqphip_kkt_order_info(int64_t n, int64_t m, int64_t nnzJ, const int64_t *jrow, const int64_t *jcol,
+                                     int64_t nnzH, const int64_t *hrow, const int64_t *hcol, const double *gL,
+                                     const double *gU, int32_t condense, int32_t tile_order, int32_t *pos, int32_t *info,
+                                     uint8_t *tmask, int32_t cap_mask, int32_t *pair_ptr, int32_t cap_ptr, int32_t *pair_k,
+                                     int32_t cap_k, int32_t *n_k)
+{
+    if (n <= 0 || m < 0 || !pos || !info || (m > 0 && (!gL || !gU))) return SQPHIP_EINVAL;
+    OrderInput in;
+    if (!order_input(n, m, nnzJ, jrow, jcol, nnzH, hrow, hcol, gL, gU, condense != 0, in)) return SQPHIP_EINVAL;
+    const int nu = (int)n + in.mk;
+    sqphip::KktOrder o;
+    if (condense && tile_order)
+        o = sqphip::kkt_order((int)n, (int)m, in.kpos, in.mk, in.hcolptr, in.hrowval, in.jrowptr, in.jrcol, /*rows_last=*/true);
+    else {
+        o.pos.resize(nu);
+        std::iota(o.pos.begin(), o.pos.end(), 0);
+        o.Nf = nu;
+    }
+    const int Fpad = (o.Nf + 63) / 64 * 64, Tr = Fpad / 64 - o.Ts;
+    const bool masks = o.Ts > 0 && o.Tr > 0 && !getenv("SQPHIP_NO_TILE_MASK");
+    for (int u = 0; u < nu; ++u) pos[u] = o.pos[u];
+    info[0] = nu; info[1] = o.Ts; info[2] = Tr; info[3] = o.Nf; info[4] = Fpad; info[5] = masks ? 1 : 0;
+    if (!masks) {        // the kernels get no mask: reported as an empty one, with the (empty) lists it gives
+        o.tmask.assign((size_t)Tr * std::max(1, o.Ts), 0);
+        sqphip::kkt_pair_lists(o.Ts, Tr, o.tmask, o.pair_ptr, o.pair_k);
+    }
+    if (n_k) *n_k = (int)o.pair_k.size();
+    if (tmask && cap_mask >= (int)o.tmask.size()) std::copy(o.tmask.begin(), o.tmask.end(), tmask);
+    if (pair_ptr && cap_ptr >= (int)o.pair_ptr.size()) std::copy(o.pair_ptr.begin(), o.pair_ptr.end(), pair_ptr);
+    if (pair_k && cap_k >= (int)o.pair_k.size()) std::copy(o.pair_k.begin(), o.pair_k.end(), pair_k);
     return SQPHIP_OK;
 }

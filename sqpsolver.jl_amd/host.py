@@ -81,6 +81,27 @@ def kkt_order(n, m, jrow, jcol, hrow, hcol, gL, gU, rows_last=True):
     return pos, ts.value, nf.value
 
 
+def kkt_order_info(n, m, jrow, jcol, hrow, hcol, gL, gU, condense=1, tile_order=1):
+    """What `sqphip_create` sets up for the dense path (`sqphip_kkt_order_info`, host only): a dict with pos [nu], nu, Ts,
+    Tr, Nf, Fpad, masks (whether the kernels get the coupling mask), tmask [Tr, max(Ts, 1)], pair_ptr, pair_k."""
+    L = _lib.lib()
+    jr, jc, hr, hc = (np.ascontiguousarray(a, dtype=np.int64) for a in (jrow, jcol, hrow, hcol))
+    pos = np.zeros(n + m, dtype=np.int32); info = np.zeros(6, dtype=np.int32); nk = C.c_int32()
+    args = (n, m, len(jr), _l(jr), _l(jc), len(hr), _l(hr), _l(hc), _d(_f(gL)), _d(_f(gU)), int(condense), int(tile_order))
+    rc = L.sqphip_kkt_order_info(*args, _i(pos), _i(info), None, 0, None, 0, None, 0, C.byref(nk))
+    if rc != 0:
+        raise SqpHipError(f"sqphip_kkt_order_info failed ({rc})")
+    nu, Ts, Tr = (int(x) for x in info[:3])
+    tmask = np.zeros((Tr, max(Ts, 1)), dtype=np.uint8); pptr = np.zeros(Tr * (Tr + 1) // 2 + 1, dtype=np.int32)
+    pk = np.zeros(max(1, nk.value), dtype=np.int32)
+    rc = L.sqphip_kkt_order_info(*args, _i(pos), _i(info), tmask.ctypes.data_as(C.POINTER(C.c_uint8)), tmask.size, _i(pptr),
+                                 pptr.size, _i(pk), pk.size, C.byref(nk))
+    if rc != 0:
+        raise SqpHipError(f"sqphip_kkt_order_info failed ({rc})")
+    return {"pos": pos[:nu].copy(), "nu": nu, "Ts": Ts, "Tr": Tr, "Nf": int(info[3]), "Fpad": int(info[4]),
+            "masks": bool(info[5]), "tmask": tmask, "pair_ptr": pptr, "pair_k": pk[:nk.value].copy()}
+
+
 def kkt_symbolic(n, m, jrow, jcol, hrow, hcol, gL, gU, condense=True, rows_after_vars=True, small_front=0,
                  zero_frac=-1.0):
     """(pos, stats dict) of `sqphip_kkt_symbolic`: the symbolic analysis of the sparse Newton matrix; host-only."""
@@ -420,6 +441,27 @@ class Context:
                                               _i(rt), _d(_f(hsc)), _d(_f(dw)), _d(_f(dw_last)), _i(fa), float(sentinel),
                                               _d(v0), _d(v1), C.byref(nk)))
         return v0, v1
+
+    def kkt_dense_test(self, active, jval, hval, Dd, sigp, hd, rtype, hsc, dw, dw_last, fac_attempt, rhs, Fpad, nu,
+                       sentinel=-7.5):
+        """Kernel-level hook of the dense path (`sqphip_kkt_dense_test`); per-instance inputs stacked as [B, ...], rhs
+        [B, n + m].  Fpad, nu: as `kkt_order_info` reports them for the context's structure and options.  Returns a dict:
+        K [B, Fpad, Fpad] (K[b][r, c]: row r, column c of the matrix as assembled, factorised order), xv [B, Fpad],
+        xv_mismatch (entries on which the two loaders of the working vector differ), sol / dinv [B, nu] (unknown order),
+        dinv_pad [B, Fpad], decision [B, 4] (outcome 0 idle / 1 another shift / 2 passed / 3 given up, sel, n_factor,
+        fac_attempt), dw [B]."""
+        rhs = _f(rhs); B = rhs.shape[0]
+        K = np.zeros((B, Fpad, Fpad)); xv = np.zeros((B, Fpad)); dpad = np.zeros((B, Fpad))
+        sol = np.zeros((B, nu)); dinv = np.zeros((B, nu))
+        dec = np.zeros((B, 4), dtype=np.int32); dwo = np.zeros(B); mis = C.c_int32(-1)
+        i32 = lambda a: np.ascontiguousarray(a, dtype=np.int32)
+        act, rt, fa = i32(active), i32(rtype), i32(fac_attempt)
+        self._ck(self.L.sqphip_kkt_dense_test(self.h, _i(act), _d(_f(jval)), _d(_f(hval)), _d(_f(Dd)), _d(_f(sigp)), _d(_f(hd)),
+                                              _i(rt), _d(_f(hsc)), _d(_f(dw)), _d(_f(dw_last)), _i(fa), _d(rhs), float(sentinel),
+                                              _d(K), _d(xv), C.byref(mis), _d(sol), _d(dinv), _d(dpad), _i(dec), _d(dwo)))
+        # the device holds the matrix column-major: K[b][c, r] as read; hand out row-major views
+        return {"K": K.transpose(0, 2, 1), "xv": xv, "xv_mismatch": int(mis.value), "sol": sol, "dinv": dinv,
+                "dinv_pad": dpad, "decision": dec, "dw": dwo}
 
     def mf_census(self):
         """Launch census of the multifrontal path (`sqphip_mf_census`): {kernel instantiation: launches enqueued}."""
