@@ -562,6 +562,55 @@ int sqphip_nlp_add_softmax_block(sqphip_ctx *ctx, int64_t N, int32_t d, int32_t 
                                  const int64_t *cols /* [Kf][d] 1-based */, const double *A /* [N][d] row-major */,
                                  const int32_t *labels /* [N] 0-based */, const double *shift /* [Kf][N] or NULL: zeros */,
                                  const double *weight /* [N] or NULL: ones */, int32_t *blk_out /* 0-based block number, or NULL */);
+/* Cox partial-likelihood data blocks of the objective of an NLP context (survival data, Breslow ties): the block adds
+ *     sum_{i < N} c_i [ log( sum_{j < risk[i]} W[j] exp(u_j) ) - u_i ],   u_i = sum_{j < d} A[i][j] x_{cols[j]} + S[i],   c_i = W[i] event[i]
+ * to row 0.  The points are given sorted by non-increasing time, so the risk set of point i is the risk[i] leading points:
+ * i + 1 <= risk[i] <= N (i 0-based), non-decreasing in i, one value per tie group.  event[i] >= 0 is the event indicator (0: a
+ * censored point).  A, cols, risk and event are shared by the batch; the weights W [N] (0 / 1 for folds, integers for
+ * resamples) and the offsets S [N] belong to the instance.  A point with c_i = 0 contributes exactly 0 and its logarithm is
+ * never formed; W[j] = 0 removes point j from every risk set, so a fold is the Cox fit on the subset and an integer weight is a
+ * replicated point.  W >= 0 is the caller's business.  Limits: 1 <= d <= 128 distinct 1-based columns in any order, N >= 1,
+ * N d < 2^31.  Cox blocks count among the four blocks of a context and are evaluated in block order with the others, behind
+ * the same barrier.  With m = max_i u_i, e_j = W[j] exp(u_j - m), T_i = sum_{j < risk[i]} e_j, q_i = c_i / T_i (0 where
+ * c_i = 0) and Q_j = sum_{i : risk[i] > j} q_i:
+ *     f = sum_i c_i (m + log T_i - u_i),   gradient A'(e o Q - c),
+ *     Hessian A' diag(e o Q) A - sum_i (c_i / T_i^2) m_i m_i',   m_i = sum_{j < risk[i]} e_j A[j][.]
+ * State rules and re-lay as for sqphip_nlp_add_block (SQPHIP_ESTATE once the layout is final); the instance's block grows by
+ *     W [N] | S [N]                                                               (padded to an even count)
+ * and its workspace by 6 N + N d doubles (u, e, the running sums of e, q, -q, 1 / T and the N x d running sums P of e_j A[j][.]).
+ * sqphip_nlp_set_instance_block and sqphip_nlp_stream_set_block serve the block unchanged (weight [N], shift [N]);
+ * sqphip_nlp_stream_set restores the data of this call.
+ * Unless nnzH = 0 the Hessian COO of sqphip_create must hold the lower entry of every pair of block columns, the diagonal
+ * included.
+ * SQPHIP_EINVAL, with sqphip_last_error naming the block and the 1-based column, entry or point: a context without an NLP
+ * attach, d outside 1..128, N < 1 or N d too large, a fifth block, null cols, A, risk or event, risk[i] outside i + 1 .. N,
+ * risk decreasing, an event that is negative or not finite, a column out of range or twice, a missing Hessian entry.
+ * Evaluation (one workgroup per instance; every sum in an order that depends on N, d and risk only, no atomics):
+ *   points    u_i = 0, u_i = fma(A[i][j], x_cols[j], u_i) for j = 0 .. d - 1, u_i += S[i]; m by a maximum over the workgroup;
+ *             e_i = W[i] exp(u_i - m);
+ *   scans     one wave per scan, chunks of 64 points in rising order: within a chunk lane l adds the value of lane l - o for
+ *             o = 1, 2, .. 32, then the carry of the chunks before, and lane 63's sum becomes the next carry.  The running sums
+ *             of e give T_i = (sum up to point risk[i] - 1); those of e_k A[k][c] (one rounding) give column c of P; q is
+ *             scanned from the last point down and Q_j is that sum at the first point i with risk[i] > j;
+ *   f         thread t sums c_i ((m + log T_i) - u_i) over the i = t, t + 1024, ... with c_i != 0, a wave adds its 64 sums by
+ *             the xor butterfly 32, 16, .. 1, thread 0 adds the 16 wave sums in wave order, and the result is added to f.  A
+ *             call for f alone (the Armijo probe) forms u, m, e and T and nothing else;
+ *   gradient  column j: lane l of its wave sums (e_i Q_i - c_i) A[i][j] over i = l, l + 64, ..., the same butterfly, added to
+ *             grad[cols[j]];
+ *   Hessian   lower 16 x 16 tiles on v_mfma_f64_16x16x4_f64, four points per instruction in rising order, two accumulator
+ *             chains: (e_p Q_p) A[p][r] against A[p][c], and (-q_p) P[risk[p] - 1][r] against P[risk[p] - 1][c] (1 / T_p) -- the factor
+ *             -c_p / T_p^2 split between the operands, since T^2 underflows for logits 350 below the maximum; ragged
+ *             edges as zeros; sigma times (chain 1 + chain 2) is added to the entry's COO slot by one thread.  The two parts are
+ *             separate sums; their difference is a covariance and cancels, and the error bound (tests/nlp_cox_ref.py) is that
+ *             of their magnitudes added.
+ * Domain: a point whose u_j lies more than about 700 below max u underflows to e_j = 0, and a risk set made of such points
+ * alone has T = 0: the caller's business.  Results are bit-reproducible and independent of slot, neighbours and instance
+ * groups.  A context without a Cox block files the bits it filed before this call existed. */
+int sqphip_nlp_add_cox_block(sqphip_ctx *ctx, int64_t N, int32_t d, const int64_t *cols /* [d] 1-based */,
+                             const double *A /* [N][d] row-major, points by non-increasing time */,
+                             const int32_t *risk /* [N] leading points in the risk set */, const double *event /* [N] >= 0 */,
+                             const double *shift /* [N] or NULL: zeros */, const double *weight /* [N] or NULL: ones */,
+                             int32_t *blk_out /* 0-based block number, or NULL */);
 /* Dense data blocks with several outputs: one design matrix, R weight vectors, a target row each.  Output r adds
  *     sum_{i < N} W[r][i] kappa(sum_{j < d} A[i][j] x_{cols[j]} + S[i])
  * to row rows[r]; row 0 is the objective, row i >= 1 a nonlinear constraint row (i > num_linear).  Constraints on the data the

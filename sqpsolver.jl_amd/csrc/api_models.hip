@@ -599,6 +599,48 @@ extern "C" int sqphip_nlp_add_softmax_block(sqphip_ctx *h, int64_t N, int32_t d,
     return nlp_block_commit(h, blk, kb, (long)N, d, (long)N, (long)Kf * N, (long)Kf * N, A, cv, hs, weight, shift, Kb, blk_out);
 }
 
+// a Cox partial-likelihood block (nlp_cox_dev.hpp): the shape checks of sqphip_nlp_add_block, then risk and event
+extern "C" int sqphip_nlp_add_cox_block(sqphip_ctx *h, int64_t N, int32_t d, const int64_t *cols, const double *A, const int32_t *risk,
+                                        const double *event, const double *shift, const double *weight, int32_t *blk_out)
+{
+    const std::string who = "sqphip_nlp_add_cox_block";
+    if (!h) return SQPHIP_EINVAL;
+    Ctx &C0 = h->c;
+    int kb; std::string blk;
+    if (int rc = nlp_block_begin(h, who, kb, blk)) return rc;
+    auto fail = [&](const std::string &msg) { C0.err = blk + ": " + msg; return (int)SQPHIP_EINVAL; };
+    if (d < 1 || d > NLP_BLOCK_MAX_D) return fail("d = " + std::to_string(d) + " columns (1.." + std::to_string((int)NLP_BLOCK_MAX_D) + ")");
+    if (N < 1) return fail("N = " + std::to_string(N) + " points (at least 1)");
+    if (N > INT32_MAX / d) return fail("N d = " + std::to_string(N) + " x " + std::to_string(d) + " is too large (N d < 2^31)");
+    if (!cols || !A || !risk || !event) return fail("null cols, A, risk or event");
+    for (int64_t i = 0; i < N; ++i) {
+        if (risk[i] < i + 1 || risk[i] > N)
+            return fail("point " + std::to_string(i + 1) + ": risk " + std::to_string(risk[i]) + " outside " + std::to_string(i + 1) + ".." + std::to_string(N));
+        if (i > 0 && risk[i] < risk[i - 1])
+            return fail("point " + std::to_string(i + 1) + ": risk " + std::to_string(risk[i]) + " decreases from " + std::to_string(risk[i - 1]));
+        if (!std::isfinite(event[i]) || event[i] < 0.0)
+            return fail("point " + std::to_string(i + 1) + ": event " + std::to_string(event[i]) + " (finite and not negative)");
+    }
+    std::vector<int> hs, cv;
+    const std::string bad = nlp_block_columns(C0.nl.slots, d, cols, cv, hs);
+    if (!bad.empty()) return fail(bad);
+    // first[j]: the first point whose risk set holds point j; risk is non-decreasing, so these points are i >= first[j]
+    std::vector<int> fst((size_t)N);
+    for (int64_t j = 0, i = 0; j < N; ++j) {
+        while (risk[i] <= j) ++i;              // (risk[j] >= j + 1: i <= j)
+        fst[j] = (int)i;
+    }
+    NlpBlkDev Kb = {};
+    Kb.cox = 1;
+    const int rc = guarded(h, [&](Ctx &C) {
+        Kb.risk = C.upload(std::vector<int>(risk, risk + N)); Kb.first = C.upload(fst);
+        Kb.event = C.upload(std::vector<double>(event, event + N));
+        return SQPHIP_OK;
+    });
+    if (rc) return rc;
+    return nlp_block_commit(h, blk, kb, (long)N, d, (long)N, (long)N, 6 * (long)N + (long)N * d, A, cv, hs, weight, shift, Kb, blk_out);
+}
+
 // weight / shift of block blk into the block of values v (of an instance or of a scenario of the queue); NULL: kept
 static int nlp_block_put(sqphip_ctx *h, double *v, int32_t blk, const double *weight, const double *shift)
 {

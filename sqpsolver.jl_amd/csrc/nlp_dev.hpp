@@ -44,6 +44,8 @@
 // one design matrix: sum_i W_r[i] kappa(A_i'x + S_i) is added to row r's value, A'(W_r kappa') to its Jacobian row and
 // A' diag(kappa'' sum_r mu_r W_r) A to the Hessian of the Lagrangian in one MFMA pass (nlp_rowblock_dev.hpp).  It counts among
 // the same four blocks and adds to gv and jv behind the plan passes as the others add to f, grad and hv.
+// sqphip_nlp_add_cox_block: Cox partial-likelihood blocks sum_i c_i [log sum_{j < risk[i]} W_j exp(u_j) - u_i] couple the points of
+// a block through prefix and suffix scans (nlp_cox_dev.hpp); they count among the same four blocks and add to f, grad and hv.
 #pragma once
 #include "ctx.hpp"
 #include "dev_util.hpp"
@@ -74,6 +76,11 @@ struct NlpBlkDev {
     int R;
     int row[NLP_BLOCK_MAX_R];             // [R] target of an output: 0 the objective, i row i (1-based)
     const int *js;                        // [R][d] Jacobian COO slot of (row[r], col[j]); unread for an output on row 0
+    // a Cox partial-likelihood block (sqphip_nlp_add_cox_block; nlp_cox_dev.hpp): cox != 0, K = R = 0, ke and par unread.  wz: u [N] |
+    // e [N] | cs [N] | q [N] | -q [N] | 1 / T [N] | P [N][d]
+    int cox;
+    const int *risk, *first;              // [N] leading points in the risk set of a point; [N] the first point whose risk set holds a point (0-based)
+    const double *event;                  // [N] event indicator (0: censored)
 };
 
 struct NlpDev {
@@ -98,7 +105,7 @@ struct NlpDev {
     const double *fpar;                   // [nfac] real exponent of a POWR factor (loaded for that kind only)
     int data;                             // sqphip_nlp_attach_data: b, a, p are the instance's, in its block of DV::nlv at ...
     int ob, oa, op;                       // ... ob [nfac], oa [nargs], op [nfac] (op: with a POWR factor only); fab, acoef, aw, fpar unread
-    int ws;                               // doubles of workspace per instance (DV::nlw): 3 nfac, with blocks + TPB / 64 wave sums + 3 TPB kappa values + a block's own (2 N, Kf N, 3 N)
+    int ws;                               // doubles of workspace per instance (DV::nlw): 3 nfac, with blocks + TPB / 64 wave sums + 3 TPB kappa values + a block's own (2 N, Kf N, 3 N, 6 N + N d)
     int nblk;                             // dense data blocks of the objective (sqphip_nlp_add_block, nlp_block_dev.hpp); uniform over the launch
     NlpBlkDev blk[NLP_MAX_BLOCKS];
 };
@@ -202,6 +209,7 @@ static __device__ __forceinline__ void nlp_factor(int ke, double a, double u, do
 #include "nlp_block_dev.hpp"
 #include "nlp_rowblock_dev.hpp"
 #include "nlp_softmax_dev.hpp"
+#include "nlp_cox_dev.hpp"
 namespace sqphip {
 
 // the acopf_eval signature; any of f_out, grad, gv, jv, hv may be null.  Called by every thread of the workgroup.

@@ -592,7 +592,17 @@ class Context:
         sqp_run or nlp_stream_begin.  Returns its number.  An nlp_terms.NlpSoftmaxBlock goes through
         sqphip_nlp_add_softmax_block, an nlp_terms.NlpRowBlock (several outputs, constraint rows) through
         sqphip_nlp_add_row_block."""
-        from .nlp_terms import NlpRowBlock, NlpSoftmaxBlock
+        from .nlp_terms import NlpCoxBlock, NlpRowBlock, NlpSoftmaxBlock
+        if isinstance(b, NlpCoxBlock):                # (sqphip_nlp_add_cox_block)
+            if not hasattr(self.L, "sqphip_nlp_add_cox_block"):
+                raise SqpHipError("libsqphip.so lacks sqphip_nlp_add_cox_block: rebuild it")
+            A = _f(np.atleast_2d(b.A))
+            out = C.c_int32(-1)
+            self._ck(self.L.sqphip_nlp_add_cox_block(self.h, A.shape[0], A.shape[1], _l(np.ascontiguousarray(b.cols, dtype=np.int64)),
+                                                     _d(A), _i(np.ascontiguousarray(b.risk, dtype=np.int32)), _d(_f(b.event)),
+                                                     _d(None if b.shift is None else _f(b.shift)),
+                                                     _d(None if b.weight is None else _f(b.weight)), C.byref(out)))
+            return out.value
         if isinstance(b, NlpRowBlock):
             if not hasattr(self.L, "sqphip_nlp_add_row_block"):
                 raise SqpHipError("libsqphip.so lacks sqphip_nlp_add_row_block: rebuild it")

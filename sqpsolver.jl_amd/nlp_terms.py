@@ -41,11 +41,14 @@ plain affine factors.  Twice inside one factor stays an error.  SQRT and POWR ne
                          u_ik = A_i'x_cols[k] + shift_ki (sqphip_nlp_add_softmax_block); it sits in NlpTerms.blocks beside NlpBlock
     NlpRowBlock          a dense data block with several outputs: one A, R <= 8 weight vectors with a target row each (row 0:
                          the objective), sum_i w_ri kappa(A_i'x_cols + b_i) added to row r (sqphip_nlp_add_row_block)
+    NlpCoxBlock          a Cox partial-likelihood data block (survival data, Breslow ties), sum_i w_i event_i [log sum_{j < risk_i}
+                         w_j exp(u_j) - u_i] over points sorted by non-increasing time (sqphip_nlp_add_cox_block)
     block_eval           value, gradient and dense Hessian of the blocks of a problem in numpy
     row_block_eval       ... of its blocks with several outputs: the rows' values and Jacobian rows too, the Hessian of the
                          Lagrangian with sigma and lam
     neyman_pearson_model, rate_constrained_logistic_model     constraints on the data the objective is fitted to, as row blocks
     multinomial_block_model  ridge-regularised K-class logistic regression as one softmax block plus terms
+    cox_risk, cox_block_model  the risk sets of sorted times; ridge-regularised Cox regression as one Cox block plus terms
     logistic_block_model, poisson_block_model, least_squares_block_model     data fits of any size as one block plus terms
     fold_weights         the k training folds of N points as 0 / 1 weight vectors (logistic_fold_indices)
     from_qcqp            a Qcqp (qcqp.py) restated as terms
@@ -129,6 +132,48 @@ class NlpSoftmaxBlock:
 
 
 @dataclasses.dataclass
+class NlpCoxBlock:
+    """sum_{i < N} c_i [log sum_{j < risk_i} weight_j exp(u_j) - u_i], u_i = sum_j A[i, j] x_{cols[j]} + shift_i, c_i = weight_i event_i,
+    in the objective: the Cox partial likelihood with Breslow ties.  The points are sorted by non-increasing time and the risk
+    set of point i is the risk[i] leading points: i + 1 <= risk[i] <= N (i 0-based), non-decreasing, one value per tie group
+    (cox_risk).  cols d distinct 1-based variables in any order (d <= 128), A [N, d], event [N] >= 0 (0: censored); shift None:
+    zeros, weight None: ones (0 / 1 for folds, integers for resamples)."""
+    cols: np.ndarray
+    A: np.ndarray
+    risk: np.ndarray
+    event: np.ndarray
+    shift: np.ndarray | None = None
+    weight: np.ndarray | None = None
+
+    def __post_init__(self):
+        self.cols = _i64(np.atleast_1d(self.cols))
+        self.A = _f64(np.atleast_2d(self.A))
+        N, d = self.A.shape
+        if not 1 <= d <= MAX_BLOCK_COLS:
+            raise ValueError(f"d = {d} columns (1..{MAX_BLOCK_COLS})")
+        if len(self.cols) != d or len(np.unique(self.cols)) != d:
+            raise ValueError(f"cols: {d} distinct variables")
+        self.risk = np.ascontiguousarray(np.atleast_1d(self.risk), dtype=np.int32)
+        self.event = _f64(np.atleast_1d(self.event))
+        if self.risk.shape != (N,) or self.event.shape != (N,):
+            raise ValueError(f"risk and event: {N} values each")
+        lo = np.arange(1, N + 1)
+        if np.any(self.risk < lo) or np.any(self.risk > N):
+            i = int(np.argmax((self.risk < lo) | (self.risk > N)))
+            raise ValueError(f"point {i + 1}: risk {int(self.risk[i])} outside {i + 1}..{N}")
+        if np.any(np.diff(self.risk) < 0):
+            i = int(np.argmax(np.diff(self.risk) < 0)) + 1
+            raise ValueError(f"point {i + 1}: risk {int(self.risk[i])} decreases from {int(self.risk[i - 1])}")
+        if not np.all(np.isfinite(self.event)) or np.any(self.event < 0):
+            i = int(np.argmax(~(np.isfinite(self.event) & (self.event >= 0))))
+            raise ValueError(f"point {i + 1}: event {self.event[i]} (finite and not negative)")
+        self.shift = np.zeros(N) if self.shift is None else _f64(self.shift)
+        self.weight = np.ones(N) if self.weight is None else _f64(self.weight)
+        if self.shift.shape != (N,) or self.weight.shape != (N,):
+            raise ValueError(f"shift and weight: {N} values each")
+
+
+@dataclasses.dataclass
 class NlpRowBlock:
     """Output r adds sum_{i < N} weight[r, i] kappa(sum_j A[i, j] x_{cols[j]} + shift_i) to row rows[r] (0: the objective, i: row
     i, a nonlinear one): one design matrix, R = len(rows) <= 8 distinct target rows.  kind, cols, A, exp, par as in NlpBlock;
@@ -184,7 +229,7 @@ class NlpTerms:
     fpar: np.ndarray | None = None     # [nfac] real exponent of a POWR factor (0 elsewhere); None: no POWR factor
     general: bool = False              # written for sqphip_nlp_attach_general (make_nlp_terms: needs_general); False: a model
                                        # of the older calls, which keep refusing what they refuse
-    blocks: list = dataclasses.field(default_factory=list)     # NlpBlock, NlpSoftmaxBlock, NlpRowBlock: dense data blocks (at most 4)
+    blocks: list = dataclasses.field(default_factory=list)     # NlpBlock, NlpSoftmaxBlock, NlpRowBlock, NlpCoxBlock: dense data blocks (at most 4)
 
     @property
     def affine(self) -> bool:
@@ -257,7 +302,7 @@ def make_nlp_terms(n, m, num_linear, terms, g0=None, f0=0.0, xL=None, xU=None, g
     if len(p.blocks) > MAX_BLOCKS:
         raise ValueError(f"{len(p.blocks)} blocks (at most {MAX_BLOCKS})")
     for k, b in enumerate(p.blocks):
-        if isinstance(b, (NlpSoftmaxBlock, NlpRowBlock)) and (b.cols.min() < 1 or b.cols.max() > n):
+        if isinstance(b, (NlpSoftmaxBlock, NlpRowBlock, NlpCoxBlock)) and (b.cols.min() < 1 or b.cols.max() > n):
             raise ValueError(f"block {k + 1}: a column outside 1..{n}")
         if isinstance(b, NlpRowBlock):
             if b.rows.min() < 0 or b.rows.max() > m:
@@ -630,6 +675,31 @@ def _softmax_eval(b: NlpSoftmaxBlock, x):
     return f, g, H
 
 
+def _cox_eval(b: NlpCoxBlock, x):
+    """(f, grad [d], H [d, d]) of a Cox block in the block's own column order.  The logits are shifted by their maximum; T and Q
+    are running sums from the front and from the back, as on the device; the Hessian is formed as A'diag(e Q) A minus
+    M'diag(c) M with M_i = P[risk_i - 1] / T_i, P the running sums of e_j A_j: two separate sums, as the device forms it.  A
+    point with c_i = 0 contributes exactly 0 and its logarithm is never formed."""
+    N, d = b.A.shape
+    u = b.A @ x[b.cols - 1] + b.shift
+    m = u.max()
+    e = b.weight * np.exp(u - m)
+    c = b.weight * b.event
+    on = c != 0.0
+    T = np.cumsum(e)[b.risk - 1]
+    with np.errstate(all="ignore"):
+        lt = np.where(on, np.log(np.where(on, T, 1.0)), 0.0)
+        q = np.where(on, c / np.where(on, T, 1.0), 0.0)
+    f = float(np.sum(np.where(on, c * ((m + lt) - u), 0.0)))
+    first = np.searchsorted(b.risk, np.arange(N), side="right")       # the first i with risk_i > j
+    G = e * np.cumsum(q[::-1])[::-1][first]
+    g = b.A.T @ (G - c)
+    with np.errstate(all="ignore"):
+        M = np.where(on[:, None], np.cumsum(e[:, None] * b.A, axis=0)[b.risk - 1] / np.where(on, T, 1.0)[:, None], 0.0)
+    H = b.A.T @ (G[:, None] * b.A) - M.T @ (c[:, None] * M)
+    return f, g, H
+
+
 def block_eval(p: NlpTerms, x, blocks=None):
     """(f, grad [n], H [n, n]) of the blocks of p at x: sum_i w_i kappa(u_i), A'(w kappa'), A' diag(w kappa'') A scattered to
     the blocks' columns.  Blocks with several outputs (NlpRowBlock) are row_block_eval's, not counted here."""
@@ -641,6 +711,13 @@ def block_eval(p: NlpTerms, x, blocks=None):
         if isinstance(b, NlpSoftmaxBlock):
             fb, gb, Hb = _softmax_eval(b, x)
             c = b.cols.ravel() - 1
+            f += fb
+            np.add.at(g, c, gb)
+            H[np.ix_(c, c)] += Hb
+            continue
+        if isinstance(b, NlpCoxBlock):
+            fb, gb, Hb = _cox_eval(b, x)
+            c = b.cols - 1
             f += fb
             np.add.at(g, c, gb)
             H[np.ix_(c, c)] += Hb
@@ -712,6 +789,34 @@ def multinomial_block_model(X, y, K, reg, pinned=True, weight=None) -> NlpTerms:
     n = Kf * d
     blk = NlpSoftmaxBlock(np.arange(1, n + 1).reshape(Kf, d), X, y, K, pinned, None, weight)
     return make_nlp_terms(n, 0, 0, _ridge(n, reg), xL=np.full(n, -50.0), xU=np.full(n, 50.0), x0=np.zeros(n), blocks=[blk])
+
+
+def cox_risk(time) -> np.ndarray:
+    """risk [N] of times sorted in non-increasing order: risk[i] is the number of points with time >= time[i] (Breslow: a tie
+    group shares one value)."""
+    t = _f64(np.atleast_1d(time))
+    if np.any(np.diff(t) > 0):
+        raise ValueError("cox_risk: the times are not sorted in non-increasing order")
+    return np.searchsorted(-t, -t, side="right").astype(np.int32)
+
+
+def cox_block_model(A, time, event, ridge, weight=None, shift=None) -> NlpTerms:
+    """Ridge-regularised Cox proportional-hazards regression with Breslow ties,
+        sum_i w_i event_i [log sum_{j: time_j >= time_i} w_j exp(A_j'b) - A_i'b] + ridge / 2 |b|^2,
+    as one Cox block plus the ridge terms, which keep the fit bounded.  The points are sorted here by decreasing time (a stable
+    sort: tied points keep their order) and weight / shift, given in the caller's order, are sorted with them; NlpTerms.cox_order
+    is that permutation, so that the weights of another fold or resample are w[p.cox_order] (fold_weights: the folds of the
+    sorted points).  -50 <= b <= 50, from b = 0."""
+    A, t, ev = np.atleast_2d(_f64(A)), _f64(time), _f64(event)
+    N, n = A.shape
+    if t.shape != (N,) or ev.shape != (N,):
+        raise ValueError(f"time and event: {N} values each")
+    order = np.argsort(-t, kind="stable")
+    pick = lambda v: None if v is None else _f64(v)[order]
+    blk = NlpCoxBlock(np.arange(1, n + 1), A[order], cox_risk(t[order]), ev[order], pick(shift), pick(weight))
+    p = make_nlp_terms(n, 0, 0, _ridge(n, ridge), xL=np.full(n, -50.0), xU=np.full(n, 50.0), x0=np.zeros(n), blocks=[blk])
+    p.cox_order = order
+    return p
 
 
 def neyman_pearson_model(X, y, alpha, reg, weight=None) -> NlpTerms:
