@@ -611,6 +611,54 @@ int sqphip_nlp_add_cox_block(sqphip_ctx *ctx, int64_t N, int32_t d, const int64_
                              const int32_t *risk /* [N] leading points in the risk set */, const double *event /* [N] >= 0 */,
                              const double *shift /* [N] or NULL: zeros */, const double *weight /* [N] or NULL: ones */,
                              int32_t *blk_out /* 0-based block number, or NULL */);
+/* Log-sum-exp row blocks of an NLP context (geometric programmes in convex form, smooth maxima of affine functions, entropic
+ * risk): output r owns the consecutive points seg[r] .. seg[r + 1] - 1 (0-based; seg[0] = 0, seg[R] = N, every segment at
+ * least one point) and adds
+ *     lse_r = log( sum_{i in segment r} W[i] exp(u_i) ),   u_i = sum_{j < d} A[i][j] x_{cols[j]} + S[i]
+ * to row rows[r]; row 0 is the objective (it may be absent), row i >= 1 a nonlinear constraint row (i > num_linear); the rows are
+ * distinct.  A posynomial sum_k c_k prod_j y_j^{a_kj} in the variables x = log y is one output with A = (a_kj) and S = log c.
+ * A, cols, seg and rows are shared by the batch; the weights W [N] >= 0 and the shifts S [N] (the log-coefficients of the
+ * monomials) belong to the instance.  W[i] = 0 removes monomial i: it contributes exactly 0 whatever its logit, and its
+ * exponential is never multiplied in.  W >= 0 is the caller's business.  Limits: 1 <= d <= 128 distinct 1-based columns in any
+ * order, N >= 1, N d < 2^31, 1 <= R <= N, R d < 2^31 -- R is not capped otherwise: rows, seg, the output of every point and the
+ * Jacobian slots live in uploaded arrays.  The block counts among the four blocks of a context and is evaluated in block order
+ * with the others, behind the same barrier.  With m_r the largest u_i over the points of segment r with W[i] != 0,
+ * e_i = W[i] exp(u_i - m_r), T_r = sum e_i, p_i = e_i / T_r and mu_r = sigma on row 0, lambda[row - 1] elsewhere:
+ *     value m_r + log T_r,   Jacobian row G[r] = A_r' p,   Hessian of the Lagrangian sum_r mu_r (A_r' diag(p) A_r - G[r] G[r]').
+ * State rules and re-lay as for sqphip_nlp_add_block (SQPHIP_ESTATE once the layout is final); the instance's block grows by
+ *     W [N] | S [N]                                                               (padded to an even count)
+ * and its workspace by 2 N + 2 R + R d doubles (u then p, e then z = mu p, m, T, G).
+ * sqphip_nlp_set_instance_block and sqphip_nlp_stream_set_block serve the block unchanged (weight [N], shift [N]);
+ * sqphip_nlp_stream_set restores the data of this call.
+ * The Jacobian COO of sqphip_create must hold (rows[r], cols[j]) for every output on a row >= 1 and every column; unless
+ * nnzH = 0 the Hessian COO must hold the lower entry of every pair of block columns, the diagonal included.  Where the COO
+ * repeats an entry the first copy owns the slot and the others read 0.
+ * SQPHIP_EINVAL, with sqphip_last_error naming the block and the 1-based output, column, entry or point: a context without an
+ * NLP attach, d outside 1..128, N < 1 or N d too large, a fifth block, null cols or A, R outside 1..N or R d too large, null
+ * rows or seg, seg[0] != 0, seg[R] != N, an empty or decreasing segment, a column out of range or twice, a missing Hessian
+ * entry, a row outside 0..m, a row twice, a row among 1..num_linear, a missing Jacobian entry.
+ * Evaluation (one workgroup per instance; every sum in an order that depends on N, d and seg only, no atomics):
+ *   logits    u_i = 0, u_i = fma(A[i][j], x_cols[j], u_i) for j = 0 .. d - 1, u_i += S[i];
+ *   maxima    wave w owns the outputs w, w + 16, ...: lane l takes the largest u_i over i = seg[r] + l, + 64, ... with W[i] != 0,
+ *             then the xor butterfly 32, 16, .. 1;
+ *   sums      e_i = W[i] exp(u_i - m_r), exactly 0 where W[i] = 0; the same wave sums e_i per lane in rising order, then the
+ *             butterfly, and adds m_r + log T_r to f (row 0) or to g[row - 1].  A call for values alone (the Armijo probe) ends
+ *             here;
+ *   Jacobian  p_i = e_i / T_r; the pairs (r, j), numbered r d + j, are dealt to the sixteen waves: lane l sums p_i A[i][j] over
+ *             i = seg[r] + l, + 64, ..., the butterfly, G[r][j] is kept and added to grad[cols[j]] (row 0) or to the Jacobian
+ *             slot of (rows[r], cols[j]);
+ *   Hessian   lower 16 x 16 tiles on v_mfma_f64_16x16x4_f64, two accumulator chains: four points per instruction in rising
+ *             order, (mu_r p_i) A[i][r'] against A[i][c'] (z = mu p and the product: one rounding each), and four outputs per
+ *             instruction in rising order, (-mu_r) G[r][r'] against G[r][c']; ragged edges as zeros; chain 1 + chain 2 is added
+ *             to the entry's COO slot by one thread.  The two parts are separate sums; their difference is a covariance and
+ *             cancels, and the error bound (tests/nlp_lse_ref.py) is that of their magnitudes added.
+ * Domain: an output whose points all have weight 0, or whose weighted points all underflow, has T = 0: the caller's business.
+ * Logits 300 either side of the middle of a segment give finite results.  Results are bit-reproducible and independent of slot,
+ * neighbours and instance groups.  A context without such a block files the bits it filed before this call existed. */
+int sqphip_nlp_add_lse_block(sqphip_ctx *ctx, int64_t N, int32_t d, const int64_t *cols /* [d] 1-based */,
+                             const double *A /* [N][d] row-major */, int32_t R, const int64_t *rows /* [R] */,
+                             const int64_t *seg /* [R + 1] */, const double *shift /* [N] or NULL: zeros */,
+                             const double *weight /* [N] or NULL: ones */, int32_t *blk_out /* 0-based block number, or NULL */);
 /* Dense data blocks with several outputs: one design matrix, R weight vectors, a target row each.  Output r adds
  *     sum_{i < N} W[r][i] kappa(sum_{j < d} A[i][j] x_{cols[j]} + S[i])
  * to row rows[r]; row 0 is the objective, row i >= 1 a nonlinear constraint row (i > num_linear).  Constraints on the data the

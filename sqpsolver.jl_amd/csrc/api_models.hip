@@ -641,6 +641,49 @@ extern "C" int sqphip_nlp_add_cox_block(sqphip_ctx *h, int64_t N, int32_t d, con
     return nlp_block_commit(h, blk, kb, (long)N, d, (long)N, (long)N, 6 * (long)N + (long)N * d, A, cv, hs, weight, shift, Kb, blk_out);
 }
 
+// a log-sum-exp row block (nlp_lse_dev.hpp): the shape checks of sqphip_nlp_add_cox_block, then the segments, the rows and their
+// Jacobian slots; rows, seg, the output of every point and the slots are uploaded, so R is not capped
+extern "C" int sqphip_nlp_add_lse_block(sqphip_ctx *h, int64_t N, int32_t d, const int64_t *cols, const double *A, int32_t R,
+                                        const int64_t *rows, const int64_t *seg, const double *shift, const double *weight,
+                                        int32_t *blk_out)
+{
+    const std::string who = "sqphip_nlp_add_lse_block";
+    if (!h) return SQPHIP_EINVAL;
+    Ctx &C0 = h->c;
+    int kb; std::string blk;
+    if (int rc = nlp_block_begin(h, who, kb, blk)) return rc;
+    auto fail = [&](const std::string &msg) { C0.err = blk + ": " + msg; return (int)SQPHIP_EINVAL; };
+    if (d < 1 || d > NLP_BLOCK_MAX_D) return fail("d = " + std::to_string(d) + " columns (1.." + std::to_string((int)NLP_BLOCK_MAX_D) + ")");
+    if (N < 1) return fail("N = " + std::to_string(N) + " points (at least 1)");
+    if (N > INT32_MAX / d) return fail("N d = " + std::to_string(N) + " x " + std::to_string(d) + " is too large (N d < 2^31)");
+    if (!cols || !A) return fail("null cols or A");
+    if (R < 1 || R > N) return fail("R = " + std::to_string(R) + " outputs (1.." + std::to_string(N) + ")");
+    if (R > INT32_MAX / d) return fail("R d = " + std::to_string(R) + " x " + std::to_string(d) + " is too large (R d < 2^31)");
+    if (!rows || !seg) return fail("null rows or seg");
+    if (seg[0] != 0) return fail("output 1: seg[0] = " + std::to_string(seg[0]) + " (the first segment starts at point 0)");
+    for (int r = 0; r < R; ++r)
+        if (seg[r + 1] <= seg[r])
+            return fail("output " + std::to_string(r + 1) + ": the segment " + std::to_string(seg[r]) + ".." + std::to_string(seg[r + 1]) +
+                        " is " + (seg[r + 1] == seg[r] ? "empty" : "decreasing"));
+    if (seg[R] != N) return fail("output " + std::to_string(R) + ": seg[R] = " + std::to_string(seg[R]) + " (the last segment ends at N = " + std::to_string(N) + ")");
+    std::vector<int> hs, cv;
+    if (const std::string bad = nlp_block_columns(C0.nl.slots, d, cols, cv, hs); !bad.empty()) return fail(bad);
+    std::vector<int> row((size_t)R), js;
+    if (const std::string bad = nlp_block_rows(C0.nl.slots, C0.d.m, C0.d.nlin, R, rows, cv, row.data(), js); !bad.empty()) return fail(bad);
+    std::vector<int> sg((size_t)R + 1), outp((size_t)N);
+    for (int r = 0; r <= R; ++r) sg[r] = (int)seg[r];
+    for (int r = 0; r < R; ++r)
+        for (int i = sg[r]; i < sg[r + 1]; ++i) outp[i] = r;
+    NlpBlkDev Kb = {};
+    Kb.lse = R;
+    const int rc = guarded(h, [&](Ctx &C) {
+        Kb.lrow = C.upload(row); Kb.seg = C.upload(sg); Kb.outp = C.upload(outp); Kb.js = C.upload(js);
+        return SQPHIP_OK;
+    });
+    if (rc) return rc;
+    return nlp_block_commit(h, blk, kb, (long)N, d, (long)N, (long)N, 2 * (long)N + 2 * (long)R + (long)R * d, A, cv, hs, weight, shift, Kb, blk_out);
+}
+
 // weight / shift of block blk into the block of values v (of an instance or of a scenario of the queue); NULL: kept
 static int nlp_block_put(sqphip_ctx *h, double *v, int32_t blk, const double *weight, const double *shift)
 {

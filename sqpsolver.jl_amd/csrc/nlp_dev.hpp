@@ -46,6 +46,9 @@
 // the same four blocks and adds to gv and jv behind the plan passes as the others add to f, grad and hv.
 // sqphip_nlp_add_cox_block: Cox partial-likelihood blocks sum_i c_i [log sum_{j < risk[i]} W_j exp(u_j) - u_i] couple the points of
 // a block through prefix and suffix scans (nlp_cox_dev.hpp); they count among the same four blocks and add to f, grad and hv.
+// sqphip_nlp_add_lse_block: log-sum-exp row blocks, output r = log sum_{i in segment r} W_i exp(u_i) on the objective or a
+// constraint row, any number of outputs over consecutive segments of the points (nlp_lse_dev.hpp); they count among the same
+// four blocks and add to f, grad, gv, jv and hv.
 #pragma once
 #include "ctx.hpp"
 #include "dev_util.hpp"
@@ -81,6 +84,10 @@ struct NlpBlkDev {
     int cox;
     const int *risk, *first;              // [N] leading points in the risk set of a point; [N] the first point whose risk set holds a point (0-based)
     const double *event;                  // [N] event indicator (0: censored)
+    // a log-sum-exp row block (sqphip_nlp_add_lse_block; nlp_lse_dev.hpp): lse = R != 0 outputs, K = R = cox = 0, ke, par and row
+    // unread; js [lse][d] as above.  wz: u [N] | e [N] | m [lse] | T [lse] | G [lse][d]
+    int lse;
+    const int *lrow, *seg, *outp;         // [lse] target row of an output; [lse + 1] first point of an output; [N] output of a point
 };
 
 struct NlpDev {
@@ -105,7 +112,7 @@ struct NlpDev {
     const double *fpar;                   // [nfac] real exponent of a POWR factor (loaded for that kind only)
     int data;                             // sqphip_nlp_attach_data: b, a, p are the instance's, in its block of DV::nlv at ...
     int ob, oa, op;                       // ... ob [nfac], oa [nargs], op [nfac] (op: with a POWR factor only); fab, acoef, aw, fpar unread
-    int ws;                               // doubles of workspace per instance (DV::nlw): 3 nfac, with blocks + TPB / 64 wave sums + 3 TPB kappa values + a block's own (2 N, Kf N, 3 N, 6 N + N d)
+    int ws;                               // doubles of workspace per instance (DV::nlw): 3 nfac, with blocks + TPB / 64 wave sums + 3 TPB kappa values + a block's own (2 N, Kf N, 3 N, 6 N + N d, 2 N + 2 R + R d)
     int nblk;                             // dense data blocks of the objective (sqphip_nlp_add_block, nlp_block_dev.hpp); uniform over the launch
     NlpBlkDev blk[NLP_MAX_BLOCKS];
 };
@@ -210,6 +217,7 @@ static __device__ __forceinline__ void nlp_factor(int ke, double a, double u, do
 #include "nlp_rowblock_dev.hpp"
 #include "nlp_softmax_dev.hpp"
 #include "nlp_cox_dev.hpp"
+#include "nlp_lse_dev.hpp"
 namespace sqphip {
 
 // the acopf_eval signature; any of f_out, grad, gv, jv, hv may be null.  Called by every thread of the workgroup.

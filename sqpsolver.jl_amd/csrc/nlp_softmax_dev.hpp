@@ -8,7 +8,7 @@
 // nlp_blocks_eval (below) is the one call site for blocks of the kernels that inline nlp_eval: it walks the blocks in block
 // order behind a barrier each and hands a softmax block (NlpBlkDev::K != 0) to nlp_softmax_eval, a block with several outputs
 // (NlpBlkDev::R != 0) to nlp_rowblock_eval (nlp_rowblock_dev.hpp), a Cox block (NlpBlkDev::cox != 0) to nlp_cox_eval
-// (nlp_cox_dev.hpp), any other to nlp_block_eval.
+// (nlp_cox_dev.hpp), a log-sum-exp row block (NlpBlkDev::lse != 0) to nlp_lse_eval (nlp_lse_dev.hpp), any other to nlp_block_eval.
 // One call of nlp_softmax_eval, by every thread of the workgroup:
 //   1. points: thread i % TPB computes u_ik as the scalar blocks do (u = 0, u = fma(At[j][i], x_{col[k][j]}, u) for j rising,
 //      u += S[k][i]) for k = 0 .. Kf - 1 and the maximum m of the logits (the pinned class enters with 0, last); then, with
@@ -170,6 +170,10 @@ static __device__ __noinline__ void nlp_softmax_eval(const NlpBlkDev *bp_, const
 // (nlp_cox_dev.hpp, which uses nlp_softmax_exp and nlp_softmax_log above)
 static __device__ __noinline__ void nlp_cox_eval(const NlpBlkDev *bp_, const double *val_, double *wsp_, double *part_, const double *x_,
                                                  double sigma, double *f_out_, double *grad_, double *hv_);
+// (nlp_lse_dev.hpp, likewise)
+static __device__ __noinline__ void nlp_lse_eval(const NlpBlkDev *bp_, const double *val_, double *wsp_, double *part_, const double *x_,
+                                                 double sigma_, const double *lam_, double *f_out_, double *grad_, double *gv_,
+                                                 double *jv_, double *hv_);
 
 // every block of the context in block order; a barrier in front of each: the plan passes of nlp_eval and an earlier block wrote
 // f, grad and hv entries that this block adds to from other threads.  Out of line, pointers and scalars only: the kernels that
@@ -194,6 +198,7 @@ static __device__ __noinline__ void nlp_blocks_eval(const NlpBlkDev *blk_, int n
         __syncthreads();
         if (__builtin_amdgcn_readfirstlane(blk[k].K) != 0) nlp_softmax_eval(blk + k, val, wsp, part, x, sigma, f_out, grad, hv);      // uniform over the launch
         else if (__builtin_amdgcn_readfirstlane(blk[k].cox) != 0) nlp_cox_eval(blk + k, val, wsp, part, x, sigma, f_out, grad, hv);
+        else if (__builtin_amdgcn_readfirstlane(blk[k].lse) != 0) nlp_lse_eval(blk + k, val, wsp, part, x, sigma, lam, f_out, grad, gv, jv, hv);
         else if (__builtin_amdgcn_readfirstlane(blk[k].R) != 0) nlp_rowblock_eval(blk + k, val, wsp, part, x, sigma, lam, f_out, grad, gv, jv, hv);
         else nlp_block_eval(blk + k, val, wsp, part, x, sigma, f_out, grad, hv);
     }

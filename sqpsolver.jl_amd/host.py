@@ -591,9 +591,21 @@ class Context:
         """One dense data block of the objective (sqphip_nlp_add_block; b: nlp_terms.NlpBlock); before the first sqp_reset,
         sqp_run or nlp_stream_begin.  Returns its number.  An nlp_terms.NlpSoftmaxBlock goes through
         sqphip_nlp_add_softmax_block, an nlp_terms.NlpRowBlock (several outputs, constraint rows) through
-        sqphip_nlp_add_row_block."""
-        from .nlp_terms import NlpCoxBlock, NlpRowBlock, NlpSoftmaxBlock
-        if isinstance(b, NlpCoxBlock):                # (sqphip_nlp_add_cox_block)
+        sqphip_nlp_add_row_block, an nlp_terms.NlpCoxBlock through sqphip_nlp_add_cox_block, an nlp_terms.NlpLseBlock
+        (log-sum-exp rows) through sqphip_nlp_add_lse_block."""
+        from .nlp_terms import NlpCoxBlock, NlpLseBlock, NlpRowBlock, NlpSoftmaxBlock
+        if isinstance(b, NlpLseBlock):                # (sqphip_nlp_add_lse_block)
+            if not hasattr(self.L, "sqphip_nlp_add_lse_block"):
+                raise SqpHipError("libsqphip.so lacks sqphip_nlp_add_lse_block: rebuild it")
+            A = _f(np.atleast_2d(b.A))
+            rows = np.ascontiguousarray(b.rows, dtype=np.int64)
+            out = C.c_int32(-1)
+            self._ck(self.L.sqphip_nlp_add_lse_block(self.h, A.shape[0], A.shape[1], _l(np.ascontiguousarray(b.cols, dtype=np.int64)),
+                                                     _d(A), len(rows), _l(rows), _l(np.ascontiguousarray(b.seg, dtype=np.int64)),
+                                                     _d(None if b.shift is None else _f(b.shift)),
+                                                     _d(None if b.weight is None else _f(b.weight)), C.byref(out)))
+            return out.value
+        if isinstance(b, NlpCoxBlock):               # (sqphip_nlp_add_cox_block)
             if not hasattr(self.L, "sqphip_nlp_add_cox_block"):
                 raise SqpHipError("libsqphip.so lacks sqphip_nlp_add_cox_block: rebuild it")
             A = _f(np.atleast_2d(b.A))

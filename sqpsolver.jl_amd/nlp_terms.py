@@ -43,9 +43,14 @@ plain affine factors.  Twice inside one factor stays an error.  SQRT and POWR ne
                          the objective), sum_i w_ri kappa(A_i'x_cols + b_i) added to row r (sqphip_nlp_add_row_block)
     NlpCoxBlock          a Cox partial-likelihood data block (survival data, Breslow ties), sum_i w_i event_i [log sum_{j < risk_i}
                          w_j exp(u_j) - u_i] over points sorted by non-increasing time (sqphip_nlp_add_cox_block)
+    NlpLseBlock          a log-sum-exp row block: output r = log sum_{i in segment r} w_i exp(A_i'x_cols + b_i) added to row r, any
+                         number of outputs over consecutive segments of the points (sqphip_nlp_add_lse_block)
     block_eval           value, gradient and dense Hessian of the blocks of a problem in numpy
     row_block_eval       ... of its blocks with several outputs: the rows' values and Jacobian rows too, the Hessian of the
                          Lagrangian with sigma and lam
+    lse_block_eval       ... of its log-sum-exp row blocks, likewise
+    geometric_program_model, gp_synth, gp_scenario     a geometric programme in log variables as one log-sum-exp row block; a
+                         seeded one; its scenarios (other log-coefficients)
     neyman_pearson_model, rate_constrained_logistic_model     constraints on the data the objective is fitted to, as row blocks
     multinomial_block_model  ridge-regularised K-class logistic regression as one softmax block plus terms
     cox_risk, cox_block_model  the risk sets of sorted times; ridge-regularised Cox regression as one Cox block plus terms
@@ -174,6 +179,53 @@ class NlpCoxBlock:
 
 
 @dataclasses.dataclass
+class NlpLseBlock:
+    """Output r adds log sum_{i in segment r} weight_i exp(u_i), u_i = sum_j A[i, j] x_{cols[j]} + shift_i, to row rows[r] (0: the
+    objective, i: row i, a nonlinear one): the log-sum-exp of the consecutive points seg[r] .. seg[r + 1] - 1 (seg[0] = 0,
+    seg[R] = N, every segment at least one point), R = len(rows) distinct target rows, 1 <= R <= N.  cols d distinct 1-based
+    variables in any order (d <= 128), A [N, d]; shift [N] None: zeros (the log-coefficients of the monomials), weight [N] >= 0
+    None: ones (0 removes a monomial)."""
+    cols: np.ndarray
+    A: np.ndarray
+    rows: np.ndarray
+    seg: np.ndarray
+    shift: np.ndarray | None = None
+    weight: np.ndarray | None = None
+
+    def __post_init__(self):
+        self.cols = _i64(np.atleast_1d(self.cols))
+        self.A = _f64(np.atleast_2d(self.A))
+        self.rows = _i64(np.atleast_1d(self.rows))
+        self.seg = _i64(np.atleast_1d(self.seg))
+        N, d = self.A.shape
+        R = len(self.rows)
+        if not 1 <= d <= MAX_BLOCK_COLS:
+            raise ValueError(f"d = {d} columns (1..{MAX_BLOCK_COLS})")
+        if N < 1:
+            raise ValueError(f"N = {N} points (at least 1)")
+        if len(self.cols) != d or len(np.unique(self.cols)) != d:
+            raise ValueError(f"cols: {d} distinct variables")
+        if not 1 <= R <= N:
+            raise ValueError(f"R = {R} outputs (1..{N})")
+        if self.seg.shape != (R + 1,):
+            raise ValueError(f"seg: R + 1 = {R + 1} values")
+        if self.seg[0] != 0:
+            raise ValueError(f"output 1: seg[0] = {int(self.seg[0])} (the first segment starts at point 0)")
+        if np.any(np.diff(self.seg) <= 0):
+            r = int(np.argmax(np.diff(self.seg) <= 0))
+            raise ValueError(f"output {r + 1}: the segment {int(self.seg[r])}..{int(self.seg[r + 1])} is "
+                             + ("empty" if self.seg[r + 1] == self.seg[r] else "decreasing"))
+        if self.seg[R] != N:
+            raise ValueError(f"output {R}: seg[R] = {int(self.seg[R])} (the last segment ends at N = {N})")
+        if len(np.unique(self.rows)) != R:
+            raise ValueError("a row is the target of two outputs of the block")
+        self.shift = np.zeros(N) if self.shift is None else _f64(self.shift)
+        self.weight = np.ones(N) if self.weight is None else _f64(self.weight)
+        if self.shift.shape != (N,) or self.weight.shape != (N,):
+            raise ValueError(f"shift and weight: {N} values each")
+
+
+@dataclasses.dataclass
 class NlpRowBlock:
     """Output r adds sum_{i < N} weight[r, i] kappa(sum_j A[i, j] x_{cols[j]} + shift_i) to row rows[r] (0: the objective, i: row
     i, a nonlinear one): one design matrix, R = len(rows) <= 8 distinct target rows.  kind, cols, A, exp, par as in NlpBlock;
@@ -229,7 +281,7 @@ class NlpTerms:
     fpar: np.ndarray | None = None     # [nfac] real exponent of a POWR factor (0 elsewhere); None: no POWR factor
     general: bool = False              # written for sqphip_nlp_attach_general (make_nlp_terms: needs_general); False: a model
                                        # of the older calls, which keep refusing what they refuse
-    blocks: list = dataclasses.field(default_factory=list)     # NlpBlock, NlpSoftmaxBlock, NlpRowBlock, NlpCoxBlock: dense data blocks (at most 4)
+    blocks: list = dataclasses.field(default_factory=list)     # NlpBlock, NlpSoftmaxBlock, NlpRowBlock, NlpCoxBlock, NlpLseBlock: dense data blocks (at most 4)
 
     @property
     def affine(self) -> bool:
@@ -302,9 +354,9 @@ def make_nlp_terms(n, m, num_linear, terms, g0=None, f0=0.0, xL=None, xU=None, g
     if len(p.blocks) > MAX_BLOCKS:
         raise ValueError(f"{len(p.blocks)} blocks (at most {MAX_BLOCKS})")
     for k, b in enumerate(p.blocks):
-        if isinstance(b, (NlpSoftmaxBlock, NlpRowBlock, NlpCoxBlock)) and (b.cols.min() < 1 or b.cols.max() > n):
+        if isinstance(b, (NlpSoftmaxBlock, NlpRowBlock, NlpCoxBlock, NlpLseBlock)) and (b.cols.min() < 1 or b.cols.max() > n):
             raise ValueError(f"block {k + 1}: a column outside 1..{n}")
-        if isinstance(b, NlpRowBlock):
+        if isinstance(b, (NlpRowBlock, NlpLseBlock)):
             if b.rows.min() < 0 or b.rows.max() > m:
                 raise ValueError(f"block {k + 1}: a row outside 0..{m}")
             if np.any((b.rows >= 1) & (b.rows <= num_linear)):
@@ -329,7 +381,7 @@ def nlp_terms_layout(p: NlpTerms) -> NlpTermsLayout:
     inrow = rows > 0
     jk = [(rows[inrow] - 1) * n + (avar[inrow] - 1)]
     for b in getattr(p, "blocks", []):
-        if isinstance(b, NlpRowBlock):
+        if isinstance(b, (NlpRowBlock, NlpLseBlock)):
             jk += [(i - 1) * n + (b.cols - 1) for i in b.rows.tolist() if i >= 1]
     jkey = np.unique(np.concatenate(jk))
     hk = []
@@ -702,11 +754,12 @@ def _cox_eval(b: NlpCoxBlock, x):
 
 def block_eval(p: NlpTerms, x, blocks=None):
     """(f, grad [n], H [n, n]) of the blocks of p at x: sum_i w_i kappa(u_i), A'(w kappa'), A' diag(w kappa'') A scattered to
-    the blocks' columns.  Blocks with several outputs (NlpRowBlock) are row_block_eval's, not counted here."""
+    the blocks' columns.  Blocks with several outputs (NlpRowBlock) are row_block_eval's and log-sum-exp row blocks (NlpLseBlock)
+    lse_block_eval's, not counted here."""
     x = _f64(x)
     f, g, H = 0.0, np.zeros(p.n), np.zeros((p.n, p.n))
     for b in (p.blocks if blocks is None else blocks):
-        if isinstance(b, NlpRowBlock):
+        if isinstance(b, (NlpRowBlock, NlpLseBlock)):
             continue
         if isinstance(b, NlpSoftmaxBlock):
             fb, gb, Hb = _softmax_eval(b, x)
@@ -753,6 +806,114 @@ def row_block_eval(p: NlpTerms, x, sigma=1.0, lam=None, blocks=None):
             e += (float(sigma) if i == 0 else lam[i - 1]) * b.weight[r]
         H[np.ix_(c, c)] += b.A.T @ ((e * k2)[:, None] * b.A)
     return f, g, gv, J, H
+
+
+def lse_block_eval(p: NlpTerms, x, sigma=1.0, lam=None, blocks=None):
+    """(f, grad [n], g [m], J [m, n], H [n, n]) of the log-sum-exp row blocks of p at x: what they add to the objective, its
+    gradient, the rows' values and Jacobian rows, and to the Hessian of the Lagrangian, sum_r mu_r (A_r' diag(p) A_r - G_r G_r')
+    with mu_r = sigma for row 0 and lam[i - 1] for row i (lam None: zeros).  The logits of a segment are shifted by the largest
+    among its points of non-zero weight; a zero-weight point contributes exactly 0 and its exponential is never formed."""
+    x = _f64(x)
+    lam = np.zeros(p.m) if lam is None else _f64(lam)
+    f, g, gv, J, H = 0.0, np.zeros(p.n), np.zeros(p.m), np.zeros((p.m, p.n)), np.zeros((p.n, p.n))
+    for b in (p.blocks if blocks is None else blocks):
+        if not isinstance(b, NlpLseBlock):
+            continue
+        c = b.cols - 1
+        u = b.A @ x[c] + b.shift
+        for r, i in enumerate(b.rows.tolist()):
+            s0, s1 = int(b.seg[r]), int(b.seg[r + 1])
+            on = b.weight[s0:s1] != 0.0
+            Ar, ur, wr = b.A[s0:s1][on], u[s0:s1][on], b.weight[s0:s1][on]
+            with np.errstate(all="ignore"):
+                mr = ur.max() if len(ur) else -np.inf
+                e = wr * np.exp(ur - mr)
+                T = e.sum()
+                pr = e / T
+                val = float(mr + np.log(T))
+            Gr = Ar.T @ pr
+            mu = float(sigma) if i == 0 else lam[i - 1]
+            if i == 0:
+                f += val
+                np.add.at(g, c, Gr)
+            else:
+                gv[i - 1] += val
+                np.add.at(J[i - 1], c, Gr)
+            H[np.ix_(c, c)] += mu * (Ar.T @ (pr[:, None] * Ar) - np.outer(Gr, Gr))
+    return f, g, gv, J, H
+
+
+def geometric_program_model(n, posynomials, monomial_rows=None, bounds=(-np.inf, np.inf), ridge=0.0, x0=None) -> NlpTerms:
+    """A geometric programme in the log variables x = log y:
+        min  log P_0(e^x) + ridge sum_j x_j^2   s.t.  log P_k(e^x) <= 0 (k >= 1),   a_l'x + log c_l = 0,   lo <= x <= hi.
+    posynomials: [(coefs [k] > 0, exponents [k, n])], number 0 the objective, every other one a row log-sum-exp <= 0.  All
+    of them are one NlpLseBlock on the variables in use: its points are the monomials, its shifts the log-coefficients, so the
+    scenarios of one programme differ in the shifts only (gp_scenario).  monomial_rows: [(coef > 0, exponents [n])], the monomial
+    equalities c prod y^a = 1, which are linear in x: they go to the num_linear leading rows of the terms.  bounds (lo, hi):
+    scalars or [n].  From x0 (None: zeros)."""
+    n = int(n)
+    mono = list(monomial_rows or [])
+    nl, K = len(mono), len(posynomials)
+    if K < 1:
+        raise ValueError("geometric_program_model: the objective posynomial is missing")
+    A, S, seg = [], [], [0]
+    for k, (c, E) in enumerate(posynomials):
+        c, E = _f64(np.atleast_1d(c)), _f64(np.atleast_2d(E))
+        if E.shape != (len(c), n) or len(c) < 1:
+            raise ValueError(f"posynomial {k}: coefficients [k] and exponents [k, {n}]")
+        if not np.all(c > 0) or not np.all(np.isfinite(c)):
+            raise ValueError(f"posynomial {k}: a coefficient is not positive and finite")
+        A.append(E); S.append(np.log(c)); seg.append(seg[-1] + len(c))
+    A, S = np.vstack(A), np.concatenate(S)
+    used = np.flatnonzero(np.any(A != 0.0, axis=0))
+    if len(used) == 0:
+        used = np.arange(1)
+    rows = [0] + [nl + k for k in range(1, K)]
+    blk = NlpLseBlock(used + 1, A[:, used], rows, seg, S)
+    m = nl + K - 1
+    terms, g0 = [], np.zeros(m)
+    for l, (c, a) in enumerate(mono):
+        a = _f64(np.atleast_1d(a))
+        if a.shape != (n,) or not float(c) > 0:
+            raise ValueError(f"monomial row {l + 1}: a positive coefficient and exponents [{n}]")
+        terms += [(l + 1, float(a[j]), [(j + 1, POW)]) for j in np.flatnonzero(a)]
+        g0[l] = np.log(float(c))
+    if ridge:
+        terms += [(0, float(ridge), [(j + 1, POW, 2)]) for j in range(n)]
+    lo, hi = bounds
+    gL = np.concatenate([np.zeros(nl), np.full(K - 1, -np.inf)])
+    return make_nlp_terms(n, m, nl, terms, g0=g0, xL=np.broadcast_to(_f64(lo), (n,)).copy(), xU=np.broadcast_to(_f64(hi), (n,)).copy(),
+                          gL=gL, gU=np.zeros(m), x0=np.zeros(n) if x0 is None else x0, blocks=[blk])
+
+
+def gp_synth(n: int, lens, seed: int = 1) -> NlpTerms:
+    """A seeded geometric programme on n log variables: lens[0] monomials in the objective, lens[k] in constraint k.  The
+    exponents lie on the half-integer grid round(2 U(-2, 2)) / 2 with about 40 % non-zeros (a monomial left empty gets one);
+    the coefficients are exp(0.5 N(0, 1)), normalised so that every constraint posynomial is 0.5 at x = 0 (x = 0 is strictly
+    feasible) and the objective 1.  A ridge 1e-3 x_j^2 on every variable stays in the terms; -3 <= x <= 3, from x = 0."""
+    rng = np.random.default_rng(int(seed))
+    n = int(n)
+    pos = []
+    for k, K in enumerate(lens):
+        E = np.round(2.0 * rng.uniform(-2.0, 2.0, (int(K), n))) / 2.0
+        E *= rng.random((int(K), n)) < 0.4
+        for i in np.flatnonzero(~np.any(E != 0.0, axis=1)):
+            E[i, rng.integers(n)] = 1.0 if rng.random() < 0.5 else -1.0
+        c = np.exp(0.5 * rng.standard_normal(int(K)))
+        pos.append((c * ((1.0 if k == 0 else 0.5) / c.sum()), E))
+    return geometric_program_model(n, pos, bounds=(-3.0, 3.0), ridge=1e-3)
+
+
+def gp_scenario(p: NlpTerms, s: int, seed: int = 1, noise: float = 0.05) -> NlpTerms:
+    """Scenario s of a geometric programme (s = 0 or noise = 0: p itself): every log-coefficient of its log-sum-exp row blocks
+    moved by noise N(0, 1) -- prices, loads, process corners.  Structure, bounds and start stay."""
+    if s == 0 or noise == 0:
+        return p
+    rng = np.random.default_rng(int(seed) * 1000 + int(s))
+    out = dataclasses.replace(p)
+    out.blocks = [dataclasses.replace(b, shift=b.shift + noise * rng.standard_normal(len(b.shift))) if isinstance(b, NlpLseBlock) else b
+                  for b in p.blocks]
+    return out
 
 
 def fold_weights(N: int, k: int) -> np.ndarray:
