@@ -95,6 +95,16 @@ int sqphip_kkt_dense_test(sqphip_ctx *ctx, const int32_t *active, const double *
                           const double *dw_last, const int32_t *fac_attempt, const double *rhs, double sentinel,
                           double *K_assembled, double *xv_loaded, int32_t *xv_mismatch, double *sol, double *dinv,
                           double *dinv_pad, int32_t *decision, double *dw_out);
+/* The working vector of the solves by the two routines of the one-workgroup stages, on a context of either solver: the column
+ * walk (load_solve_vector) and the entry-parallel terms in LDS (solve_vector_terms, what build_rhs runs where the context has
+ * the stage).  Inputs per instance, back to back: Jval [B][nnzJ], Dd / rtype [B][m], rhs [B][n + m] = [g; b].  Every instance
+ * with active[b] != 0 is built by both; xv of every instance is preset to SQPHIP_SOLVE_VECTOR_SENTINEL before each, which is
+ * what an inactive instance comes back with.  xv_plain / xv_terms [B][Fpad] (may be null); *mismatch: entries whose bits differ.
+ * SQPHIP_ESTATE where the context runs without the stage (options.kkt_condense = 0, SQPHIP_NO_VSTAGE, SQPHIP_XV_TERMS=0, a
+ * structure whose stage does not fit).  Leaves every instance idle. */
+#define SQPHIP_SOLVE_VECTOR_SENTINEL (-7.5)
+int sqphip_solve_vector_test(sqphip_ctx *ctx, const int32_t *active, const double *Jval, const double *Dd, const int32_t *rtype,
+                             const double *rhs, double *xv_plain, double *xv_terms, int32_t *mismatch);
 /* Launch census of the multifrontal path: launches enqueued per kernel instantiation (factor, solve, inertia test) since the
  * context was created.  counts[cap]; names (may be null): cap x 64 characters; *n_kernels = number of instantiations. */
 int sqphip_mf_census(const sqphip_ctx *ctx, int64_t *counts, char *names, int32_t cap, int32_t *n_kernels);

@@ -475,6 +475,14 @@ extern "C" int sqphip_create(sqphip_ctx **out, int64_t n, int64_t m, int64_t num
             d.vstage = 0;
             d.fH = C.dalloc<double>(Bn); d.fJt = C.dalloc<double>(Bn); d.fJ = C.dalloc<double>(Bm); d.fX = C.dalloc<double>(Bm);
         }
+        // the working vector of the condensed form from entry-parallel terms in LDS (ipm.hip, solve_vector_terms): where the
+        // vector stages are on and its stage fits the 160 KB of a workgroup beside the static LDS of the reductions (8 KB kept
+        // back); SQPHIP_XV_TERMS=0 leaves the column walk of load_solve_vector (cross-check, A / B runs; read once, here)
+        d.xstage = 0;
+        if (d.vstage && d.condense && !(getenv("SQPHIP_XV_TERMS") && atoi(getenv("SQPHIP_XV_TERMS")) == 0)) {
+            const size_t xs = xv_terms_doubles(d);
+            if (8 * xs <= 152 * 1024 && (8 * xs <= 64 * 1024 || ipm_device_setup(C))) d.xstage = (int)xs;
+        }
         d.tol_direction = opt->tol_direction; d.tol_residual = opt->tol_residual;
         d.tol_infeas = opt->tol_infeas; d.init_mu = opt->init_mu; d.tr_size = opt->tr_size;
         d.max_iter = opt->max_iter; d.use_soc = opt->use_soc; d.literal_quirks = opt->literal_quirks;
@@ -830,6 +838,57 @@ extern "C" int sqphip_kkt_dense_test(sqphip_ctx *h, const int32_t *active, const
             }
             if (dw_out) dw_out[b] = st[b].dw;
         }
+        return SQPHIP_OK;
+    });
+}
+
+// The working vector of the solves by both routines of the one-workgroup stages, on a sparse or a dense context: every instance
+// with active[b] != 0 gets its Jacobian values, D, row types and full-length right-hand side and goes to PH_FACTOR; xv is preset
+// to SQPHIP_SOLVE_VECTOR_SENTINEL, built by load_solve_vector (k_load_solve_vector_test) and copied out, preset again, built by solve_vector_terms
+// behind a stage filled from the same arrays (k_solve_vector_terms_test) and copied out.  *mismatch: entries whose bits differ.
+// SQPHIP_ESTATE where the context runs without the stage (DV::xstage == 0).  Leaves every instance idle.
+extern "C" int sqphip_solve_vector_test(sqphip_ctx *h, const int32_t *active, const double *Jval, const double *Dd,
+                                        const int32_t *rtype, const double *rhs, double *xv_plain, double *xv_terms,
+                                        int32_t *mismatch)
+{
+    if (!h || !active || !Jval || !Dd || !rtype || !rhs) return SQPHIP_EINVAL;
+    if (h->c.d.xstage == 0) { h->c.err = "sqphip_solve_vector_test: the context builds the working vector without the LDS stage (xstage = 0)"; return SQPHIP_ESTATE; }
+    return guarded(h, [&](Ctx &C) {
+        DV &d = C.d;
+        const int B = d.B;
+        const size_t BF = (size_t)B * d.Fpad;
+        for (int b = 0; b < B; ++b) {
+            const size_t om = (size_t)b * d.m;
+            h2d(C, d.jcoo + (size_t)b * d.nnzj_coo, Jval + (size_t)b * d.nnzj_coo, d.nnzj_coo);
+            SQPHIP_HIP_OK(hipMemsetAsync(d.hcoo + (size_t)b * d.nnzh_coo, 0, sizeof(double) * (size_t)d.nnzh_coo, C.stream));
+            h2d(C, d.Dd + om, Dd + om, d.m);
+            SQPHIP_HIP_OK(hipMemcpyAsync(d.rtype + om, rtype + om, sizeof(int) * (size_t)d.m, hipMemcpyHostToDevice, C.stream));
+            h2d(C, d.rhs + (size_t)b * d.Npad, rhs + (size_t)b * d.N, d.N);
+            hipLaunchKernelGGL(k_mf_inst_set, dim3(1), dim3(64), 0, C.stream, d, b, active[b] ? 1 : 0, (int)PH_IDLE, 0.0, 0.0, 0.0, 0);
+        }
+        launch_qp_gather(C);                       // COO -> CSC values of the active instances (start flag set, stage 0)
+        for (int b = 0; b < B; ++b)
+            hipLaunchKernelGGL(k_mf_inst_set, dim3(1), dim3(64), 0, C.stream, d, b, 0, active[b] ? (int)PH_FACTOR : (int)PH_IDLE,
+                               0.0, 0.0, 0.0, 0);
+        const std::vector<double> fill(BF, SQPHIP_SOLVE_VECTOR_SENTINEL);
+        std::vector<double> xa(BF), xb(BF);
+        h2d(C, d.xv, fill.data(), BF);
+        launch_load_xv_test(C, false);
+        d2h(C, xa.data(), d.xv, BF);
+        h2d(C, d.xv, fill.data(), BF);
+        launch_xv_terms_test(C);
+        d2h(C, xb.data(), d.xv, BF);
+        for (int b = 0; b < B; ++b)
+            hipLaunchKernelGGL(k_mf_inst_set, dim3(1), dim3(64), 0, C.stream, d, b, 0, (int)PH_IDLE, 0.0, 0.0, 0.0, 0);
+        SQPHIP_HIP_OK(hipStreamSynchronize(C.stream));
+        SQPHIP_HIP_OK(hipGetLastError());
+        if (mismatch) {
+            int bad = 0;
+            for (size_t k = 0; k < BF; ++k) bad += std::memcmp(&xa[k], &xb[k], sizeof(double)) != 0;
+            *mismatch = bad;
+        }
+        if (xv_plain) std::copy(xa.begin(), xa.end(), xv_plain);
+        if (xv_terms) std::copy(xb.begin(), xb.end(), xv_terms);
         return SQPHIP_OK;
     });
 }

@@ -174,6 +174,7 @@ struct DV {
     double ipm_tol;
     int ipm_max_iter, ipm_phase1, ipm_corrector, ipm_warm;
     int side;                             // 0: transitions in line; 1: this launch is a transition kernel on the side stream; 2: a main kernel beside it
+    int xstage;                           // doubles of dynamic LDS of the entry-parallel solve vector (ipm.hip, solve_vector_terms; 0: off)
     double refine_tol;                    // refinement step when the relative residual is above this (condensed form)
     int vstage;                           // doubles of dynamic LDS of the vector stages (n + N; 0: the vectors do not fit, ipm.hip)
     int hfull;                            // 1: the Hessian pattern is completely dense (n^2 entries of the full symmetric CSC): hess_row reads column k at row j (ipm.hip)
@@ -315,6 +316,9 @@ void sqp_stream_rearm(Ctx &C);        // ... slots that found the queue empty lo
 void launch_qp_gather(Ctx &C);       // COO -> CSC for instances with start set (stage 0)
 void launch_kkt_assemble(Ctx &C);     // k_kkt_assemble over the batch (dense path: the sweep and sqphip_kkt_dense_test)
 void launch_load_xv_test(Ctx &C, bool flat_kernel);   // test hook: the working vector of the solves by k_sp_load_xv or by load_solve_vector
+size_t xv_terms_doubles(const DV &d);  // dynamic LDS (doubles) the entry-parallel solve vector needs for the structure (solve_vector_terms)
+bool ipm_device_setup(Ctx &C);        // the stage kernels granted 160 KB of dynamic LDS on the context's device (DV::xstage past 64 KB)
+void launch_xv_terms_test(Ctx &C);    // test hook: the working vector of the PH_FACTOR instances from d.rhs by solve_vector_terms
 // comm.hip
 void comm_release(Ctx &C);
 // mfront.hip

@@ -19,7 +19,9 @@
 #include "dev_util.hpp"
 #include "mf_dev.hpp"
 #include "sqp_dev.hpp"
+#include <algorithm>
 #include <cmath>
+#include <mutex>
 
 #ifndef SQPHIP_VEC_FUSE
 #define SQPHIP_VEC_FUSE 1      // rows of H v / J v formed inside the loops that consume them (0: separate passes + barrier)
@@ -36,11 +38,20 @@ extern __shared__ double ipm_lds[];
 
 // shader-clock stamps inside the vector stages (instance 0, thread 0; scripts/gpu_mf_trace.py builds with -DSQPHIP_MF_TRACE)
 #ifdef SQPHIP_MF_TRACE
-__device__ long long g_vec_trace[64];
-#define VTR(i) if (blockIdx.x == 0 && threadIdx.x == 0) g_vec_trace[i] = (long long)clock64();
+// g_vec_trace[i]: the last stamp i; [64 + i] / [128 + i]: cycles summed over / number of the segments that ended at stamp i
+// (from whichever stamp the thread passed before it; one instance group only: every group has a workgroup 0); [192], [193]: that
+// stamp and its index (scripts/gpu_post_stamps.py prints the averages)
+__device__ long long g_vec_trace[194];
+#define VTR(i) if (blockIdx.x == 0 && threadIdx.x == 0) { const long long vtr_t = (long long)clock64(); g_vec_trace[i] = vtr_t; \
+        g_vec_trace[64 + (i)] += vtr_t - g_vec_trace[192]; g_vec_trace[128 + (i)] += 1; g_vec_trace[192] = vtr_t; g_vec_trace[193] = (i); }
+// ... a stamp that is summed only when the stamp passed before it was `prev` (a stamp several paths lead to)
+#define VTR_AFTER(i, prev) if (blockIdx.x == 0 && threadIdx.x == 0) { const long long vtr_t = (long long)clock64(); g_vec_trace[i] = vtr_t; \
+        if (g_vec_trace[193] == (prev)) { g_vec_trace[64 + (i)] += vtr_t - g_vec_trace[192]; g_vec_trace[128 + (i)] += 1; } g_vec_trace[192] = vtr_t; g_vec_trace[193] = (i); }
 extern "C" int sqphip_vec_trace_read(long long *out) { return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_vec_trace), sizeof(long long) * 64); }
+extern "C" int sqphip_vec_trace_sums(long long *out) { return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_vec_trace), sizeof(long long) * 193); }
 #else
 #define VTR(i)
+#define VTR_AFTER(i, prev)
 #endif
 
 #define RHO_BIG0 1e4
@@ -625,6 +636,104 @@ __global__ __launch_bounds__(TPB) void k_load_solve_vector_test(DV d)
     load_solve_vector(d, inst, d.rhs + (long)inst * d.Npad, d.xv + (long)inst * d.Fpad);
 }
 
+// The working vector of the condensed form from entry-parallel terms (DV::xstage).  solve_vector_at
+// walks the column of a variable through global memory, two dependent round trips per pair of entries, and the workgroup
+// lasts as long as the thread that owns the longest column (42 entries on the IEEE-118 shape, mean 5.6).  Here the right-hand
+// side, D and the "row is eliminated" flags are staged in LDS by the caller (XvStage), and the vector is built in two phases:
+//   1  one entry of the Jacobian per thread and trip (coalesced jv / jrowval, the gathers from LDS): its term
+//      jk * si / (Di + reg) -- the expression of solve_vector_at, so the same bits whichever thread forms it: the division
+//      comes last and nothing fuses into it -- goes to T[k], and whether the entry is added at all to one bit of a ballot word
+//      per 64 consecutive entries (a skipped entry stays skipped: v + 0.0 turns -0.0 into +0.0);
+//   2  one position per thread and trip: v = the source entry solve_vector_at starts from, then v += T[k] over the column's
+//      entries, k ascending, where the bit is set -- the order of solve_vector_at -- out of LDS.
+// One barrier between the two, LDS only.  The stage overlays the gathered vectors of b_refine / b_ipm_prepare (ipm_lds): the
+// callers of build_rhs have a barrier behind the last read of those.
+struct XvStage {
+    double *srhs, *sD, *T;                // [N] the right-hand side [g; b], [m] D, [nnzjc] the terms
+    unsigned long long *bits;             // [ceil(nnzjc / 64)] entry k is added: bit k & 63 of word k >> 6
+    unsigned char *sE;                    // [m] row is eliminated and not free: its entries are added
+};
+__device__ __forceinline__ XvStage xv_stage(const DV &d)
+{
+    XvStage s;
+    s.srhs = ipm_lds; s.sD = s.srhs + d.N; s.T = s.sD + d.m;
+    s.bits = reinterpret_cast<unsigned long long *>(s.T + d.nnzjc);
+    s.sE = reinterpret_cast<unsigned char *>(s.bits + (d.nnzjc + 63) / 64);
+    return s;
+}
+#ifndef XV_TERMS_PER_THREAD
+#define XV_TERMS_PER_THREAD 6             // entries a thread holds in registers per trip of phase 1 (6 x 1 024 covers the IEEE-118 shape)
+#endif
+#ifndef XV_POS_PER_THREAD
+#define XV_POS_PER_THREAD 3               // positions a thread serves per trip of phase 2 (their index loads issued together)
+#endif
+__device__ __forceinline__ void solve_vector_terms(const DV &d, const double *jv, const XvStage &s, double *xv)
+{
+    const int nnz = d.nnzjc, tid = threadIdx.x;
+    for (int kb = 0; kb < nnz; kb += XV_TERMS_PER_THREAD * TPB) {
+        double jk[XV_TERMS_PER_THREAD];
+        int ri[XV_TERMS_PER_THREAD];
+#pragma unroll
+        for (int r = 0; r < XV_TERMS_PER_THREAD; ++r) {          // (every load of the trip before the first use)
+            const int k = kb + r * TPB + tid;
+            jk[r] = k < nnz ? jv[k] : 0.0;
+            ri[r] = k < nnz ? d.jrowval[k] : -1;
+        }
+#pragma unroll
+        for (int r = 0; r < XV_TERMS_PER_THREAD; ++r) {
+            const int k = kb + r * TPB + tid, i = ri[r];
+            const bool add = i >= 0 && s.sE[i] != 0;
+            if (add) s.T[k] = jk[r] * s.srhs[d.n + i] / (s.sD[i] + IPM_REG_D);
+            // (kb, r * TPB and the wave's first thread are multiples of 64: the 64 lanes hold the entries of one word)
+            const unsigned long long w = __ballot(add);
+            if ((tid & 63) == 0 && k < nnz) s.bits[k >> 6] = w;
+        }
+    }
+    VTR(46)
+    __syncthreads();
+    VTR(47)
+    for (int pb = 0; pb < d.Fpad; pb += XV_POS_PER_THREAD * TPB) {
+        int u[XV_POS_PER_THREAD], k0[XV_POS_PER_THREAD], k1[XV_POS_PER_THREAD];
+#pragma unroll
+        for (int r = 0; r < XV_POS_PER_THREAD; ++r) {
+            const int p = pb + r * TPB + tid;
+            u[r] = p < d.Fpad ? d.uinv[p] : -1;
+        }
+#pragma unroll
+        for (int r = 0; r < XV_POS_PER_THREAD; ++r) {            // a kept row: k0 = its row, no entries; a variable: its column
+            k0[r] = 0; k1[r] = 0;
+            if (u[r] >= d.n) k0[r] = d.krow[u[r] - d.n];
+            else if (u[r] >= 0) { k0[r] = d.jcolptr[u[r]]; k1[r] = d.jcolptr[u[r] + 1]; }
+        }
+#pragma unroll
+        for (int r = 0; r < XV_POS_PER_THREAD; ++r) {
+            const int p = pb + r * TPB + tid;
+            double v = 0.0;                                           // identity padding
+            if (u[r] >= d.n) v = s.srhs[d.n + k0[r]];
+            else if (u[r] >= 0) {
+                v = s.srhs[u[r]];
+                for (int k = k0[r]; k < k1[r]; ++k)
+                    if ((s.bits[k >> 6] >> (k & 63)) & 1ull) v += s.T[k];
+            }
+            if (p < d.Fpad) xv[p] = v;
+        }
+    }
+}
+// test hook (sqphip_solve_vector_test): the stage from d.rhs / d.Dd / d.rtype of every instance about to be factorised, then
+// the routine build_rhs runs
+__global__ __launch_bounds__(TPB) void k_solve_vector_terms_test(DV d)
+{
+    const int inst = blockIdx.x;
+    if (d.phase[inst] != PH_FACTOR) return;
+    const XvStage s = xv_stage(d);
+    const double *rhs = d.rhs + (long)inst * d.Npad, *Dd = d.Dd + (long)inst * d.m;
+    const int *rt = d.rtype + (long)inst * d.m;
+    for (int i = threadIdx.x; i < d.N; i += TPB) s.srhs[i] = rhs[i];
+    for (int i = threadIdx.x; i < d.m; i += TPB) { s.sD[i] = Dd[i]; s.sE[i] = rt[i] != ROW_FREE && d.kpos[i] < 0; }
+    __syncthreads();
+    solve_vector_terms(d, d.jv + (long)inst * d.nnzjc, s, d.xv + (long)inst * d.Fpad);
+}
+
 // Newton right-hand side for centring target tgt (minus the second-order terms when soc), its working copy xv
 // for the triangular solves, sol = 0.  Returns max |rhs| (block-wide).
 __device__ __forceinline__ double build_rhs(const DV &d, int inst, double tgt, bool soc)
@@ -632,6 +741,10 @@ __device__ __forceinline__ double build_rhs(const DV &d, int inst, double tgt, b
     INST_PTRS
     SOC_PTRS
     double rn = 0.0;
+    // the working vector from entry-parallel terms (solve_vector_terms): g, b, D and the row flags also go to LDS here
+    const bool terms = d.xstage != 0 && d.condense && !d.flat;
+    const XvStage xs = xv_stage(d);
+    VTR(40)
     for (int j = threadIdx.x; j < d.n; j += TPB) {
         const double rdj = rd[j], lbj = lb[j], ubj = ub[j], pj = p[j], zlj = zl[j], zuj = zu[j];
         const double sl = SOCV(sZL, j), su = SOCV(sZU, j);
@@ -639,12 +752,16 @@ __device__ __forceinline__ double build_rhs(const DV &d, int inst, double tgt, b
         if (fin(lbj)) { const double gl = pj - lbj; g += (tgt - sl - zlj * gl) / gl; }
         if (fin(ubj)) { const double gu = ubj - pj; g -= (tgt - su - zuj * gu) / gu; }
         rhs[j] = g; rn = fmax(rn, fabs(g));
+        if (terms) xs.srhs[j] = g;
     }
     for (int i = threadIdx.x; i < d.m; i += TPB) {
         const int rti = rt[i];
         const double zp = zpv[i], zm = zmv[i], tpi = tp[i], tmi = tm[i], rpi = rp[i], si = s[i], loi = lo[i], hii = hi[i],
                      vli = vl[i], vui = vu[i];
         const double sp_ = SOCV(sZP, i), sm_ = SOCV(sZM, i), svl = SOCV(sVL, i), svu = SOCV(sVU, i);
+        // (D is read here, not taken from b_ipm_prepare: an instance that retries after a failed inertia test comes without it)
+        const double Ddi = terms ? Dd[i] : 0.0;
+        const int kpi = terms ? d.kpos[i] : 0;
         double b = 0.0;
         if (rti != ROW_FREE) {
             const double cp = tgt - sp_ - zp * tpi, cm = tgt - sm_ - zm * tmi;
@@ -657,10 +774,16 @@ __device__ __forceinline__ double build_rhs(const DV &d, int inst, double tgt, b
             }
         }
         rhs[d.n + i] = b; rn = fmax(rn, fabs(b));
+        if (terms) { xs.srhs[d.n + i] = b; xs.sD[i] = Ddi; xs.sE[i] = rti != ROW_FREE && kpi < 0; }
     }
-    rn = block_reduce<OpMax>(rn);        // (its barriers also publish rhs to the whole workgroup)
+    VTR(41)
+    rn = block_reduce<OpMax>(rn);        // (its barriers also publish rhs, and the LDS stage, to the whole workgroup)
+    VTR(42)
     for (int i = threadIdx.x; i < d.Npad; i += TPB) sol[i] = 0.0;
-    if (!d.flat) load_solve_vector(d, inst, rhs, d.xv + (long)inst * d.Fpad);       // (flat: k_sp_load_xv behind this kernel)
+    VTR(43)
+    if (terms) solve_vector_terms(d, jv, xs, d.xv + (long)inst * d.Fpad);
+    else if (!d.flat) load_solve_vector(d, inst, rhs, d.xv + (long)inst * d.Fpad);       // (flat: k_sp_load_xv behind this kernel)
+    VTR(44)
     return rn;
 }
 
@@ -1124,6 +1247,7 @@ __global__ __launch_bounds__(TPB, SQPHIP_VEC_WAVES_PER_EU) void k_ipm_tail(DV d,
 static __device__ __forceinline__ void b_sweep_count(const DV &d, int *host_slot)
 {
     __syncthreads();                 // the state words of this instance are final
+    VTR_AFTER(45, 44)                // (behind a barrier: the whole workgroup is through the working vector, not thread 0 alone)
     if (threadIdx.x != 0) return;
     const int inst = blockIdx.x;
     const SqpState &S = d.sst[inst];
@@ -1315,6 +1439,39 @@ void launch_load_xv_test(Ctx &C, bool flat_kernel)
     else hipLaunchKernelGGL(k_load_solve_vector_test, dim3(C.d.B), dim3(TPB), 0, C.stream, C.d);
 }
 
+// ... and by solve_vector_terms behind a stage filled from the same arrays (sqphip_solve_vector_test)
+void launch_xv_terms_test(Ctx &C)
+{
+    hipLaunchKernelGGL(k_solve_vector_terms_test, dim3(C.d.B), dim3(TPB), 8 * (size_t)C.d.xstage, C.stream, C.d);
+}
+
+// dynamic LDS of solve_vector_terms for the structure, in doubles: the layout of xv_stage
+size_t xv_terms_doubles(const DV &d)
+{
+    return (size_t)d.N + d.m + d.nnzjc + (d.nnzjc + 63) / 64 + (d.m + 7) / 8;
+}
+
+// The stage of solve_vector_terms passes 64 KB on the IEEE-118 shape: every kernel ipm_sweep launches with the stage's size
+// gets the attribute on the context's device, once per context, as mf_device_setup does for the front kernels: 152 KB, the bound
+// the stage is held to (sqphip_create) -- these kernels have static LDS of their own (the reductions), and the device refuses
+// a dynamic size that does not fit beside it.  False: the device did not grant it (the caller then leaves the stage off).
+bool ipm_device_setup(Ctx &C)
+{
+    static std::mutex mu;
+    std::lock_guard<std::mutex> lk(mu);
+    bool ok = true;
+    auto big = [&](const void *f) { ok &= hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 152 * 1024) == hipSuccess; };
+    big(reinterpret_cast<const void *>(k_ipm_head)); big(reinterpret_cast<const void *>(k_ipm_rhs));
+    big(reinterpret_cast<const void *>(k_ipm_mid)); big(reinterpret_cast<const void *>(k_ipm_tail));
+    big(reinterpret_cast<const void *>(k_ipm_post<PH_SOLVE, true>)); big(reinterpret_cast<const void *>(k_ipm_post<PH_SOLVE, false>));
+    big(reinterpret_cast<const void *>(k_ipm_post<PH_RESOLVE, true>)); big(reinterpret_cast<const void *>(k_ipm_post<PH_RESOLVE, false>));
+    big(reinterpret_cast<const void *>(k_ipm_post_ride));
+    big(reinterpret_cast<const void *>(k_solve_vector_terms_test));
+    (void)hipGetLastError();
+    (void)C;
+    return ok;
+}
+
 void launch_qp_gather(Ctx &C)
 {
     hipLaunchKernelGGL(k_qp_gather, dim3(C.d.B), dim3(TPB), 0, C.stream, C.d);
@@ -1344,7 +1501,7 @@ bool ipm_sweep(Ctx &C, bool sqp_level, int *host_slot)
     hipStream_t s = C.stream;
     const dim3 gB(d.B), bT(TPB);
     C.n_sweeps++;
-    const size_t vlds = 8 * (size_t)d.vstage;
+    const size_t vlds = 8 * (size_t)std::max(d.vstage, d.xstage);     // (the stage of solve_vector_terms overlays the gathered vectors)
     // Transitions between sub-problems -- k_qp_finish, the stage kernel of run!, the start of the next sub-problem in
     // k_ipm_head -- concern three or four of the 128 instances of a group in any one sweep, and each of these kernels
     // lasts as long as its slowest instance (20 + 95 + 120 us against ~25 us for the right-hand sides of everybody else):

@@ -463,6 +463,22 @@ class Context:
         return {"K": K.transpose(0, 2, 1), "xv": xv, "xv_mismatch": int(mis.value), "sol": sol, "dinv": dinv,
                 "dinv_pad": dpad, "decision": dec, "dw": dwo}
 
+    SOLVE_VECTOR_SENTINEL = -7.5          # SQPHIP_SOLVE_VECTOR_SENTINEL (include/sqphip_test_hooks.h)
+
+    def solve_vector_test(self, active, jval, Dd, rtype, rhs):
+        """The working vector of the solves by both routines (`sqphip_solve_vector_test`), on a sparse or a dense context;
+        per-instance inputs stacked as [B, ...], rhs [B, n + m].  Returns (xv_plain, xv_terms, mismatch): the vector by the
+        column walk and by the entry-parallel terms, each [B, Fpad] (Fpad: the order of the factorised matrix padded to 64)
+        with SOLVE_VECTOR_SENTINEL where nothing was written, and the number of entries whose bits differ.  Raises
+        SqpHipError (state) where the context runs without the LDS stage."""
+        rhs = _f(rhs); B = rhs.shape[0]
+        Fpad = (self.counters()["kkt_order"] + 63) // 64 * 64
+        xa = np.zeros((B, Fpad)); xb = np.zeros((B, Fpad)); mis = C.c_int32(-1)
+        act = np.ascontiguousarray(active, dtype=np.int32); rt = np.ascontiguousarray(rtype, dtype=np.int32)
+        self._ck(self.L.sqphip_solve_vector_test(self.h, _i(act), _d(_f(jval)), _d(_f(Dd)), _i(rt), _d(rhs), _d(xa), _d(xb),
+                                                 C.byref(mis)))
+        return xa, xb, int(mis.value)
+
     def mf_census(self):
         """Launch census of the multifrontal path (`sqphip_mf_census`): {kernel instantiation: launches enqueued}."""
         nk = C.c_int32()
