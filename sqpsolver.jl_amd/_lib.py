@@ -13,7 +13,7 @@ if os.environ.get("SQPHIP_SO"):        # experiment aid: another build of the li
     SO_PATH = os.path.abspath(os.environ["SQPHIP_SO"])
 SOURCES = ["ldlt.hip", "kernel_api.hip", "ipm.hip", "acopf.hip", "sqp.hip", "api.hip", "api_models.hip", "model_plans.cpp", "order.hip",
            "symbolic.hip", "mfplan.hip", "mf_select.cpp", "mfront.hip", "comm.hip"]
-HEADERS = ["sqphip_internal.hpp", "ctx.hpp", "api_util.hpp", "model_plans.hpp", "sparse.hpp", "mf_kernels.hpp", "mf_select.hpp", "dev_util.hpp", "mf_dev.hpp", "sqp_dev.hpp", "acopf_dev.hpp", "qcqp_dev.hpp", "nlp_dev.hpp", "nlp_block_dev.hpp", "nlp_rowblock_dev.hpp", "nlp_softmax_dev.hpp", "nlp_cox_dev.hpp", "nlp_lse_dev.hpp", os.path.join("..", "..", "include", "sqphip.h"),
+HEADERS = ["sqphip_internal.hpp", "ctx.hpp", "api_util.hpp", "model_plans.hpp", "sparse.hpp", "mf_kernels.hpp", "mf_select.hpp", "dev_util.hpp", "mf_dev.hpp", "sqp_dev.hpp", "acopf_dev.hpp", "qcqp_dev.hpp", "nlp_dev.hpp", "nlp_blocks_dev.hpp", "nlp_block_dev.hpp", "nlp_rowblock_dev.hpp", "nlp_softmax_dev.hpp", "nlp_cox_dev.hpp", "nlp_lse_dev.hpp", os.path.join("..", "..", "include", "sqphip.h"),
            os.path.join("..", "..", "include", "sqphip_test_hooks.h")]
 
 _lib = None

@@ -437,10 +437,11 @@ extern "C" int sqphip_nlp_set_instance(sqphip_ctx *h, int32_t inst, const double
     });
 }
 
-// ---- dense data blocks of the objective of a factorable NLP (nlp_block_dev.hpp, nlp_softmax_dev.hpp)
+// ---- dense data blocks of a factorable NLP (nlp_blocks_dev.hpp, the five family headers, nlp_blocks_eval of nlp_dev.hpp)
 // the state rules of the add calls; kb: the number of the block to be, blk: "who: block kb + 1" for the messages
 static int nlp_block_begin(sqphip_ctx *h, const std::string &who, int &kb, std::string &blk)
 {
+    if (!h) return SQPHIP_EINVAL;
     Ctx &C0 = h->c;
     if (!C0.d.nlp) { C0.err = who + ": the context has no factorable NLP attached (sqphip_nlp_attach*)"; return SQPHIP_EINVAL; }
     if (C0.nl.started) {
@@ -503,12 +504,29 @@ static int nlp_block_commit(sqphip_ctx *h, const std::string &blk, int kb, long 
     });
 }
 
+// The opening of an add call: the null handle and the state rules (begin), and the refusal "who: block k: msg" (fail)
+struct NlpBlockAdd {
+    sqphip_ctx *h;
+    int kb = 0;
+    std::string blk;
+    int begin(const char *who) { return nlp_block_begin(h, who, kb, blk); }
+    int fail(const std::string &msg) const { h->c.err = blk + ": " + msg; return (int)SQPHIP_EINVAL; }
+};
+
+// what every add call refuses of N points on d columns, of which it takes max_d at most (the softmax block, which has checked
+// its own Kf d, passes d)
+static std::string nlp_block_shape(int64_t N, int32_t d, int max_d)
+{
+    if (d < 1 || d > max_d) return "d = " + std::to_string(d) + " columns (1.." + std::to_string(max_d) + ")";
+    if (N < 1) return "N = " + std::to_string(N) + " points (at least 1)";
+    if (N > INT32_MAX / d) return "N d = " + std::to_string(N) + " x " + std::to_string(d) + " is too large (N d < 2^31)";
+    return "";
+}
+
 // what sqphip_nlp_add_block and sqphip_nlp_add_row_block refuse of the shape and the menu entry; e: the exponent in use
 static std::string nlp_block_menu(int32_t kind, int32_t exp, double par, int64_t N, int32_t d, const int64_t *cols, const double *A, int &e)
 {
-    if (d < 1 || d > NLP_BLOCK_MAX_D) return "d = " + std::to_string(d) + " columns (1.." + std::to_string((int)NLP_BLOCK_MAX_D) + ")";
-    if (N < 1) return "N = " + std::to_string(N) + " points (at least 1)";
-    if (N > INT32_MAX / d) return "N d = " + std::to_string(N) + " x " + std::to_string(d) + " is too large (N d < 2^31)";
+    if (const std::string bad = nlp_block_shape(N, d, NLP_BLOCK_MAX_D); !bad.empty()) return bad;
     if (!cols || !A) return "null cols or A";
     if (kind < NLP_POW || kind > NLP_POWR) return "unknown kind " + std::to_string(kind);
     e = kind == NLP_POW ? exp : 1;
@@ -521,21 +539,18 @@ static std::string nlp_block_menu(int32_t kind, int32_t exp, double par, int64_t
 extern "C" int sqphip_nlp_add_block(sqphip_ctx *h, int32_t kind, int32_t exp, double par, int64_t N, int32_t d, const int64_t *cols,
                                     const double *A, const double *shift, const double *weight, int32_t *blk_out)
 {
-    const std::string who = "sqphip_nlp_add_block";
-    if (!h) return SQPHIP_EINVAL;
+    NlpBlockAdd call{h};
+    if (int rc = call.begin("sqphip_nlp_add_block")) return rc;
     Ctx &C0 = h->c;
-    int kb; std::string blk;
-    if (int rc = nlp_block_begin(h, who, kb, blk)) return rc;
-    auto fail = [&](const std::string &msg) { C0.err = blk + ": " + msg; return (int)SQPHIP_EINVAL; };
     int e;
-    if (const std::string bad = nlp_block_menu(kind, exp, par, N, d, cols, A, e); !bad.empty()) return fail(bad);
+    if (const std::string bad = nlp_block_menu(kind, exp, par, N, d, cols, A, e); !bad.empty()) return call.fail(bad);
     std::vector<int> hs, cv;
-    const std::string bad = nlp_block_columns(C0.nl.slots, d, cols, cv, hs);
-    if (!bad.empty()) return fail(bad);
+    if (const std::string bad = nlp_block_columns(C0.nl.slots, d, cols, cv, hs); !bad.empty()) return call.fail(bad);
     NlpBlkDev K = {};
+    K.family = NLP_BLK_SCALAR;
     K.ke = kind + (e + 32) * (1 << NLP_KIND_BITS);
     K.par = kind == NLP_POWR ? par : 0.0;
-    return nlp_block_commit(h, blk, kb, (long)N, d, (long)N, (long)N, 2 * (long)N, A, cv, hs, weight, shift, K, blk_out);
+    return nlp_block_commit(h, call.blk, call.kb, (long)N, d, (long)N, (long)N, nlp_block_ws(N).size, A, cv, hs, weight, shift, K, blk_out);
 }
 
 // a block with several outputs (nlp_rowblock_dev.hpp): the checks of sqphip_nlp_add_block, then the rows and their Jacobian slots
@@ -543,28 +558,26 @@ extern "C" int sqphip_nlp_add_row_block(sqphip_ctx *h, int32_t kind, int32_t exp
                                         const double *A, int32_t R, const int64_t *rows, const double *shift, const double *weight,
                                         int32_t *blk_out)
 {
-    const std::string who = "sqphip_nlp_add_row_block";
-    if (!h) return SQPHIP_EINVAL;
+    NlpBlockAdd call{h};
+    if (int rc = call.begin("sqphip_nlp_add_row_block")) return rc;
     Ctx &C0 = h->c;
-    int kb; std::string blk;
-    if (int rc = nlp_block_begin(h, who, kb, blk)) return rc;
-    auto fail = [&](const std::string &msg) { C0.err = blk + ": " + msg; return (int)SQPHIP_EINVAL; };
     int e;
-    if (const std::string bad = nlp_block_menu(kind, exp, par, N, d, cols, A, e); !bad.empty()) return fail(bad);
-    if (R < 1 || R > NLP_BLOCK_MAX_R) return fail("R = " + std::to_string(R) + " outputs (1.." + std::to_string((int)NLP_BLOCK_MAX_R) + ")");
-    if (!rows) return fail("null rows");
-    if (N > INT32_MAX / R) return fail("R N = " + std::to_string(R) + " x " + std::to_string(N) + " is too large (R N < 2^31)");
+    if (const std::string bad = nlp_block_menu(kind, exp, par, N, d, cols, A, e); !bad.empty()) return call.fail(bad);
+    if (R < 1 || R > NLP_BLOCK_MAX_R) return call.fail("R = " + std::to_string(R) + " outputs (1.." + std::to_string((int)NLP_BLOCK_MAX_R) + ")");
+    if (!rows) return call.fail("null rows");
+    if (N > INT32_MAX / R) return call.fail("R N = " + std::to_string(R) + " x " + std::to_string(N) + " is too large (R N < 2^31)");
     std::vector<int> hs, cv;
-    if (const std::string bad = nlp_block_columns(C0.nl.slots, d, cols, cv, hs); !bad.empty()) return fail(bad);
+    if (const std::string bad = nlp_block_columns(C0.nl.slots, d, cols, cv, hs); !bad.empty()) return call.fail(bad);
     NlpBlkDev K = {};
     std::vector<int> js;
-    if (const std::string bad = nlp_block_rows(C0.nl.slots, C0.d.m, C0.d.nlin, R, rows, cv, K.row, js); !bad.empty()) return fail(bad);
+    if (const std::string bad = nlp_block_rows(C0.nl.slots, C0.d.m, C0.d.nlin, R, rows, cv, K.row, js); !bad.empty()) return call.fail(bad);
+    K.family = NLP_BLK_ROWS;
     K.ke = kind + (e + 32) * (1 << NLP_KIND_BITS);
     K.par = kind == NLP_POWR ? par : 0.0;
     K.R = R;
     const int rc = guarded(h, [&](Ctx &C) { K.js = C.upload(js); return SQPHIP_OK; });
     if (rc) return rc;
-    return nlp_block_commit(h, blk, kb, (long)N, d, (long)R * N, (long)N, 3 * (long)N, A, cv, hs, weight, shift, K, blk_out);
+    return nlp_block_commit(h, call.blk, call.kb, (long)N, d, (long)R * N, (long)N, nlp_rowblock_ws(N).size, A, cv, hs, weight, shift, K, blk_out);
 }
 
 // a multinomial (softmax) block (nlp_softmax_dev.hpp)
@@ -572,58 +585,48 @@ extern "C" int sqphip_nlp_add_softmax_block(sqphip_ctx *h, int64_t N, int32_t d,
                                             const double *A, const int32_t *labels, const double *shift, const double *weight,
                                             int32_t *blk_out)
 {
-    const std::string who = "sqphip_nlp_add_softmax_block";
-    if (!h) return SQPHIP_EINVAL;
+    NlpBlockAdd call{h};
+    if (int rc = call.begin("sqphip_nlp_add_softmax_block")) return rc;
     Ctx &C0 = h->c;
-    int kb; std::string blk;
-    if (int rc = nlp_block_begin(h, who, kb, blk)) return rc;
-    auto fail = [&](const std::string &msg) { C0.err = blk + ": " + msg; return (int)SQPHIP_EINVAL; };
-    if (K < 2 || K > NLP_SOFTMAX_MAX_K) return fail("K = " + std::to_string(K) + " classes (2.." + std::to_string((int)NLP_SOFTMAX_MAX_K) + ")");
-    if (d < 1) return fail("d = " + std::to_string(d) + " features (at least 1)");
+    if (K < 2 || K > NLP_SOFTMAX_MAX_K) return call.fail("K = " + std::to_string(K) + " classes (2.." + std::to_string((int)NLP_SOFTMAX_MAX_K) + ")");
+    if (d < 1) return call.fail("d = " + std::to_string(d) + " features (at least 1)");
     const int Kf = pinned ? K - 1 : K;
     if ((long)Kf * d > NLP_BLOCK_MAX_D)
-        return fail("Kf d = " + std::to_string(Kf) + " x " + std::to_string(d) + " columns (at most " + std::to_string((int)NLP_BLOCK_MAX_D) + ")");
-    if (N < 1) return fail("N = " + std::to_string(N) + " points (at least 1)");
-    if (N > INT32_MAX / d) return fail("N d = " + std::to_string(N) + " x " + std::to_string(d) + " is too large (N d < 2^31)");
-    if (!cols || !A || !labels) return fail("null cols, A or labels");
+        return call.fail("Kf d = " + std::to_string(Kf) + " x " + std::to_string(d) + " columns (at most " + std::to_string((int)NLP_BLOCK_MAX_D) + ")");
+    if (const std::string bad = nlp_block_shape(N, d, d); !bad.empty()) return call.fail(bad);
+    if (!cols || !A || !labels) return call.fail("null cols, A or labels");
     for (int64_t i = 0; i < N; ++i)
         if (labels[i] < 0 || labels[i] >= K)
-            return fail("point " + std::to_string(i + 1) + ": label " + std::to_string(labels[i]) + " outside 0.." + std::to_string(K - 1));
+            return call.fail("point " + std::to_string(i + 1) + ": label " + std::to_string(labels[i]) + " outside 0.." + std::to_string(K - 1));
     std::vector<int> hs, cv;
-    const std::string bad = nlp_block_columns(C0.nl.slots, Kf * d, cols, cv, hs);
-    if (!bad.empty()) return fail(bad);
+    if (const std::string bad = nlp_block_columns(C0.nl.slots, Kf * d, cols, cv, hs); !bad.empty()) return call.fail(bad);
     NlpBlkDev Kb = {};
+    Kb.family = NLP_BLK_SOFTMAX;
     Kb.K = K; Kb.Kf = Kf;
     const int rc = guarded(h, [&](Ctx &C) { Kb.y = C.upload(std::vector<int>(labels, labels + N)); return SQPHIP_OK; });
     if (rc) return rc;
-    return nlp_block_commit(h, blk, kb, (long)N, d, (long)N, (long)Kf * N, (long)Kf * N, A, cv, hs, weight, shift, Kb, blk_out);
+    return nlp_block_commit(h, call.blk, call.kb, (long)N, d, (long)N, (long)Kf * N, nlp_softmax_ws(N, Kf).size, A, cv, hs, weight, shift, Kb, blk_out);
 }
 
 // a Cox partial-likelihood block (nlp_cox_dev.hpp): the shape checks of sqphip_nlp_add_block, then risk and event
 extern "C" int sqphip_nlp_add_cox_block(sqphip_ctx *h, int64_t N, int32_t d, const int64_t *cols, const double *A, const int32_t *risk,
                                         const double *event, const double *shift, const double *weight, int32_t *blk_out)
 {
-    const std::string who = "sqphip_nlp_add_cox_block";
-    if (!h) return SQPHIP_EINVAL;
+    NlpBlockAdd call{h};
+    if (int rc = call.begin("sqphip_nlp_add_cox_block")) return rc;
     Ctx &C0 = h->c;
-    int kb; std::string blk;
-    if (int rc = nlp_block_begin(h, who, kb, blk)) return rc;
-    auto fail = [&](const std::string &msg) { C0.err = blk + ": " + msg; return (int)SQPHIP_EINVAL; };
-    if (d < 1 || d > NLP_BLOCK_MAX_D) return fail("d = " + std::to_string(d) + " columns (1.." + std::to_string((int)NLP_BLOCK_MAX_D) + ")");
-    if (N < 1) return fail("N = " + std::to_string(N) + " points (at least 1)");
-    if (N > INT32_MAX / d) return fail("N d = " + std::to_string(N) + " x " + std::to_string(d) + " is too large (N d < 2^31)");
-    if (!cols || !A || !risk || !event) return fail("null cols, A, risk or event");
+    if (const std::string bad = nlp_block_shape(N, d, NLP_BLOCK_MAX_D); !bad.empty()) return call.fail(bad);
+    if (!cols || !A || !risk || !event) return call.fail("null cols, A, risk or event");
     for (int64_t i = 0; i < N; ++i) {
         if (risk[i] < i + 1 || risk[i] > N)
-            return fail("point " + std::to_string(i + 1) + ": risk " + std::to_string(risk[i]) + " outside " + std::to_string(i + 1) + ".." + std::to_string(N));
+            return call.fail("point " + std::to_string(i + 1) + ": risk " + std::to_string(risk[i]) + " outside " + std::to_string(i + 1) + ".." + std::to_string(N));
         if (i > 0 && risk[i] < risk[i - 1])
-            return fail("point " + std::to_string(i + 1) + ": risk " + std::to_string(risk[i]) + " decreases from " + std::to_string(risk[i - 1]));
+            return call.fail("point " + std::to_string(i + 1) + ": risk " + std::to_string(risk[i]) + " decreases from " + std::to_string(risk[i - 1]));
         if (!std::isfinite(event[i]) || event[i] < 0.0)
-            return fail("point " + std::to_string(i + 1) + ": event " + std::to_string(event[i]) + " (finite and not negative)");
+            return call.fail("point " + std::to_string(i + 1) + ": event " + std::to_string(event[i]) + " (finite and not negative)");
     }
     std::vector<int> hs, cv;
-    const std::string bad = nlp_block_columns(C0.nl.slots, d, cols, cv, hs);
-    if (!bad.empty()) return fail(bad);
+    if (const std::string bad = nlp_block_columns(C0.nl.slots, d, cols, cv, hs); !bad.empty()) return call.fail(bad);
     // first[j]: the first point whose risk set holds point j; risk is non-decreasing, so these points are i >= first[j]
     std::vector<int> fst((size_t)N);
     for (int64_t j = 0, i = 0; j < N; ++j) {
@@ -631,14 +634,14 @@ extern "C" int sqphip_nlp_add_cox_block(sqphip_ctx *h, int64_t N, int32_t d, con
         fst[j] = (int)i;
     }
     NlpBlkDev Kb = {};
-    Kb.cox = 1;
+    Kb.family = NLP_BLK_COX;
     const int rc = guarded(h, [&](Ctx &C) {
         Kb.risk = C.upload(std::vector<int>(risk, risk + N)); Kb.first = C.upload(fst);
         Kb.event = C.upload(std::vector<double>(event, event + N));
         return SQPHIP_OK;
     });
     if (rc) return rc;
-    return nlp_block_commit(h, blk, kb, (long)N, d, (long)N, (long)N, 6 * (long)N + (long)N * d, A, cv, hs, weight, shift, Kb, blk_out);
+    return nlp_block_commit(h, call.blk, call.kb, (long)N, d, (long)N, (long)N, nlp_cox_ws(N, d).size, A, cv, hs, weight, shift, Kb, blk_out);
 }
 
 // a log-sum-exp row block (nlp_lse_dev.hpp): the shape checks of sqphip_nlp_add_cox_block, then the segments, the rows and their
@@ -647,41 +650,37 @@ extern "C" int sqphip_nlp_add_lse_block(sqphip_ctx *h, int64_t N, int32_t d, con
                                         const int64_t *rows, const int64_t *seg, const double *shift, const double *weight,
                                         int32_t *blk_out)
 {
-    const std::string who = "sqphip_nlp_add_lse_block";
-    if (!h) return SQPHIP_EINVAL;
+    NlpBlockAdd call{h};
+    if (int rc = call.begin("sqphip_nlp_add_lse_block")) return rc;
     Ctx &C0 = h->c;
-    int kb; std::string blk;
-    if (int rc = nlp_block_begin(h, who, kb, blk)) return rc;
-    auto fail = [&](const std::string &msg) { C0.err = blk + ": " + msg; return (int)SQPHIP_EINVAL; };
-    if (d < 1 || d > NLP_BLOCK_MAX_D) return fail("d = " + std::to_string(d) + " columns (1.." + std::to_string((int)NLP_BLOCK_MAX_D) + ")");
-    if (N < 1) return fail("N = " + std::to_string(N) + " points (at least 1)");
-    if (N > INT32_MAX / d) return fail("N d = " + std::to_string(N) + " x " + std::to_string(d) + " is too large (N d < 2^31)");
-    if (!cols || !A) return fail("null cols or A");
-    if (R < 1 || R > N) return fail("R = " + std::to_string(R) + " outputs (1.." + std::to_string(N) + ")");
-    if (R > INT32_MAX / d) return fail("R d = " + std::to_string(R) + " x " + std::to_string(d) + " is too large (R d < 2^31)");
-    if (!rows || !seg) return fail("null rows or seg");
-    if (seg[0] != 0) return fail("output 1: seg[0] = " + std::to_string(seg[0]) + " (the first segment starts at point 0)");
+    if (const std::string bad = nlp_block_shape(N, d, NLP_BLOCK_MAX_D); !bad.empty()) return call.fail(bad);
+    if (!cols || !A) return call.fail("null cols or A");
+    if (R < 1 || R > N) return call.fail("R = " + std::to_string(R) + " outputs (1.." + std::to_string(N) + ")");
+    if (R > INT32_MAX / d) return call.fail("R d = " + std::to_string(R) + " x " + std::to_string(d) + " is too large (R d < 2^31)");
+    if (!rows || !seg) return call.fail("null rows or seg");
+    if (seg[0] != 0) return call.fail("output 1: seg[0] = " + std::to_string(seg[0]) + " (the first segment starts at point 0)");
     for (int r = 0; r < R; ++r)
         if (seg[r + 1] <= seg[r])
-            return fail("output " + std::to_string(r + 1) + ": the segment " + std::to_string(seg[r]) + ".." + std::to_string(seg[r + 1]) +
-                        " is " + (seg[r + 1] == seg[r] ? "empty" : "decreasing"));
-    if (seg[R] != N) return fail("output " + std::to_string(R) + ": seg[R] = " + std::to_string(seg[R]) + " (the last segment ends at N = " + std::to_string(N) + ")");
+            return call.fail("output " + std::to_string(r + 1) + ": the segment " + std::to_string(seg[r]) + ".." + std::to_string(seg[r + 1]) +
+                             " is " + (seg[r + 1] == seg[r] ? "empty" : "decreasing"));
+    if (seg[R] != N) return call.fail("output " + std::to_string(R) + ": seg[R] = " + std::to_string(seg[R]) + " (the last segment ends at N = " + std::to_string(N) + ")");
     std::vector<int> hs, cv;
-    if (const std::string bad = nlp_block_columns(C0.nl.slots, d, cols, cv, hs); !bad.empty()) return fail(bad);
+    if (const std::string bad = nlp_block_columns(C0.nl.slots, d, cols, cv, hs); !bad.empty()) return call.fail(bad);
     std::vector<int> row((size_t)R), js;
-    if (const std::string bad = nlp_block_rows(C0.nl.slots, C0.d.m, C0.d.nlin, R, rows, cv, row.data(), js); !bad.empty()) return fail(bad);
+    if (const std::string bad = nlp_block_rows(C0.nl.slots, C0.d.m, C0.d.nlin, R, rows, cv, row.data(), js); !bad.empty()) return call.fail(bad);
     std::vector<int> sg((size_t)R + 1), outp((size_t)N);
     for (int r = 0; r <= R; ++r) sg[r] = (int)seg[r];
     for (int r = 0; r < R; ++r)
         for (int i = sg[r]; i < sg[r + 1]; ++i) outp[i] = r;
     NlpBlkDev Kb = {};
-    Kb.lse = R;
+    Kb.family = NLP_BLK_LSE;
+    Kb.R = R;
     const int rc = guarded(h, [&](Ctx &C) {
         Kb.lrow = C.upload(row); Kb.seg = C.upload(sg); Kb.outp = C.upload(outp); Kb.js = C.upload(js);
         return SQPHIP_OK;
     });
     if (rc) return rc;
-    return nlp_block_commit(h, blk, kb, (long)N, d, (long)N, (long)N, 2 * (long)N + 2 * (long)R + (long)R * d, A, cv, hs, weight, shift, Kb, blk_out);
+    return nlp_block_commit(h, call.blk, call.kb, (long)N, d, (long)N, (long)N, nlp_lse_ws(N, R, d).size, A, cv, hs, weight, shift, Kb, blk_out);
 }
 
 // weight / shift of block blk into the block of values v (of an instance or of a scenario of the queue); NULL: kept

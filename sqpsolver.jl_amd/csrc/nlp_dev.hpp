@@ -38,8 +38,8 @@
 // inside a branch on NlpDev::nblk that is uniform over the launch: a context without a block runs the passes above and
 // nothing else, on the workspace stride NlpDev::ws = 3 nfac it always had.
 // sqphip_nlp_add_softmax_block: multinomial blocks sum_i W_i [log sum_k exp(u_ik) - u_{i, y_i}] count among the same four
-// blocks; nlp_eval's one call for blocks is nlp_blocks_eval (nlp_softmax_dev.hpp), which walks the blocks in block order and
-// hands each to nlp_block_eval or nlp_softmax_eval.
+// blocks; nlp_eval's one call for blocks is nlp_blocks_eval (below), which walks the blocks in block order and
+// hands each to the evaluator of its family (NlpBlkDev::family).
 // sqphip_nlp_add_row_block: a block with R <= 8 outputs, one weight vector and one target row each (row 0: the objective), on
 // one design matrix: sum_i W_r[i] kappa(A_i'x + S_i) is added to row r's value, A'(W_r kappa') to its Jacobian row and
 // A' diag(kappa'' sum_r mu_r W_r) A to the Hessian of the Lagrangian in one MFMA pass (nlp_rowblock_dev.hpp).  It counts among
@@ -59,35 +59,35 @@ namespace sqphip {
 // (the kinds NLP_POW .. NLP_POWR and NLP_KIND_BITS / _MASK: model_plans.hpp, shared with the host-side plan builder)
 enum { NLP_NONE = -(1 << 30), NLP_ARG = (1 << 28) - 1 };     // no factor of a term; the argument bits of a plan entry (nargs <= 2^28)
 
-// a dense data block of the objective (sqphip_nlp_add_block; evaluator: nlp_block_dev.hpp, included below)
+// a dense data block (the sqphip_nlp_add_*_block calls; the shared steps, the evaluators and their dispatcher: included below)
 enum { NLP_MAX_BLOCKS = 4, NLP_BLOCK_MAX_D = 128, NLP_SOFTMAX_MAX_K = 64, NLP_BLOCK_MAX_R = 8 };
+// the family of a block, set by its add call and read by nlp_blocks_eval: sqphip_nlp_add_block, _row_block, _softmax_block,
+// _cox_block, _lse_block
+enum { NLP_BLK_SCALAR, NLP_BLK_ROWS, NLP_BLK_SOFTMAX, NLP_BLK_COX, NLP_BLK_LSE };
 
 struct NlpBlkDev {
-    int ke, N, d;                         // kind + 16 * (exponent + 32) as NlpDev::fke; points; columns
-    int ow, os;                           // W [N], S [N] in the instance's block of DV::nlv
-    int wz;                               // z1 [N] | z2 [N] in the instance's workspace (DV::nlw)
-    double par;                           // real exponent (POWR)
+    int family;
+    int ke, N, d;                         // kind + 16 * (exponent + 32) as NlpDev::fke (SCALAR, ROWS); points; columns
+    int ow, os;                           // W [N] (ROWS: [R][N]), S [N] (SOFTMAX: [Kf][N]) in the instance's block of DV::nlv
+    int wz;                               // the block's arrays in the instance's workspace (DV::nlw), laid out by the family's nlp_*_ws
+    double par;                           // real exponent (POWR; SCALAR, ROWS)
     const double *A, *At;                 // [N][d] row-major (Hessian) and its transpose [d][N] (points, gradient)
-    const int *col;                       // [d] variable of a column (0-based)
-    const int *hs;                        // [d (d + 1) / 2] COO slot of the lower entry (r, c) at r (r + 1) / 2 + c; -1: no Hessian structure
-    // a softmax block (sqphip_nlp_add_softmax_block; nlp_softmax_dev.hpp): K != 0, ke and par unread.  Kf = K or K - 1 classes
-    // carry variables; col [Kf d] and hs over the flat index k d + j; S [Kf][N] at os; wz: P [Kf][N]
+    const int *col;                       // [d] variable of a column (0-based); SOFTMAX: [Kf d] over the flat index k d + j
+    const int *hs;                        // [D (D + 1) / 2] COO slot of the lower entry (r, c) at r (r + 1) / 2 + c, D = d (SOFTMAX: Kf d); -1: no Hessian structure
+    // SOFTMAX: K classes, of which Kf = K or K - 1 carry variables
     int K, Kf;
     const int *y;                         // [N] label of a point, 0 .. K - 1
-    // a block with several outputs (sqphip_nlp_add_row_block; nlp_rowblock_dev.hpp): R != 0, K = 0.  W [R][N] at ow; wz: kappa [N] |
-    // kappa' [N] | z2 [N]
+    // ROWS, LSE: R outputs; their targets (0: the objective, i: row i, 1-based) in row for ROWS (inline, R <= 8) and in lrow for
+    // LSE (uploaded, R not capped)
     int R;
-    int row[NLP_BLOCK_MAX_R];             // [R] target of an output: 0 the objective, i row i (1-based)
-    const int *js;                        // [R][d] Jacobian COO slot of (row[r], col[j]); unread for an output on row 0
-    // a Cox partial-likelihood block (sqphip_nlp_add_cox_block; nlp_cox_dev.hpp): cox != 0, K = R = 0, ke and par unread.  wz: u [N] |
-    // e [N] | cs [N] | q [N] | -q [N] | 1 / T [N] | P [N][d]
-    int cox;
+    int row[NLP_BLOCK_MAX_R];
+    const int *lrow;
+    const int *js;                        // [R][d] Jacobian COO slot of (target of r, col[j]); unread for an output on row 0
+    // COX
     const int *risk, *first;              // [N] leading points in the risk set of a point; [N] the first point whose risk set holds a point (0-based)
     const double *event;                  // [N] event indicator (0: censored)
-    // a log-sum-exp row block (sqphip_nlp_add_lse_block; nlp_lse_dev.hpp): lse = R != 0 outputs, K = R = cox = 0, ke, par and row
-    // unread; js [lse][d] as above.  wz: u [N] | e [N] | m [lse] | T [lse] | G [lse][d]
-    int lse;
-    const int *lrow, *seg, *outp;         // [lse] target row of an output; [lse + 1] first point of an output; [N] output of a point
+    // LSE
+    const int *seg, *outp;                // [R + 1] first point of an output; [N] output of a point
 };
 
 struct NlpDev {
@@ -112,8 +112,8 @@ struct NlpDev {
     const double *fpar;                   // [nfac] real exponent of a POWR factor (loaded for that kind only)
     int data;                             // sqphip_nlp_attach_data: b, a, p are the instance's, in its block of DV::nlv at ...
     int ob, oa, op;                       // ... ob [nfac], oa [nargs], op [nfac] (op: with a POWR factor only); fab, acoef, aw, fpar unread
-    int ws;                               // doubles of workspace per instance (DV::nlw): 3 nfac, with blocks + TPB / 64 wave sums + 3 TPB kappa values + a block's own (2 N, Kf N, 3 N, 6 N + N d, 2 N + 2 R + R d)
-    int nblk;                             // dense data blocks of the objective (sqphip_nlp_add_block, nlp_block_dev.hpp); uniform over the launch
+    int ws;                               // doubles of workspace per instance (DV::nlw): 3 nfac, with blocks + TPB / 64 wave sums + 3 TPB kappa values + every block's own (the size of its family's nlp_*_ws)
+    int nblk;                             // dense data blocks of any family (the sqphip_nlp_add_*_block calls); uniform over the launch
     NlpBlkDev blk[NLP_MAX_BLOCKS];
 };
 
@@ -213,12 +213,43 @@ static __device__ __forceinline__ void nlp_factor(int ke, double a, double u, do
 }
 
 }  // namespace sqphip
+#include "nlp_blocks_dev.hpp"
 #include "nlp_block_dev.hpp"
 #include "nlp_rowblock_dev.hpp"
 #include "nlp_softmax_dev.hpp"
 #include "nlp_cox_dev.hpp"
 #include "nlp_lse_dev.hpp"
 namespace sqphip {
+
+// every block of the context in block order; a barrier in front of each: the plan passes of nlp_eval and an earlier block wrote
+// f, grad, gv, jv and hv entries that this block adds to from other threads.  Out of line, pointers and scalars only: the kernels
+// that inline nlp_eval carry one call for all blocks of any family.
+static __device__ __noinline__ void nlp_blocks_eval(const NlpBlkDev *blk_, int nblk_, const double *val_, double *wsp_, double *part_,
+                                                    const double *x_, double sigma_, const double *lam_, double *f_out_, double *grad_,
+                                                    double *gv_, double *jv_, double *hv_)
+{
+    // the arguments are the same in every lane: in scalar registers they cross the calls below without a frame of saved
+    // vector registers (80 B per lane otherwise, which every kernel that inlines nlp_eval would carry)
+    const NlpBlkDev *blk = nlp_uniform(blk_);
+    const double *val = nlp_uniform(val_), *x = nlp_uniform(x_);
+    double *wsp = nlp_uniform(wsp_), *part = nlp_uniform(part_), *f_out = nlp_uniform(f_out_), *grad = nlp_uniform(grad_), *hv = nlp_uniform(hv_);
+    const double *lam = nlp_uniform(lam_);
+    double *gv = nlp_uniform(gv_), *jv = nlp_uniform(jv_);      // (read and written by the families with target rows only)
+    const int nblk = __builtin_amdgcn_readfirstlane(nblk_);
+    const double sigma = nlp_uniform(sigma_);
+    #pragma unroll 1
+    for (int k = 0; k < nblk; ++k) {
+        __syncthreads();
+        switch (__builtin_amdgcn_readfirstlane(blk[k].family)) {      // uniform over the launch
+        case NLP_BLK_SCALAR: nlp_block_eval(blk + k, val, wsp, part, x, sigma, f_out, grad, hv); break;
+        case NLP_BLK_ROWS: nlp_rowblock_eval(blk + k, val, wsp, part, x, sigma, lam, f_out, grad, gv, jv, hv); break;
+        case NLP_BLK_SOFTMAX: nlp_softmax_eval(blk + k, val, wsp, part, x, sigma, f_out, grad, hv); break;
+        case NLP_BLK_COX: nlp_cox_eval(blk + k, val, wsp, part, x, sigma, f_out, grad, hv); break;
+        case NLP_BLK_LSE: nlp_lse_eval(blk + k, val, wsp, part, x, sigma, lam, f_out, grad, gv, jv, hv); break;
+        }
+    }
+}
+
 
 // the acopf_eval signature; any of f_out, grad, gv, jv, hv may be null.  Called by every thread of the workgroup.
 static __device__ __forceinline__ void nlp_eval(const DV &d, int inst, const double *__restrict__ x, double sigma,
@@ -314,7 +345,7 @@ static __device__ __forceinline__ void nlp_eval(const DV &d, int inst, const dou
             hv[s_] = s;
         }
     }
-    // dense data blocks of either sort, in block order behind a barrier each: one out-of-line call (nlp_softmax_dev.hpp)
+    // dense data blocks of any family, in block order behind a barrier each: one out-of-line call
     if (q.nblk != 0) nlp_blocks_eval(q.blk, q.nblk, val, w, w + 3 * nf, x, sigma, lam, f_out, grad, gv, jv, hv);
 }
 

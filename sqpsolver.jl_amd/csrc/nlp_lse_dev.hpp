@@ -7,11 +7,9 @@
 // largest u_i over the points of segment r with W_i != 0,
 //     e_i = W_i exp(u_i - m_r),  T_r = sum e_i,  p_i = e_i / T_r,  value m_r + log T_r,  Jacobian row G_r = A_r' p,
 //     Hessian of the Lagrangian  sum_r mu_r (A_r' diag(p) A_r - G_r G_r'),   mu_r = sigma on row 0, lam[row - 1] elsewhere.
-// nlp_blocks_eval (nlp_softmax_dev.hpp) hands a block with NlpBlkDev::lse != 0 to nlp_lse_eval, behind a barrier as any block.
-// Workspace of the instance (NlpBlkDev::wz): u [N] (later p) | e [N] (later z = mu p) | m [R] | T [R] | G [R][d]: 2 N + 2 R + R d doubles.
-// One call of nlp_lse_eval, by every thread of the workgroup:
-//   1. logits: thread i % TPB computes u_i as the scalar blocks do (u = 0, u = fma(At[j][i], x_{col[j]}, u) for j rising,
-//      u += S_i);
+// nlp_blocks_eval (nlp_dev.hpp; the shared steps named below: nlp_blocks_dev.hpp) hands a block of the family NLP_BLK_LSE
+// to nlp_lse_eval, behind a barrier as any block.  One call, by every thread of the workgroup (the arrays: nlp_lse_ws below):
+//   1. logits: thread i % TPB computes the logit u_i;
 //   2. maxima: wave w owns the outputs r = w, w + 16, ...; lane l visits i = seg[r] + l, + 64, ... and keeps the largest u_i
 //      among the visited points with W_i != 0; the xor butterfly 32 .. 1 (a maximum does not depend on its order);
 //   3. exponentials, by all threads over all points: e_i = W_i exp(u_i - m_{out(i)}) where W_i != 0 and exactly 0 elsewhere.  The
@@ -23,12 +21,11 @@
 //      p_i At[j][i] over i = seg[r] + l, + 64, ... in rising order, the butterfly, and lane 0 stores G[r][j] and adds it to
 //      grad[col[j]] (row 0, with grad) or jv[js[r][j]] (with jv).  With the Hessian asked for G is formed for every output,
 //      whatever pointers are null;
-//   7. Hessian: the lower 16 x 16 tiles as in nlp_block_eval (tile t on wave t % 16), two accumulator chains of
-//      v_mfma_f64_16x16x4_f64: chain 1 one instruction per four points p = 0, 4, ... in rising order, a = z_p A[p][16 R + .]
+//   7. Hessian: the tile walk with d columns, two accumulator chains of v_mfma_f64_16x16x4_f64: chain 1 one instruction per four points p = 0, 4, ... in rising order, a = z_p A[p][16 R + .]
 //      (one rounding) against b = A[p][16 C + .]; chain 2 one instruction per four outputs r = 0, 4, ... in rising order,
 //      a = (-mu_r) G[r][16 R + .] (one rounding) against b = G[r][16 C + .].  Ragged edges in points, outputs and columns
-//      enter as zeros.  The lane that holds the lower entry (r, c) adds acc1 + acc2, with no further factor, to its COO slot
-//      (NlpBlkDev::hs).  The two parts are separate sums: their difference is a covariance and cancels, and
+//      enter as zeros.  The lane that holds the lower entry (r, c) adds acc1 + acc2, with no further factor, to its COO slot.
+//      The two parts are separate sums: their difference is a covariance and cancels, and
 //      tests/nlp_lse_ref.py bounds the error by their magnitudes added.
 // Every sum has a fixed order that depends on (N, d, seg) only.  No atomics.  Pointers and scalars only, never DV; out of line.
 // Domain: an output whose points all have weight 0, or whose weighted points all underflow, has T = 0 and files infinities or
@@ -36,6 +33,14 @@
 #pragma once
 
 namespace sqphip {
+
+// the block's doubles in the instance's workspace (at NlpBlkDev::wz): u [N] (from step 5 on p) | e [N] (from step 5 on z = mu p) |
+// m [R] | T [R] | G [R][d]
+struct NlpLseWs { long u, e, m, T, G, size; };
+static __host__ __device__ __forceinline__ NlpLseWs nlp_lse_ws(long N, long R, long d)
+{
+    return {0, N, 2 * N, 2 * N + R, 2 * N + 2 * R, 2 * N + 2 * R + R * d};
+}
 
 // val: the instance's block of values; wsp: its workspace; part: unused (the sums of this block never leave a wave)
 static __device__ __noinline__ void nlp_lse_eval(const NlpBlkDev *bp_, const double *val_, double *wsp_, double *part_,
@@ -49,27 +54,21 @@ static __device__ __noinline__ void nlp_lse_eval(const NlpBlkDev *bp_, const dou
     double *wsp = nlp_uniform(wsp_);
     double *f_out = nlp_uniform(f_out_), *grad = nlp_uniform(grad_), *gv = nlp_uniform(gv_), *jv = nlp_uniform(jv_), *hv = nlp_uniform(hv_);
     const double sigma = nlp_uniform(sigma_);
-    typedef double d4 __attribute__((ext_vector_type(4)));
     const int N = __builtin_amdgcn_readfirstlane(bp->N), d = __builtin_amdgcn_readfirstlane(bp->d);
-    const int R = __builtin_amdgcn_readfirstlane(bp->lse);
+    const int R = __builtin_amdgcn_readfirstlane(bp->R);
     const double *__restrict__ A = nlp_uniform(bp->A), *__restrict__ At = nlp_uniform(bp->At);
     const int *__restrict__ col = nlp_uniform(bp->col), *__restrict__ js = nlp_uniform(bp->js);
     const int *__restrict__ lrow = nlp_uniform(bp->lrow), *__restrict__ seg = nlp_uniform(bp->seg), *__restrict__ outp = nlp_uniform(bp->outp);
     const double *__restrict__ W = val + __builtin_amdgcn_readfirstlane(bp->ow), *__restrict__ S = val + __builtin_amdgcn_readfirstlane(bp->os);
-    double *up = wsp + __builtin_amdgcn_readfirstlane(bp->wz);        // u [N], from step 5 on p [N]
-    double *ez = up + N, *mm = ez + N, *Ts = mm + R, *G = Ts + R;     // e [N], from step 5 on z [N]; m [R]; T [R]; G [R][d]
+    const NlpLseWs ws = nlp_lse_ws(N, R, d);
+    double *base = wsp + __builtin_amdgcn_readfirstlane(bp->wz), *up = base + ws.u;        // u [N], from step 5 on p [N]
+    double *ez = base + ws.e, *mm = base + ws.m, *Ts = base + ws.T, *G = base + ws.G;     // e [N], from step 5 on z [N]; m [R]; T [R]; G [R][d]
     const bool d1 = grad || jv || hv;
     const int lane = threadIdx.x & 63;
     const int wu = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     // 1. logits
     #pragma unroll 1
-    for (int i = threadIdx.x; i < N; i += TPB) {
-        double u = 0.0;
-        #pragma unroll 1
-        for (int j = 0; j < d; ++j) u = fma(At[(long)j * N + i], x[col[j]], u);
-        u += S[i];
-        up[i] = u;
-    }
+    for (int i = threadIdx.x; i < N; i += TPB) up[i] = nlp_block_logit(At, x, col, S, N, d, i);
     __syncthreads();                        // u is complete
     // 2. maxima over the weighted points of a segment
     #pragma unroll 1
@@ -89,7 +88,7 @@ static __device__ __noinline__ void nlp_lse_eval(const NlpBlkDev *bp_, const dou
     for (int i = threadIdx.x; i < N; i += TPB) {
         const double w = W[i];
         double e = 0.0;
-        if (w != 0.0) e = w * nlp_softmax_exp(up[i] - mm[outp[i]]);
+        if (w != 0.0) e = w * nlp_block_exp(up[i] - mm[outp[i]]);
         ez[i] = e;
     }
     __syncthreads();                        // e is complete
@@ -104,7 +103,7 @@ static __device__ __noinline__ void nlp_lse_eval(const NlpBlkDev *bp_, const dou
         const int row = __builtin_amdgcn_readfirstlane(lrow[r]);
         double *out = row == 0 ? f_out : gv;
         if (out) {
-            const double v = mm[r] + nlp_softmax_log(s);
+            const double v = mm[r] + nlp_block_log(s);
             if (lane == 0) out[row == 0 ? 0 : row - 1] += v;
         }
         if (lane == 0) Ts[r] = s;
@@ -147,45 +146,33 @@ static __device__ __noinline__ void nlp_lse_eval(const NlpBlkDev *bp_, const dou
     // 7. Hessian
     if (hv) {
         __syncthreads();                    // G is complete
-        const int *__restrict__ hs = nlp_uniform(bp->hs);
-        const int nt = (d + 15) >> 4, T = nt * (nt + 1) / 2;
-        const int l15 = lane & 15, l4 = lane >> 4;
-        #pragma unroll 1
-        for (int t = wu; t < T; t += TPB / 64) {
-            int Rt = 0;
-            while ((Rt + 1) * (Rt + 2) / 2 <= t) ++Rt;
-            const int Cc = t - Rt * (Rt + 1) / 2;
-            const int cr = 16 * Rt + l15, cc = 16 * Cc + l15;
-            const bool okr = cr < d, okc = cc < d;
-            // a lane past the edge reads column 0 of the last point or output and selects zero: every load is in bounds
-            const int jr = okr ? cr : 0, jc = okc ? cc : 0;
-            d4 acc1 = {0.0, 0.0, 0.0, 0.0}, acc2 = {0.0, 0.0, 0.0, 0.0};
-            #pragma unroll 2
-            for (int p0 = 0; p0 < N; p0 += 4) {
-                const bool okp = p0 + l4 < N;
-                const int p = okp ? p0 + l4 : N - 1;
-                const double av = ez[p] * A[(long)p * d + jr], bv = A[(long)p * d + jc];
-                acc1 = __builtin_amdgcn_mfma_f64_16x16x4f64(okp && okr ? av : 0.0, okp && okc ? bv : 0.0, acc1, 0, 0, 0);
-            }
-            #pragma unroll 1
-            for (int r0 = 0; r0 < R; r0 += 4) {
-                const bool oko = r0 + l4 < R;
-                const int r = oko ? r0 + l4 : R - 1;
-                const int row = lrow[r];
-                const double mu = row == 0 ? sigma : lam[row - 1];
-                const double av = (-mu) * G[(long)r * d + jr], bv = G[(long)r * d + jc];
-                acc2 = __builtin_amdgcn_mfma_f64_16x16x4f64(oko && okr ? av : 0.0, oko && okc ? bv : 0.0, acc2, 0, 0, 0);
-            }
-            // D[i][j] = sum_k a[i][k] b[k][j]: this lane holds the rows l4 + 4 q, q = 0 .. 3, of column l15
-            #pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const int r = 16 * Rt + l4 + 4 * q;
-                if (r < d && cc <= r) {
-                    const int s = hs[r * (r + 1) / 2 + cc];
-                    if (s >= 0) hv[s] += acc1[q] + acc2[q];
+        nlp_d4 acc1, acc2;
+        nlp_block_hess_tiles(d, wu, nlp_uniform(bp->hs), hv,
+            [&](const NlpTile &t) __attribute__((always_inline)) {
+                const bool okr = t.okr, okc = t.okc;   // (copies: read through t inside the loops, the loads are formed another way)
+                const int l4 = t.l4;
+                // a lane past the edge reads column 0 of the last point or output and selects zero: every load is in bounds
+                const int jr = okr ? t.cr : 0, jc = okc ? t.cc : 0;
+                acc1 = nlp_d4{0.0, 0.0, 0.0, 0.0};
+                acc2 = nlp_d4{0.0, 0.0, 0.0, 0.0};
+                #pragma unroll 2
+                for (int p0 = 0; p0 < N; p0 += 4) {
+                    const bool okp = p0 + l4 < N;
+                    const int p = okp ? p0 + l4 : N - 1;
+                    const double av = ez[p] * A[(long)p * d + jr], bv = A[(long)p * d + jc];
+                    acc1 = __builtin_amdgcn_mfma_f64_16x16x4f64(okp && okr ? av : 0.0, okp && okc ? bv : 0.0, acc1, 0, 0, 0);
                 }
-            }
-        }
+                #pragma unroll 1
+                for (int r0 = 0; r0 < R; r0 += 4) {
+                    const bool oko = r0 + l4 < R;
+                    const int r = oko ? r0 + l4 : R - 1;
+                    const int row = lrow[r];
+                    const double mu = row == 0 ? sigma : lam[row - 1];
+                    const double av = (-mu) * G[(long)r * d + jr], bv = G[(long)r * d + jc];
+                    acc2 = __builtin_amdgcn_mfma_f64_16x16x4f64(oko && okr ? av : 0.0, oko && okc ? bv : 0.0, acc2, 0, 0, 0);
+                }
+            },
+            [&](int q, int) __attribute__((always_inline)) { return acc1[q] + acc2[q]; });
     }
 }
 

@@ -5,33 +5,29 @@
 // Row r has the Jacobian row A'(W_r kappa'), and the Hessian of the Lagrangian of all R outputs is one rank-N update
 //     A' diag(kappa'' (sum_r mu_r W_r)) A,      mu_r = sigma for row 0, lambda_i for row i,
 // which costs one pass on the MFMA pipe (v_mfma_f64_16x16x4_f64) whatever R is.
-// nlp_blocks_eval (nlp_softmax_dev.hpp) hands a block with NlpBlkDev::R != 0 to nlp_rowblock_eval, behind a barrier as any block.
+// nlp_blocks_eval (nlp_dev.hpp; the shared steps named below: nlp_blocks_dev.hpp) hands a block of the family NLP_BLK_ROWS
+// to nlp_rowblock_eval, behind a barrier as any block.
 // One call, by every thread of the workgroup, computes what the non-null pointers ask for:
-//   1. points: thread i % TPB computes u_i as nlp_block_eval does (u = 0, u = fma(At[j][i], x_{col_j}, u) for j rising, u += S_i),
-//      then kappa, kappa', kappa'' once through nlp_block_kappa, and stores kappa_i, kappa'_i (with any derivative) and
-//      z2_i = e_i kappa''_i (with the Hessian) in the instance's workspace (NlpBlkDev::wz, three arrays of N), where
+//   1. points: thread i % TPB computes the logit u_i, then kappa, kappa', kappa'' once through nlp_block_kappa, and stores
+//      kappa_i, kappa'_i (with any derivative) and z2_i = e_i kappa''_i (with the Hessian) in the instance's workspace, where
 //      e_i = 0, e_i = fma(mu_r, W_r[i], e_i) for r = 0 .. R - 1 in that order;
-//   2. values: for output r, thread t sums W_r[i] kappa_i over i = t, t + TPB, ... in rising order, the xor butterfly 32 .. 1
-//      within a wave, the sixteen wave sums added by thread 0 in wave order, and that is added to *f_out (row 0, with f_out)
-//      or gv[row - 1] (with gv);
+//   2. values: for output r, thread t sums W_r[i] kappa_i over i = t, t + TPB, ... in rising order, then the workgroup's sum
+//      (one barrier for all outputs), and that is added to *f_out (row 0, with f_out) or gv[row - 1] (with gv);
 //   3. first derivatives: the pairs (r, j), numbered r d + j, are dealt to the waves (wave, wave + 16, ...); lane l sums
 //      (W_r[i] kappa'_i) At[j][i] over i = l, l + 64, ... in rising order, the same butterfly, and lane 0 adds the sum to
 //      grad[col_j] (row 0, with grad) or jv[js[r][j]] (with jv);
-//   4. Hessian: the lower 16 x 16 tiles as in nlp_block_eval (tile t on wave t % 16, one MFMA per four points in rising order,
-//      a = z2_p A[p][16 R + .] with one rounding, b = A[p][16 C + .], ragged edges as zeros); the lane that holds the lower
-//      entry (r, c) adds the accumulator, with no further factor, to its COO slot (NlpBlkDev::hs).
+//   4. Hessian: the tile walk with d columns, one MFMA per four points in rising order, a = z2_p A[p][16 R + .] with one
+//      rounding, b = A[p][16 C + .], points >= N as zeros; the lane that holds the lower entry (r, c) adds the accumulator,
+//      with no further factor, to its COO slot.
 // Every sum has a fixed order that depends on (N, d, R) only: bit-reproducible, independent of slot, neighbours and instance
 // groups.  No atomics.  Pointers and scalars only, never DV; out of line.
 #pragma once
 
 namespace sqphip {
 
-static __device__ __forceinline__ double nlp_uniform(double v)
-{
-    const unsigned long b = (unsigned long)__double_as_longlong(v);
-    return __longlong_as_double((long long)(((unsigned long)(unsigned)__builtin_amdgcn_readfirstlane((unsigned)(b >> 32)) << 32) |
-                                            (unsigned)__builtin_amdgcn_readfirstlane((unsigned)b)));
-}
+// the block's doubles in the instance's workspace (at NlpBlkDev::wz): kappa [N] | kappa' [N] | z2 [N]
+struct NlpRowblockWs { long k0, k1, z2, size; };
+static __host__ __device__ __forceinline__ NlpRowblockWs nlp_rowblock_ws(long N) { return {0, N, 2 * N, 3 * N}; }
 
 // val: the instance's block of values; wsp: its workspace; part: [TPB / 64] wave sums of the instance, then [TPB][3] kappa,
 // kappa', kappa'' of the point a thread is at.  Behind the barrier that ends the points the wave sums of output r sit at
@@ -46,23 +42,20 @@ static __device__ __noinline__ void nlp_rowblock_eval(const NlpBlkDev *bp_, cons
     double *wsp = nlp_uniform(wsp_), *part = nlp_uniform(part_);
     double *f_out = nlp_uniform(f_out_), *grad = nlp_uniform(grad_), *gv = nlp_uniform(gv_), *jv = nlp_uniform(jv_), *hv = nlp_uniform(hv_);
     const double sigma = nlp_uniform(sigma_);
-    typedef double d4 __attribute__((ext_vector_type(4)));
     const int N = __builtin_amdgcn_readfirstlane(bp->N), d = __builtin_amdgcn_readfirstlane(bp->d);
     const int R = __builtin_amdgcn_readfirstlane(bp->R), ke = __builtin_amdgcn_readfirstlane(bp->ke);
     const double pw = nlp_uniform(bp->par);
     const double *__restrict__ A = nlp_uniform(bp->A), *__restrict__ At = nlp_uniform(bp->At);
     const int *__restrict__ col = nlp_uniform(bp->col), *__restrict__ js = nlp_uniform(bp->js);
     const double *__restrict__ W = val + __builtin_amdgcn_readfirstlane(bp->ow), *__restrict__ S = val + __builtin_amdgcn_readfirstlane(bp->os);
-    double *k0 = wsp + __builtin_amdgcn_readfirstlane(bp->wz), *k1 = k0 + N, *z2 = k1 + N;
+    const NlpRowblockWs ws = nlp_rowblock_ws(N);
+    double *base = wsp + __builtin_amdgcn_readfirstlane(bp->wz), *k0 = base + ws.k0, *k1 = base + ws.k1, *z2 = base + ws.z2;
     const bool d1 = grad || jv || hv, d2 = hv != nullptr;
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const int wu = __builtin_amdgcn_readfirstlane(wv);
     #pragma unroll 1
     for (int i = threadIdx.x; i < N; i += TPB) {
-        double u = 0.0;
-        #pragma unroll 1
-        for (int j = 0; j < d; ++j) u = fma(At[(long)j * N + i], x[col[j]], u);
-        u += S[i];
+        const double u = nlp_block_logit(At, x, col, S, N, d, i);
         double *__restrict__ k3 = part + TPB / 64 + 3 * threadIdx.x;
         nlp_block_kappa(ke, u, pw, (int)d1 + (int)d2, k3);
         k0[i] = k3[0];
@@ -86,8 +79,7 @@ static __device__ __noinline__ void nlp_rowblock_eval(const NlpBlkDev *bp_, cons
         double f = 0.0;
         #pragma unroll 1
         for (int i = threadIdx.x; i < N; i += TPB) f += Wr[i] * k0[i];
-        f = nlp_wave_sum(f);
-        if (lane == 0) part[r * (TPB / 64) + wu] = f;
+        nlp_block_sum_put(f, part + r * (TPB / 64), wu);
     }
     __syncthreads();                        // the wave sums are complete
     if (threadIdx.x == 0) {
@@ -96,9 +88,7 @@ static __device__ __noinline__ void nlp_rowblock_eval(const NlpBlkDev *bp_, cons
             const int row = __builtin_amdgcn_readfirstlane(bp->row[r]);
             double *out = row == 0 ? f_out : gv;
             if (!out) continue;
-            double s = part[r * (TPB / 64)];
-            #pragma unroll 1
-            for (int w = 1; w < TPB / 64; ++w) s += part[r * (TPB / 64) + w];
+            const double s = nlp_block_sum_get(part + r * (TPB / 64));
             if (row == 0) *out += s;
             else out[row - 1] += s;
         }
@@ -119,35 +109,23 @@ static __device__ __noinline__ void nlp_rowblock_eval(const NlpBlkDev *bp_, cons
         }
     }
     if (hv) {
-        const int *__restrict__ hs = nlp_uniform(bp->hs);
-        const int nt = (d + 15) >> 4, T = nt * (nt + 1) / 2;
-        const int l15 = lane & 15, l4 = lane >> 4;
-        #pragma unroll 1
-        for (int t = wu; t < T; t += TPB / 64) {
-            int Rt = 0;
-            while ((Rt + 1) * (Rt + 2) / 2 <= t) ++Rt;
-            const int Cc = t - Rt * (Rt + 1) / 2;
-            const int cr = 16 * Rt + l15, cc = 16 * Cc + l15;
-            const bool okr = cr < d, okc = cc < d;
-            d4 acc = {0.0, 0.0, 0.0, 0.0};
-            #pragma unroll 2
-            for (int p0 = 0; p0 < N; p0 += 4) {
-                const int p = p0 + l4;
-                const bool okp = p < N;
-                const double a = okp && okr ? z2[p] * A[(long)p * d + cr] : 0.0;
-                const double b = okp && okc ? A[(long)p * d + cc] : 0.0;
-                acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, acc, 0, 0, 0);
-            }
-            // D[i][j] = sum_k a[i][k] b[k][j]: this lane holds the rows l4 + 4 q, q = 0 .. 3, of column l15
-            #pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const int r = 16 * Rt + l4 + 4 * q;
-                if (r < d && cc <= r) {
-                    const int s = hs[r * (r + 1) / 2 + cc];
-                    if (s >= 0) hv[s] += acc[q];
+        nlp_d4 acc;
+        nlp_block_hess_tiles(d, wu, nlp_uniform(bp->hs), hv,
+            [&](const NlpTile &t) __attribute__((always_inline)) {
+                const bool okr = t.okr, okc = t.okc;   // (copies: read through t inside the loops, the loads are formed another way)
+                const int l4 = t.l4;
+                // a lane past the edge reads column 0 of the last point and selects zero: every load is in bounds and none sits behind a branch
+                const int jr = okr ? t.cr : 0, jc = okc ? t.cc : 0;
+                acc = nlp_d4{0.0, 0.0, 0.0, 0.0};
+                #pragma unroll 2
+                for (int p0 = 0; p0 < N; p0 += 4) {
+                    const bool okp = p0 + l4 < N;
+                    const int p = okp ? p0 + l4 : N - 1;
+                    const double av = z2[p] * A[(long)p * d + jr], bv = A[(long)p * d + jc];
+                    acc = __builtin_amdgcn_mfma_f64_16x16x4f64(okp && okr ? av : 0.0, okp && okc ? bv : 0.0, acc, 0, 0, 0);
                 }
-            }
-        }
+            },
+            [&](int q, int) __attribute__((always_inline)) { return acc[q]; });
     }
 }
 

@@ -5,48 +5,38 @@
 // (u_{i, K - 1} = 0), Kf = K otherwise; Kf d <= 128.  With the flat index q = k d + j and the softmax probabilities p_ik,
 //     gradient  g_q    = sum_i W_i (p_ik - [y_i = k]) A_ij
 //     Hessian   H_qq'  = sum_i W_i p_ik ([k = l] - p_il) A_ij A_ij'           (q' = l d + j')
-// nlp_blocks_eval (below) is the one call site for blocks of the kernels that inline nlp_eval: it walks the blocks in block
-// order behind a barrier each and hands a softmax block (NlpBlkDev::K != 0) to nlp_softmax_eval, a block with several outputs
-// (NlpBlkDev::R != 0) to nlp_rowblock_eval (nlp_rowblock_dev.hpp), a Cox block (NlpBlkDev::cox != 0) to nlp_cox_eval
-// (nlp_cox_dev.hpp), a log-sum-exp row block (NlpBlkDev::lse != 0) to nlp_lse_eval (nlp_lse_dev.hpp), any other to nlp_block_eval.
-// One call of nlp_softmax_eval, by every thread of the workgroup:
-//   1. points: thread i % TPB computes u_ik as the scalar blocks do (u = 0, u = fma(At[j][i], x_{col[k][j]}, u) for j rising,
-//      u += S[k][i]) for k = 0 .. Kf - 1 and the maximum m of the logits (the pinned class enters with 0, last); then, with
-//      the same logits computed again, e_k = exp(u_k - m) and their sum s in class order (the pinned class adds exp(0 - m)
-//      last), lse = m + log(s) and the point's value W_i (lse - u_{i, y_i}).  No thread keeps an array over the classes: with
-//      a gradient or Hessian asked for, e_k goes to P[k][i] in the instance's workspace (NlpBlkDev::wz, [Kf][N], consecutive
-//      doubles across lanes) and a second sweep leaves p_k = e_k / s there; for f alone nothing is stored.  u_k - m <= 0 and
-//      s >= 1, so any finite logits give finite results;
-//   2. f: as the scalar blocks: per-thread sums over i = t, t + TPB, ... in rising order, the xor butterfly 32 .. 1, the
-//      sixteen wave sums added by thread 0 in wave order, *f_out += that;
+// nlp_blocks_eval (nlp_dev.hpp; the shared steps named below: nlp_blocks_dev.hpp) hands a block of the family
+// NLP_BLK_SOFTMAX to nlp_softmax_eval, behind a barrier as any block.  One call, by every thread of the workgroup:
+//   1. points: thread i % TPB computes the logits u_ik (columns col[k][.], shifts S[k][.]) for k = 0 .. Kf - 1 and the maximum m
+//      of the logits (the pinned class enters with 0, last); then, with the same logits computed again, e_k = exp(u_k - m) and
+//      their sum s in class order (the pinned class adds exp(0 - m) last), lse = m + log(s) and the point's value
+//      W_i (lse - u_{i, y_i}).  No thread keeps an array over the classes: with a gradient or Hessian asked for, e_k goes to
+//      P[k][i] in the instance's workspace (consecutive doubles across lanes) and a second sweep leaves p_k = e_k / s there;
+//      for f alone nothing is stored.  u_k - m <= 0 and s >= 1, so any finite logits give finite results;
+//   2. f: per-thread sums over i = t, t + TPB, ... in rising order, then the workgroup's sum, *f_out += that;
 //   3. gradient: wave w owns q = w, w + 16, ...; lane l sums (W_i (P[k][i] - [y_i = k])) At[j][i] over i = l, l + 64, ... in
 //      rising order, the same butterfly, and lane 0 adds the sum to grad[col[q]];
-//   4. Hessian: the lower 16 x 16 tiles (R, C) of the Kf d x Kf d matrix, numbered R (R + 1) / 2 + C, tile t on wave t % 16,
-//      two accumulator chains of one v_mfma_f64_16x16x4_f64 per four points each, p = 0, 4, 8, ... in rising order.  Both
-//      take a = (W_p P[k(r)][p]) A[p][j(r)]; chain 1 takes b1 = (-P[k(c)][p]) A[p][j(c)], chain 2 takes b2 = A[p][j(c)].  The
-//      class of a row or column is the lane's own (k = q / d): a tile may straddle class boundaries anywhere.  Chain 2 is
-//      skipped for a tile whose rows and columns share no class (uniform over the wave).  Rows and columns >= Kf d and points
-//      >= N enter as zeros.  The lane that holds the lower entry (r, c) adds sigma (acc1 + [k(r) = k(c)] acc2) to its COO
-//      slot (NlpBlkDev::hs); distinct columns make every slot single-writer within a block.
+//   4. Hessian: the tile walk over the Kf d x Kf d matrix, two accumulator chains of one v_mfma_f64_16x16x4_f64 per four points
+//      each, p = 0, 4, 8, ... in rising order.  Both take a = (W_p P[k(r)][p]) A[p][j(r)]; chain 1 takes
+//      b1 = (-P[k(c)][p]) A[p][j(c)], chain 2 takes b2 = A[p][j(c)].  The class of a row or column is the lane's own (k = q / d):
+//      a tile may straddle class boundaries anywhere.  Chain 2 is skipped for a tile whose rows and columns share no class
+//      (uniform over the wave).  Points >= N enter as zeros.  The lane that holds the lower entry (r, c) adds
+//      sigma (acc1 + [k(r) = k(c)] acc2) to its COO slot; distinct columns make every slot single-writer within a block.
 // Every sum has a fixed order that depends on (N, d, K, pinned) only.  No atomics.  Pointers and scalars only, never DV.
 #pragma once
 
 namespace sqphip {
 
-// exp and log out of line: inlined, the constants of their polynomials stay in vector registers across the loop over the points
-// (36 of them), nlp_softmax_eval needs callee-saved registers and every kernel that inlines nlp_eval carries a 108 B frame for it
-static __device__ __noinline__ double nlp_softmax_exp(double v) { return exp(v); }
-static __device__ __noinline__ double nlp_softmax_log(double v) { return log(v); }
+// the block's doubles in the instance's workspace (at NlpBlkDev::wz): P [Kf][N]
+struct NlpSoftmaxWs { long P, size; };
+static __host__ __device__ __forceinline__ NlpSoftmaxWs nlp_softmax_ws(long N, long Kf) { return {0, Kf * N}; }
 
-// u_ik of point i: the fma rule of the scalar blocks, the class's offset last
+// u_ik of point i
 static __device__ __forceinline__ double nlp_softmax_logit(const double *__restrict__ At, const double *__restrict__ x,
                                                            const int *__restrict__ col, const double *__restrict__ S, int N, int d,
                                                            int k, int i)
 {
-    double u = 0.0;
-    #pragma unroll 1
-    for (int j = 0; j < d; ++j) u = fma(At[(long)j * N + i], x[col[k * d + j]], u);
-    return u + S[(long)k * N + i];
+    return nlp_block_logit(At, x, col + k * d, S + (long)k * N, N, d, i);
 }
 
 // val: the instance's block of values; wsp: its workspace; part: [TPB / 64] wave sums of the instance
@@ -57,7 +47,6 @@ static __device__ __noinline__ void nlp_softmax_eval(const NlpBlkDev *bp_, const
     const double *__restrict__ val = nlp_uniform(val_), *__restrict__ x = nlp_uniform(x_);
     double *wsp = nlp_uniform(wsp_), *__restrict__ part = nlp_uniform(part_);
     double *f_out = nlp_uniform(f_out_), *grad = nlp_uniform(grad_), *hv = nlp_uniform(hv_);
-    typedef double d4 __attribute__((ext_vector_type(4)));
     // the block's fields arrive through vector loads: moved to scalar registers, the loop bounds and the tile bookkeeping below
     // are uniform to the compiler as they are in fact
     const int N = __builtin_amdgcn_readfirstlane(bp->N), d = __builtin_amdgcn_readfirstlane(bp->d);
@@ -65,7 +54,7 @@ static __device__ __noinline__ void nlp_softmax_eval(const NlpBlkDev *bp_, const
     const double *__restrict__ A = nlp_uniform(bp->A), *__restrict__ At = nlp_uniform(bp->At);
     const int *__restrict__ col = nlp_uniform(bp->col), *__restrict__ y = nlp_uniform(bp->y);
     const double *__restrict__ W = val + __builtin_amdgcn_readfirstlane(bp->ow), *__restrict__ S = val + __builtin_amdgcn_readfirstlane(bp->os);
-    double *P = wsp + __builtin_amdgcn_readfirstlane(bp->wz);       // [Kf][N]
+    double *P = wsp + __builtin_amdgcn_readfirstlane(bp->wz) + nlp_softmax_ws(N, Kf).P;
     const bool d1 = grad || hv, pinned = Kf < K;
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     double f = 0.0;
@@ -83,27 +72,17 @@ static __device__ __noinline__ void nlp_softmax_eval(const NlpBlkDev *bp_, const
         double s = 0.0;
         #pragma unroll 1
         for (int k = 0; k < Kf; ++k) {
-            const double e = nlp_softmax_exp(nlp_softmax_logit(At, x, col, S, N, d, k, i) - m);
+            const double e = nlp_block_exp(nlp_softmax_logit(At, x, col, S, N, d, k, i) - m);
             s += e;
             if (d1) P[(long)k * N + i] = e;
         }
-        if (pinned) s += nlp_softmax_exp(0.0 - m);
-        f += W[i] * ((m + nlp_softmax_log(s)) - uy);
+        if (pinned) s += nlp_block_exp(0.0 - m);
+        f += W[i] * ((m + nlp_block_log(s)) - uy);
         if (d1)
             #pragma unroll 1
             for (int k = 0; k < Kf; ++k) P[(long)k * N + i] = P[(long)k * N + i] / s;
     }
-    if (f_out) {
-        f = nlp_wave_sum(f);
-        if (lane == 0) part[wv] = f;
-    }
-    __syncthreads();                        // P and the wave sums are complete
-    if (f_out && threadIdx.x == 0) {
-        double r = part[0];
-        #pragma unroll 1
-        for (int w = 1; w < TPB / 64; ++w) r += part[w];
-        *f_out += r;
-    }
+    nlp_block_sum_out(f, part, wv, f_out);      // (its barrier: P is complete as well)
     if (grad) {
         #pragma unroll 1
         for (int q = wv; q < D; q += TPB / 64) {
@@ -117,6 +96,8 @@ static __device__ __noinline__ void nlp_softmax_eval(const NlpBlkDev *bp_, const
         }
     }
     if (hv) {
+        // The tile walk of nlp_block_hess_tiles, written out: through the shared walker the compiler forms the loads of the
+        // chains another way and the larger benchmark shape loses 4 %; a change of the walk is made here as well.
         const int *__restrict__ hs = nlp_uniform(bp->hs);
         const int nt = (D + 15) >> 4, T = nt * (nt + 1) / 2;
         const int l15 = lane & 15, l4 = lane >> 4;
@@ -135,7 +116,7 @@ static __device__ __noinline__ void nlp_softmax_eval(const NlpBlkDev *bp_, const
             // the classes of the tile's rows [16 R / d, rhi] and columns [16 C / d, chi]; C <= R
             const int rhi = (min(16 * R + 15, D - 1)) / d, chi = (min(16 * Cc + 15, D - 1)) / d;
             const bool two = (16 * R) / d <= chi && (16 * Cc) / d <= rhi;
-            d4 acc1 = {0.0, 0.0, 0.0, 0.0}, acc2 = {0.0, 0.0, 0.0, 0.0};
+            nlp_d4 acc1 = {0.0, 0.0, 0.0, 0.0}, acc2 = {0.0, 0.0, 0.0, 0.0};
             // four points: both chains, or chain 1 alone (second: a constant at either call)
             auto step = [&](int p0, bool second) __attribute__((always_inline)) {
                 const bool okp = p0 + l4 < N;
@@ -154,7 +135,6 @@ static __device__ __noinline__ void nlp_softmax_eval(const NlpBlkDev *bp_, const
                 #pragma unroll 2
                 for (int p0 = 0; p0 < N; p0 += 4) step(p0, false);
             }
-            // D[i][j] = sum_k a[i][k] b[k][j]: this lane holds the rows l4 + 4 q, q = 0 .. 3, of column l15
             #pragma unroll
             for (int q = 0; q < 4; ++q) {
                 const int r = 16 * R + l4 + 4 * q;
@@ -164,43 +144,6 @@ static __device__ __noinline__ void nlp_softmax_eval(const NlpBlkDev *bp_, const
                 }
             }
         }
-    }
-}
-
-// (nlp_cox_dev.hpp, which uses nlp_softmax_exp and nlp_softmax_log above)
-static __device__ __noinline__ void nlp_cox_eval(const NlpBlkDev *bp_, const double *val_, double *wsp_, double *part_, const double *x_,
-                                                 double sigma, double *f_out_, double *grad_, double *hv_);
-// (nlp_lse_dev.hpp, likewise)
-static __device__ __noinline__ void nlp_lse_eval(const NlpBlkDev *bp_, const double *val_, double *wsp_, double *part_, const double *x_,
-                                                 double sigma_, const double *lam_, double *f_out_, double *grad_, double *gv_,
-                                                 double *jv_, double *hv_);
-
-// every block of the context in block order; a barrier in front of each: the plan passes of nlp_eval and an earlier block wrote
-// f, grad and hv entries that this block adds to from other threads.  Out of line, pointers and scalars only: the kernels that
-// inline nlp_eval carry one call for all blocks of either sort.
-static __device__ __noinline__ void nlp_blocks_eval(const NlpBlkDev *blk_, int nblk_, const double *val_, double *wsp_, double *part_,
-                                                    const double *x_, double sigma_, const double *lam_, double *f_out_, double *grad_,
-                                                    double *gv_, double *jv_, double *hv_)
-{
-    // the arguments are the same in every lane: in scalar registers they cross the calls below without a frame of saved
-    // vector registers (80 B per lane otherwise, which every kernel that inlines nlp_eval would carry)
-    const NlpBlkDev *blk = nlp_uniform(blk_);
-    const double *val = nlp_uniform(val_), *x = nlp_uniform(x_);
-    double *wsp = nlp_uniform(wsp_), *part = nlp_uniform(part_), *f_out = nlp_uniform(f_out_), *grad = nlp_uniform(grad_), *hv = nlp_uniform(hv_);
-    const double *lam = nlp_uniform(lam_);
-    double *gv = nlp_uniform(gv_), *jv = nlp_uniform(jv_);      // (read and written by a block with several outputs only)
-    const int nblk = __builtin_amdgcn_readfirstlane(nblk_);
-    const unsigned long sb = (unsigned long)__double_as_longlong(sigma_);
-    const double sigma = __longlong_as_double((long long)(((unsigned long)(unsigned)__builtin_amdgcn_readfirstlane((unsigned)(sb >> 32)) << 32) |
-                                                          (unsigned)__builtin_amdgcn_readfirstlane((unsigned)sb)));
-    #pragma unroll 1
-    for (int k = 0; k < nblk; ++k) {
-        __syncthreads();
-        if (__builtin_amdgcn_readfirstlane(blk[k].K) != 0) nlp_softmax_eval(blk + k, val, wsp, part, x, sigma, f_out, grad, hv);      // uniform over the launch
-        else if (__builtin_amdgcn_readfirstlane(blk[k].cox) != 0) nlp_cox_eval(blk + k, val, wsp, part, x, sigma, f_out, grad, hv);
-        else if (__builtin_amdgcn_readfirstlane(blk[k].lse) != 0) nlp_lse_eval(blk + k, val, wsp, part, x, sigma, lam, f_out, grad, gv, jv, hv);
-        else if (__builtin_amdgcn_readfirstlane(blk[k].R) != 0) nlp_rowblock_eval(blk + k, val, wsp, part, x, sigma, lam, f_out, grad, gv, jv, hv);
-        else nlp_block_eval(blk + k, val, wsp, part, x, sigma, f_out, grad, hv);
     }
 }
 

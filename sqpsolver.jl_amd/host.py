@@ -610,57 +610,43 @@ class Context:
         sqphip_nlp_add_row_block, an nlp_terms.NlpCoxBlock through sqphip_nlp_add_cox_block, an nlp_terms.NlpLseBlock
         (log-sum-exp rows) through sqphip_nlp_add_lse_block."""
         from .nlp_terms import NlpCoxBlock, NlpLseBlock, NlpRowBlock, NlpSoftmaxBlock
-        if isinstance(b, NlpLseBlock):                # (sqphip_nlp_add_lse_block)
-            if not hasattr(self.L, "sqphip_nlp_add_lse_block"):
-                raise SqpHipError("libsqphip.so lacks sqphip_nlp_add_lse_block: rebuild it")
-            A = _f(np.atleast_2d(b.A))
-            rows = np.ascontiguousarray(b.rows, dtype=np.int64)
-            out = C.c_int32(-1)
-            self._ck(self.L.sqphip_nlp_add_lse_block(self.h, A.shape[0], A.shape[1], _l(np.ascontiguousarray(b.cols, dtype=np.int64)),
-                                                     _d(A), len(rows), _l(rows), _l(np.ascontiguousarray(b.seg, dtype=np.int64)),
-                                                     _d(None if b.shift is None else _f(b.shift)),
-                                                     _d(None if b.weight is None else _f(b.weight)), C.byref(out)))
-            return out.value
-        if isinstance(b, NlpCoxBlock):               # (sqphip_nlp_add_cox_block)
-            if not hasattr(self.L, "sqphip_nlp_add_cox_block"):
-                raise SqpHipError("libsqphip.so lacks sqphip_nlp_add_cox_block: rebuild it")
-            A = _f(np.atleast_2d(b.A))
-            out = C.c_int32(-1)
-            self._ck(self.L.sqphip_nlp_add_cox_block(self.h, A.shape[0], A.shape[1], _l(np.ascontiguousarray(b.cols, dtype=np.int64)),
-                                                     _d(A), _i(np.ascontiguousarray(b.risk, dtype=np.int32)), _d(_f(b.event)),
-                                                     _d(None if b.shift is None else _f(b.shift)),
-                                                     _d(None if b.weight is None else _f(b.weight)), C.byref(out)))
-            return out.value
-        if isinstance(b, NlpRowBlock):
-            if not hasattr(self.L, "sqphip_nlp_add_row_block"):
-                raise SqpHipError("libsqphip.so lacks sqphip_nlp_add_row_block: rebuild it")
-            A = _f(np.atleast_2d(b.A))
-            rows = np.ascontiguousarray(b.rows, dtype=np.int64)
-            out = C.c_int32(-1)
-            self._ck(self.L.sqphip_nlp_add_row_block(self.h, int(b.kind), int(b.exp), float(b.par), A.shape[0], A.shape[1],
-                                                     _l(np.ascontiguousarray(b.cols, dtype=np.int64)), _d(A), len(rows), _l(rows),
-                                                     _d(None if b.shift is None else _f(b.shift)),
-                                                     _d(None if b.weight is None else _f(b.weight).ravel()), C.byref(out)))
-            return out.value
-        if isinstance(b, NlpSoftmaxBlock):
-            if not hasattr(self.L, "sqphip_nlp_add_softmax_block"):
-                raise SqpHipError("libsqphip.so lacks sqphip_nlp_add_softmax_block: rebuild it")
-            A = _f(np.atleast_2d(b.A))
-            out = C.c_int32(-1)
-            self._ck(self.L.sqphip_nlp_add_softmax_block(self.h, A.shape[0], A.shape[1], int(b.K), int(bool(b.pinned)),
-                                                         _l(np.ascontiguousarray(b.cols, dtype=np.int64).ravel()), _d(A),
-                                                         _i(np.ascontiguousarray(b.labels, dtype=np.int32)),
-                                                         _d(None if b.shift is None else _f(b.shift).ravel()),
-                                                         _d(None if b.weight is None else _f(b.weight)), C.byref(out)))
-            return out.value
-        if not hasattr(self.L, "sqphip_nlp_add_block"):
-            raise SqpHipError("libsqphip.so lacks sqphip_nlp_add_block: rebuild it")
+        def i32(a):
+            return _i(np.ascontiguousarray(a, dtype=np.int32))
+
+        def i64(a):
+            return _l(np.ascontiguousarray(a, dtype=np.int64).ravel())
+
+        # the arguments of a call between the handle and shift, weight, the block number (N, d; cols, A: pointers)
+        def scalar(N, d, cols, A):
+            return (int(b.kind), int(b.exp), float(b.par), N, d, cols, A)
+
+        def rows(N, d, cols, A):
+            r = np.ascontiguousarray(b.rows, dtype=np.int64)
+            return scalar(N, d, cols, A) + (len(r), _l(r))
+
+        def softmax(N, d, cols, A):
+            return (N, d, int(b.K), int(bool(b.pinned)), cols, A, i32(b.labels))
+
+        def cox(N, d, cols, A):
+            return (N, d, cols, A, i32(b.risk), _d(_f(b.event)))
+
+        def lse(N, d, cols, A):
+            r = np.ascontiguousarray(b.rows, dtype=np.int64)
+            return (N, d, cols, A, len(r), _l(r), i64(b.seg))
+
+        symbol, args = "sqphip_nlp_add_block", scalar         # any other class
+        for cls, sym, fn in ((NlpLseBlock, "sqphip_nlp_add_lse_block", lse), (NlpCoxBlock, "sqphip_nlp_add_cox_block", cox),
+                             (NlpRowBlock, "sqphip_nlp_add_row_block", rows), (NlpSoftmaxBlock, "sqphip_nlp_add_softmax_block", softmax)):
+            if isinstance(b, cls):
+                symbol, args = sym, fn
+                break
+        if not hasattr(self.L, symbol):
+            raise SqpHipError(f"libsqphip.so lacks {symbol}: rebuild it")
         A = _f(np.atleast_2d(b.A))
         out = C.c_int32(-1)
-        self._ck(self.L.sqphip_nlp_add_block(self.h, int(b.kind), int(b.exp), float(b.par), A.shape[0], A.shape[1],
-                                             _l(np.ascontiguousarray(b.cols, dtype=np.int64)), _d(A),
-                                             _d(None if b.shift is None else _f(b.shift)),
-                                             _d(None if b.weight is None else _f(b.weight)), C.byref(out)))
+        self._ck(getattr(self.L, symbol)(self.h, *args(A.shape[0], A.shape[1], i64(b.cols), _d(A)),
+                                         _d(None if b.shift is None else _f(b.shift).ravel()),
+                                         _d(None if b.weight is None else _f(b.weight).ravel()), C.byref(out)))
         return out.value
 
     @staticmethod
