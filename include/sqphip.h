@@ -659,6 +659,61 @@ int sqphip_nlp_add_lse_block(sqphip_ctx *ctx, int64_t N, int32_t d, const int64_
                              const double *A /* [N][d] row-major */, int32_t R, const int64_t *rows /* [R] */,
                              const int64_t *seg /* [R + 1] */, const double *shift /* [N] or NULL: zeros */,
                              const double *weight /* [N] or NULL: ones */, int32_t *blk_out /* 0-based block number, or NULL */);
+/* Euclidean-norm row blocks of an NLP context (second-order-cone rows a'x + kappa |P x| <= b, chance constraints, risk budgets;
+ * sums of norms in the objective: Fermat-Weber location, group lasso, total variation, robust least squares): output r owns the
+ * consecutive points seg[r] .. seg[r + 1] - 1 (0-based; seg[0] = 0, seg[R] = N, every segment at least one point) and adds
+ *     f_r = sqrt( sum_{i in segment r} W[i] v_i^2 ),   v_i = sum_{j < d} A[i][j] x_{cols[j]} + S[i]
+ * to row rows[r]; row 0 is the objective (it may be absent), row i >= 1 a nonlinear constraint row (i > num_linear).  Any number
+ * of outputs may share a row, row 0 included: a sum of norms in the objective is several outputs on row 0.  The linear part of
+ * a cone row stays in the terms of the same row.  A, cols, seg and rows are shared by the batch; the weights W [N] >= 0 and the
+ * shifts S [N] belong to the instance.  A coefficient c_r > 0 on a norm goes into the weights of its points as c_r^2.  There is
+ * no smoothing parameter: a point whose row of A is zero and whose shift is delta puts delta^2 under the root, per instance.
+ * W[i] = 0 removes point i without a trace: its residual is never read into a maximum, a sum or a product and may be infinite or
+ * NaN.  W >= 0 and finite residuals on weighted points are the caller's business.  Limits: 1 <= d <= 128 distinct 1-based
+ * columns in any order, N >= 1, N d < 2^31, 1 <= R <= N, R d < 2^31.  The block counts among the four blocks of a context and
+ * is evaluated in block order with the others, behind the same barrier.  With m_r the largest |v_i| over the points of segment r
+ * with W[i] != 0, y_i = v_i / m_r, s_r = sum W[i] y_i^2 and mu_r = sigma on row 0, lambda[row - 1] elsewhere:
+ *     value f_r = m_r sqrt(s_r),   q_i = W[i] y_i / sqrt(s_r),   Jacobian row G[r] = A_r' q,
+ *     Hessian of the Lagrangian sum_r mu_r (A_r' diag(W / f_r) A_r - G[r] G[r]' / f_r).
+ * Residuals of 1e+-200 give finite values and first derivatives.
+ * The apex: an output with f_r = 0 -- all its weights zero, or all its weighted residuals exactly zero -- files the value 0,
+ * which is exact for an unsmoothed norm, and contributes exactly nothing to gradient, Jacobian and Hessian (q = 0, z = 0, no
+ * division by zero, no NaN).  That derivative is a choice of subgradient; a model that is to converge to an apex carries the
+ * smoothing point.
+ * State rules and re-lay as for sqphip_nlp_add_block (SQPHIP_ESTATE once the layout is final); the instance's block grows by
+ *     W [N] | S [N]                                                               (padded to an even count)
+ * and its workspace by 2 N + 2 R + R d doubles (v then q, z, m, F, G).
+ * sqphip_nlp_set_instance_block and sqphip_nlp_stream_set_block serve the block unchanged (weight [N], shift [N]);
+ * sqphip_nlp_stream_set restores the data of this call.
+ * The Jacobian COO of sqphip_create must hold (rows[r], cols[j]) for every output on a row >= 1 and every column; unless
+ * nnzH = 0 the Hessian COO must hold the lower entry of every pair of block columns, the diagonal included.  Where the COO
+ * repeats an entry the first copy owns the slot and the others read 0.
+ * SQPHIP_EINVAL, with sqphip_last_error naming the block and the 1-based output, column, entry or point: a context without an
+ * NLP attach, d outside 1..128, N < 1 or N d too large, a fifth block, null cols or A, R outside 1..N or R d too large, null
+ * rows or seg, seg[0] != 0, seg[R] != N, an empty or decreasing segment, a column out of range or twice, a missing Hessian
+ * entry, a row outside 0..m, a row among 1..num_linear, a missing Jacobian entry.  A repeated row is accepted.
+ * Evaluation (one workgroup per instance; every sum in an order that depends on N, d, seg and rows only, no atomics).  An output
+ * of at most 64 points is short, any other long:
+ *   residuals v_i = 0, v_i = fma(A[i][j], x_cols[j], v_i) for j = 0 .. d - 1, v_i += S[i];
+ *   norms     a long output belongs to a wave: lane l takes the largest |v_i| over i = seg[r] + l, + 64, ... with W[i] != 0, the
+ *             xor butterfly 32, 16, .. 1, then sums W[i] y_i^2 over the same points in rising order and the butterfly.  A short
+ *             output belongs to one thread, which does both in rising i;
+ *   values    one thread per distinct target row adds f_r over its outputs in rising r to f (row 0) or g[row - 1].  A call for
+ *             values alone (the Armijo probe) ends here, with the bits of a full call;
+ *   Jacobian  G[r][j] = sum q_i A[i][j]: for a long output by a wave per (r, j) as above, for a short one by one thread per
+ *             (r, j) in rising i; then one thread per (target row, j) adds G[r][j] over the row's outputs in rising r to
+ *             grad[cols[j]] (row 0) or to the Jacobian slot of (row, cols[j]);
+ *   Hessian   lower 16 x 16 tiles on v_mfma_f64_16x16x4_f64, two accumulator chains: four points per instruction in rising
+ *             order, (mu_r W[i] / f_r) A[i][r'] against A[i][c'], and four outputs per instruction in rising order,
+ *             (-mu_r / f_r) G[r][r'] against G[r][c']; ragged edges as zeros; chain 1 + chain 2 is added to the entry's COO slot by
+ *             one thread.  The two parts are separate sums; their difference cancels, and the error bound
+ *             (tests/nlp_norm_ref.py) is that of their magnitudes added.
+ * Results are bit-reproducible and independent of slot, neighbours and instance groups.  A context without such a block files
+ * the bits it filed before this call existed. */
+int sqphip_nlp_add_norm_block(sqphip_ctx *ctx, int64_t N, int32_t d, const int64_t *cols /* [d] 1-based */,
+                              const double *A /* [N][d] row-major */, int32_t R, const int64_t *rows /* [R], may repeat */,
+                              const int64_t *seg /* [R + 1] */, const double *shift /* [N] or NULL: zeros */,
+                              const double *weight /* [N] or NULL: ones */, int32_t *blk_out /* 0-based block number, or NULL */);
 /* Dense data blocks with several outputs: one design matrix, R weight vectors, a target row each.  Output r adds
  *     sum_{i < N} W[r][i] kappa(sum_{j < d} A[i][j] x_{cols[j]} + S[i])
  * to row rows[r]; row 0 is the objective, row i >= 1 a nonlinear constraint row (i > num_linear).  Constraints on the data the

@@ -13,7 +13,7 @@ if os.environ.get("SQPHIP_SO"):        # experiment aid: another build of the li
     SO_PATH = os.path.abspath(os.environ["SQPHIP_SO"])
 SOURCES = ["ldlt.hip", "kernel_api.hip", "ipm.hip", "acopf.hip", "sqp.hip", "api.hip", "api_models.hip", "model_plans.cpp", "order.hip",
            "symbolic.hip", "mfplan.hip", "mf_select.cpp", "mfront.hip", "comm.hip"]
-HEADERS = ["sqphip_internal.hpp", "ctx.hpp", "api_util.hpp", "model_plans.hpp", "sparse.hpp", "mf_kernels.hpp", "mf_select.hpp", "dev_util.hpp", "mf_dev.hpp", "sqp_dev.hpp", "acopf_dev.hpp", "qcqp_dev.hpp", "nlp_dev.hpp", "nlp_blocks_dev.hpp", "nlp_block_dev.hpp", "nlp_rowblock_dev.hpp", "nlp_softmax_dev.hpp", "nlp_cox_dev.hpp", "nlp_lse_dev.hpp", os.path.join("..", "..", "include", "sqphip.h"),
+HEADERS = ["sqphip_internal.hpp", "ctx.hpp", "api_util.hpp", "model_plans.hpp", "sparse.hpp", "mf_kernels.hpp", "mf_select.hpp", "dev_util.hpp", "mf_dev.hpp", "sqp_dev.hpp", "acopf_dev.hpp", "qcqp_dev.hpp", "nlp_dev.hpp", "nlp_blocks_dev.hpp", "nlp_block_dev.hpp", "nlp_rowblock_dev.hpp", "nlp_softmax_dev.hpp", "nlp_cox_dev.hpp", "nlp_lse_dev.hpp", "nlp_norm_dev.hpp", os.path.join("..", "..", "include", "sqphip.h"),
            os.path.join("..", "..", "include", "sqphip_test_hooks.h")]
 
 _lib = None
@@ -218,6 +218,8 @@ def lib():
                 L.sqphip_nlp_add_cox_block.argtypes = [vp, C.c_int64, C.c_int32, lp, dp, ip, dp, dp, dp, ip]
             if not os.environ.get("SQPHIP_SO") or hasattr(L, "sqphip_nlp_add_lse_block"):   # (an older build given through SQPHIP_SO lacks the log-sum-exp blocks)
                 L.sqphip_nlp_add_lse_block.argtypes = [vp, C.c_int64, C.c_int32, lp, dp, C.c_int32, lp, lp, dp, dp, ip]
+            if not os.environ.get("SQPHIP_SO") or hasattr(L, "sqphip_nlp_add_norm_block"):   # (an older build given through SQPHIP_SO lacks the Euclidean-norm blocks)
+                L.sqphip_nlp_add_norm_block.argtypes = [vp, C.c_int64, C.c_int32, lp, dp, C.c_int32, lp, lp, dp, dp, ip]
             L.sqphip_acopf_set_shunts.argtypes = [vp, C.c_int32, ip, dp, dp]
             L.sqphip_acopf_set_dclines.argtypes = [vp, C.c_int32, dp]
             L.sqphip_kkt_order.argtypes = [C.c_int64, C.c_int64, C.c_int64, lp, lp, C.c_int64, lp, lp, dp, dp, C.c_int32,
@@ -296,7 +298,7 @@ EXPORTS = [
     "sqphip_kt_residuals", "sqphip_norm_complementarity", "sqphip_compute_phi",
     "sqphip_compute_qmodel", "sqphip_compute_derivative", "sqphip_compute_derivative_full", "sqphip_compute_mu_rule_dev",
     "sqphip_acopf_armijo", "sqphip_tr_update",
-    "sqphip_kkt_order", "sqphip_kkt_order_info", "sqphip_kkt_dense_test", "sqphip_solve_vector_test", "sqphip_kkt_symbolic", "sqphip_mf_host_solve", "sqphip_mf_host_top2_err", "sqphip_mf_host_spine_err", "sqphip_mf_solve_test", "sqphip_mf_batch_test", "sqphip_mf_values_test", "sqphip_mf_values_blocks", "sqphip_mf_census", "sqphip_trans_inline_groups", "sqphip_mf_plan_info", "sqphip_mf_front_launches", "sqphip_mf_factor_kernels", "sqphip_acopf_attach", "sqphip_acopf_attach_acr", "sqphip_acopf_attach_acwr", "sqphip_acopf_set_shunts", "sqphip_acopf_set_dclines", "sqphip_acopf_set_instance", "sqphip_dense_attach", "sqphip_dense_set_instance", "sqphip_qcqp_attach", "sqphip_qcqp_set_instance", "sqphip_nlp_attach", "sqphip_nlp_attach_affine", "sqphip_nlp_attach_general", "sqphip_nlp_attach_data", "sqphip_nlp_set_instance", "sqphip_nlp_set_instance_data", "sqphip_nlp_add_block", "sqphip_nlp_add_softmax_block", "sqphip_nlp_add_row_block", "sqphip_nlp_add_cox_block", "sqphip_nlp_add_lse_block", "sqphip_nlp_set_instance_block", "sqphip_nlp_stream_set_block", "sqphip_acopf_eval", "sqphip_sqp_reset",
+    "sqphip_kkt_order", "sqphip_kkt_order_info", "sqphip_kkt_dense_test", "sqphip_solve_vector_test", "sqphip_kkt_symbolic", "sqphip_mf_host_solve", "sqphip_mf_host_top2_err", "sqphip_mf_host_spine_err", "sqphip_mf_solve_test", "sqphip_mf_batch_test", "sqphip_mf_values_test", "sqphip_mf_values_blocks", "sqphip_mf_census", "sqphip_trans_inline_groups", "sqphip_mf_plan_info", "sqphip_mf_front_launches", "sqphip_mf_factor_kernels", "sqphip_acopf_attach", "sqphip_acopf_attach_acr", "sqphip_acopf_attach_acwr", "sqphip_acopf_set_shunts", "sqphip_acopf_set_dclines", "sqphip_acopf_set_instance", "sqphip_dense_attach", "sqphip_dense_set_instance", "sqphip_qcqp_attach", "sqphip_qcqp_set_instance", "sqphip_nlp_attach", "sqphip_nlp_attach_affine", "sqphip_nlp_attach_general", "sqphip_nlp_attach_data", "sqphip_nlp_set_instance", "sqphip_nlp_set_instance_data", "sqphip_nlp_add_block", "sqphip_nlp_add_softmax_block", "sqphip_nlp_add_row_block", "sqphip_nlp_add_cox_block", "sqphip_nlp_add_lse_block", "sqphip_nlp_add_norm_block", "sqphip_nlp_set_instance_block", "sqphip_nlp_stream_set_block", "sqphip_acopf_eval", "sqphip_sqp_reset",
     "sqphip_sqp_run", "sqphip_sqp_get", "sqphip_sqp_status", "sqphip_sqp_trace",
     "sqphip_comm_available", "sqphip_comm_unique_id", "sqphip_comm_init", "sqphip_gather_status", "sqphip_comm_destroy",
     "sqphip_get_counters", "sqphip_get_mode_counters", "sqphip_sqp_work", "sqphip_sqp_stream_begin", "sqphip_sqp_stream_set", "sqphip_sqp_stream_run", "sqphip_sqp_stream_get", "sqphip_sqp_stream_assign", "sqphip_sqp_stream_append", "sqphip_sqp_stream_release", "sqphip_sqp_stream_run_some", "sqphip_qcqp_stream_begin", "sqphip_qcqp_stream_set", "sqphip_nlp_stream_begin", "sqphip_nlp_stream_set", "sqphip_nlp_stream_set_data", "sqphip_sqp_stream_get_full", "sqphip_sqp_last_request", "sqphip_sqp_qp_log", "sqphip_reset_counters", "sqphip_set_timing", "sqphip_get_kernel_times", "sqphip_ldlt_factor_host",

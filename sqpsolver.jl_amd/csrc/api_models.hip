@@ -437,7 +437,7 @@ extern "C" int sqphip_nlp_set_instance(sqphip_ctx *h, int32_t inst, const double
     });
 }
 
-// ---- dense data blocks of a factorable NLP (nlp_blocks_dev.hpp, the five family headers, nlp_blocks_eval of nlp_dev.hpp)
+// ---- dense data blocks of a factorable NLP (nlp_blocks_dev.hpp, the six family headers, nlp_blocks_eval of nlp_dev.hpp)
 // the state rules of the add calls; kb: the number of the block to be, blk: "who: block kb + 1" for the messages
 static int nlp_block_begin(sqphip_ctx *h, const std::string &who, int &kb, std::string &blk)
 {
@@ -520,6 +520,21 @@ static std::string nlp_block_shape(int64_t N, int32_t d, int max_d)
     if (d < 1 || d > max_d) return "d = " + std::to_string(d) + " columns (1.." + std::to_string(max_d) + ")";
     if (N < 1) return "N = " + std::to_string(N) + " points (at least 1)";
     if (N > INT32_MAX / d) return "N d = " + std::to_string(N) + " x " + std::to_string(d) + " is too large (N d < 2^31)";
+    return "";
+}
+
+// what sqphip_nlp_add_lse_block and sqphip_nlp_add_norm_block refuse of R outputs over consecutive segments of the N points
+static std::string nlp_block_segments(int64_t N, int32_t d, int32_t R, const int64_t *rows, const int64_t *seg)
+{
+    if (R < 1 || R > N) return "R = " + std::to_string(R) + " outputs (1.." + std::to_string(N) + ")";
+    if (R > INT32_MAX / d) return "R d = " + std::to_string(R) + " x " + std::to_string(d) + " is too large (R d < 2^31)";
+    if (!rows || !seg) return "null rows or seg";
+    if (seg[0] != 0) return "output 1: seg[0] = " + std::to_string(seg[0]) + " (the first segment starts at point 0)";
+    for (int r = 0; r < R; ++r)
+        if (seg[r + 1] <= seg[r])
+            return "output " + std::to_string(r + 1) + ": the segment " + std::to_string(seg[r]) + ".." + std::to_string(seg[r + 1]) +
+                   " is " + (seg[r + 1] == seg[r] ? "empty" : "decreasing");
+    if (seg[R] != N) return "output " + std::to_string(R) + ": seg[R] = " + std::to_string(seg[R]) + " (the last segment ends at N = " + std::to_string(N) + ")";
     return "";
 }
 
@@ -655,15 +670,7 @@ extern "C" int sqphip_nlp_add_lse_block(sqphip_ctx *h, int64_t N, int32_t d, con
     Ctx &C0 = h->c;
     if (const std::string bad = nlp_block_shape(N, d, NLP_BLOCK_MAX_D); !bad.empty()) return call.fail(bad);
     if (!cols || !A) return call.fail("null cols or A");
-    if (R < 1 || R > N) return call.fail("R = " + std::to_string(R) + " outputs (1.." + std::to_string(N) + ")");
-    if (R > INT32_MAX / d) return call.fail("R d = " + std::to_string(R) + " x " + std::to_string(d) + " is too large (R d < 2^31)");
-    if (!rows || !seg) return call.fail("null rows or seg");
-    if (seg[0] != 0) return call.fail("output 1: seg[0] = " + std::to_string(seg[0]) + " (the first segment starts at point 0)");
-    for (int r = 0; r < R; ++r)
-        if (seg[r + 1] <= seg[r])
-            return call.fail("output " + std::to_string(r + 1) + ": the segment " + std::to_string(seg[r]) + ".." + std::to_string(seg[r + 1]) +
-                             " is " + (seg[r + 1] == seg[r] ? "empty" : "decreasing"));
-    if (seg[R] != N) return call.fail("output " + std::to_string(R) + ": seg[R] = " + std::to_string(seg[R]) + " (the last segment ends at N = " + std::to_string(N) + ")");
+    if (const std::string bad = nlp_block_segments(N, d, R, rows, seg); !bad.empty()) return call.fail(bad);
     std::vector<int> hs, cv;
     if (const std::string bad = nlp_block_columns(C0.nl.slots, d, cols, cv, hs); !bad.empty()) return call.fail(bad);
     std::vector<int> row((size_t)R), js;
@@ -681,6 +688,42 @@ extern "C" int sqphip_nlp_add_lse_block(sqphip_ctx *h, int64_t N, int32_t d, con
     });
     if (rc) return rc;
     return nlp_block_commit(h, call.blk, call.kb, (long)N, d, (long)N, (long)N, nlp_lse_ws(N, R, d).size, A, cv, hs, weight, shift, Kb, blk_out);
+}
+
+// a Euclidean-norm row block (nlp_norm_dev.hpp): the checks of sqphip_nlp_add_lse_block, but any number of outputs may share a target
+// row (nlp_block_targets); the targets with their outputs and Jacobian slots and the lists of the short and the long outputs are uploaded
+extern "C" int sqphip_nlp_add_norm_block(sqphip_ctx *h, int64_t N, int32_t d, const int64_t *cols, const double *A, int32_t R,
+                                         const int64_t *rows, const int64_t *seg, const double *shift, const double *weight,
+                                         int32_t *blk_out)
+{
+    NlpBlockAdd call{h};
+    if (int rc = call.begin("sqphip_nlp_add_norm_block")) return rc;
+    Ctx &C0 = h->c;
+    if (const std::string bad = nlp_block_shape(N, d, NLP_BLOCK_MAX_D); !bad.empty()) return call.fail(bad);
+    if (!cols || !A) return call.fail("null cols or A");
+    if (const std::string bad = nlp_block_segments(N, d, R, rows, seg); !bad.empty()) return call.fail(bad);
+    std::vector<int> hs, cv;
+    if (const std::string bad = nlp_block_columns(C0.nl.slots, d, cols, cv, hs); !bad.empty()) return call.fail(bad);
+    NlpBlockTargets T;
+    if (const std::string bad = nlp_block_targets(C0.nl.slots, C0.d.m, C0.d.nlin, R, rows, cv, T); !bad.empty()) return call.fail(bad);
+    std::vector<int> sg((size_t)R + 1), outp((size_t)N), shortl, longl;
+    for (int r = 0; r <= R; ++r) sg[r] = (int)seg[r];
+    for (int r = 0; r < R; ++r) {
+        for (int i = sg[r]; i < sg[r + 1]; ++i) outp[i] = r;
+        (sg[r + 1] - sg[r] <= NLP_NORM_SHORT ? shortl : longl).push_back(r);
+    }
+    NlpBlkDev Kb = {};
+    Kb.family = NLP_BLK_NORM;
+    Kb.R = R; Kb.T = (int)T.trow.size(); Kb.nshort = (int)shortl.size(); Kb.nlong = (int)longl.size();
+    if (shortl.empty()) shortl.push_back(0);      // (never read: an upload is not empty)
+    if (longl.empty()) longl.push_back(0);
+    const int rc = guarded(h, [&](Ctx &C) {
+        Kb.tgt = C.upload(T.tgt); Kb.trow = C.upload(T.trow); Kb.tptr = C.upload(T.tptr); Kb.tout = C.upload(T.tout); Kb.js = C.upload(T.js);
+        Kb.seg = C.upload(sg); Kb.outp = C.upload(outp); Kb.shortl = C.upload(shortl); Kb.longl = C.upload(longl);
+        return SQPHIP_OK;
+    });
+    if (rc) return rc;
+    return nlp_block_commit(h, call.blk, call.kb, (long)N, d, (long)N, (long)N, nlp_norm_ws(N, R, d).size, A, cv, hs, weight, shift, Kb, blk_out);
 }
 
 // weight / shift of block blk into the block of values v (of an instance or of a scenario of the queue); NULL: kept

@@ -343,4 +343,38 @@ std::string nlp_block_rows(const StructureSlots &S, int64_t m, int64_t nlin, int
     return "";
 }
 
+std::string nlp_block_targets(const StructureSlots &S, int64_t m, int64_t nlin, int R, const int64_t *rows, const std::vector<int> &cv,
+                              NlpBlockTargets &T)
+{
+    const int d = (int)cv.size();
+    T.tgt.assign((size_t)R, -1); T.trow.clear(); T.js.clear();
+    std::vector<int> seen((size_t)m + 1, -1);       // target of a row, once it has appeared
+    // (the opening of a complaint, built on the failing paths only)
+    auto out = [&](int r) { return "output " + std::to_string(r + 1) + ": row " + std::to_string(rows[r]); };
+    for (int r = 0; r < R; ++r) {
+        if (rows[r] < 0 || rows[r] > m) return out(r) + " outside 0.." + std::to_string(m);
+        if (rows[r] >= 1 && rows[r] <= nlin) return out(r) + " is one of the num_linear = " + std::to_string(nlin) + " linear rows";
+        int &t = seen[(size_t)rows[r]];
+        if (t < 0) {
+            t = (int)T.trow.size();
+            T.trow.push_back((int)rows[r]);
+            T.js.resize(T.js.size() + (size_t)d, -1);
+            for (int j = 0; rows[r] >= 1 && j < d; ++j)
+                if ((T.js[(size_t)t * d + j] = S.jfind(rows[r] - 1, cv[j])) < 0)
+                    return out(r) + ", column " + std::to_string(j + 1) + " needs the Jacobian entry (" + std::to_string(rows[r]) + ", " +
+                           std::to_string(cv[j] + 1) + ") that the structure of sqphip_create lacks";
+        }
+        T.tgt[r] = t;
+    }
+    // the outputs by target: a counting sort, which keeps them in rising order
+    const int nt = (int)T.trow.size();
+    T.tptr.assign((size_t)nt + 1, 0);
+    for (int r = 0; r < R; ++r) ++T.tptr[(size_t)T.tgt[r] + 1];
+    for (int t = 0; t < nt; ++t) T.tptr[(size_t)t + 1] += T.tptr[t];
+    T.tout.assign((size_t)R, 0);
+    std::vector<int> at(T.tptr.begin(), T.tptr.end() - 1);
+    for (int r = 0; r < R; ++r) T.tout[(size_t)at[T.tgt[r]]++] = r;
+    return "";
+}
+
 }  // namespace sqphip

@@ -101,4 +101,13 @@ std::string nlp_block_columns(const StructureSlots &S, int D, const int64_t *col
 std::string nlp_block_rows(const StructureSlots &S, int64_t m, int64_t nlin, int R, const int64_t *rows, const std::vector<int> &cv,
                            int *row, std::vector<int> &js);
 
+// rows [R] of a block whose outputs may share a target (0: the objective, i: row i, none of the rows 1..nlin; a row may be the
+// target of any number of outputs): the distinct targets in order of first appearance to trow [T], the target of every output to
+// tgt [R] (0 .. T - 1), the outputs of a target in rising order as a CSR list to tptr [T + 1] / tout [R], and the Jacobian COO
+// slot of every (trow[t], cv[j]) to js [T][d] (-1 for the target row 0).  Linear in R.  Returns the complaint, empty when there is
+// none.
+struct NlpBlockTargets { std::vector<int> tgt, trow, tptr, tout, js; };
+std::string nlp_block_targets(const StructureSlots &S, int64_t m, int64_t nlin, int R, const int64_t *rows, const std::vector<int> &cv,
+                              NlpBlockTargets &T);
+
 }  // namespace sqphip

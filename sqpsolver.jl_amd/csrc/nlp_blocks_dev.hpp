@@ -1,10 +1,11 @@
-// nlp_blocks_dev.hpp -- what the dense data blocks of a factorable NLP share.  Five families, one evaluator each in a header of
-// its own; nlp_dev.hpp includes this header, then the five, and holds their dispatcher nlp_blocks_eval behind them:
+// nlp_blocks_dev.hpp -- what the dense data blocks of a factorable NLP share.  Six families, one evaluator each in a header of
+// its own; nlp_dev.hpp includes this header, then the six, and holds their dispatcher nlp_blocks_eval behind them:
 //     NLP_BLK_SCALAR   nlp_block_eval      nlp_block_dev.hpp       sum_i W_i kappa(u_i) in the objective
 //     NLP_BLK_ROWS     nlp_rowblock_eval   nlp_rowblock_dev.hpp    R <= 8 weight vectors on one pass, a target row each
 //     NLP_BLK_SOFTMAX  nlp_softmax_eval    nlp_softmax_dev.hpp     multinomial log-likelihood
 //     NLP_BLK_COX      nlp_cox_eval        nlp_cox_dev.hpp         Cox partial likelihood
 //     NLP_BLK_LSE      nlp_lse_eval        nlp_lse_dev.hpp         log-sum-exp rows over segments of the points
+//     NLP_BLK_NORM     nlp_norm_eval       nlp_norm_dev.hpp        Euclidean norms over segments of the points, several per row
 // A family header keeps its mathematics, its order-of-summation contract and the layout of its workspace (nlp_*_ws, read by the
 // evaluator and by the add call of api_models.hip alike); the steps below are described here once.
 //   logit      u_i = 0, u_i = fma(At[j][i], x_{col_j}, u_i) for j = 0 .. d - 1 in that order, u_i += S_i: the rule of

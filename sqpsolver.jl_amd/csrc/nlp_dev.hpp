@@ -49,6 +49,9 @@
 // sqphip_nlp_add_lse_block: log-sum-exp row blocks, output r = log sum_{i in segment r} W_i exp(u_i) on the objective or a
 // constraint row, any number of outputs over consecutive segments of the points (nlp_lse_dev.hpp); they count among the same
 // four blocks and add to f, grad, gv, jv and hv.
+// sqphip_nlp_add_norm_block: Euclidean-norm row blocks, output r = sqrt(sum_{i in segment r} W_i (A_i'x + S_i)^2) on the objective
+// or a constraint row (second-order-cone rows, sums of norms), any number of outputs over consecutive segments of the points and
+// any number of them on one target row (nlp_norm_dev.hpp); they count among the same four blocks and add to f, grad, gv, jv and hv.
 #pragma once
 #include "ctx.hpp"
 #include "dev_util.hpp"
@@ -62,8 +65,8 @@ enum { NLP_NONE = -(1 << 30), NLP_ARG = (1 << 28) - 1 };     // no factor of a t
 // a dense data block (the sqphip_nlp_add_*_block calls; the shared steps, the evaluators and their dispatcher: included below)
 enum { NLP_MAX_BLOCKS = 4, NLP_BLOCK_MAX_D = 128, NLP_SOFTMAX_MAX_K = 64, NLP_BLOCK_MAX_R = 8 };
 // the family of a block, set by its add call and read by nlp_blocks_eval: sqphip_nlp_add_block, _row_block, _softmax_block,
-// _cox_block, _lse_block
-enum { NLP_BLK_SCALAR, NLP_BLK_ROWS, NLP_BLK_SOFTMAX, NLP_BLK_COX, NLP_BLK_LSE };
+// _cox_block, _lse_block, _norm_block
+enum { NLP_BLK_SCALAR, NLP_BLK_ROWS, NLP_BLK_SOFTMAX, NLP_BLK_COX, NLP_BLK_LSE, NLP_BLK_NORM };
 
 struct NlpBlkDev {
     int family;
@@ -86,8 +89,13 @@ struct NlpBlkDev {
     // COX
     const int *risk, *first;              // [N] leading points in the risk set of a point; [N] the first point whose risk set holds a point (0-based)
     const double *event;                  // [N] event indicator (0: censored)
-    // LSE
+    // LSE, NORM
     const int *seg, *outp;                // [R + 1] first point of an output; [N] output of a point
+    // NORM: R outputs on T distinct targets (js: [T][d], by target); the outputs of at most NLP_NORM_SHORT points and the others
+    const int *tgt, *trow;                // [R] target of an output, 0 .. T - 1; [T] row of a target (0: the objective, i: row i, 1-based)
+    const int *tptr, *tout;               // [T + 1], [R] the outputs of a target in rising order (CSR)
+    const int *shortl, *longl;            // [nshort], [nlong] outputs in rising order
+    int T, nshort, nlong;
 };
 
 struct NlpDev {
@@ -219,6 +227,7 @@ static __device__ __forceinline__ void nlp_factor(int ke, double a, double u, do
 #include "nlp_softmax_dev.hpp"
 #include "nlp_cox_dev.hpp"
 #include "nlp_lse_dev.hpp"
+#include "nlp_norm_dev.hpp"
 namespace sqphip {
 
 // every block of the context in block order; a barrier in front of each: the plan passes of nlp_eval and an earlier block wrote
@@ -246,6 +255,7 @@ static __device__ __noinline__ void nlp_blocks_eval(const NlpBlkDev *blk_, int n
         case NLP_BLK_SOFTMAX: nlp_softmax_eval(blk + k, val, wsp, part, x, sigma, f_out, grad, hv); break;
         case NLP_BLK_COX: nlp_cox_eval(blk + k, val, wsp, part, x, sigma, f_out, grad, hv); break;
         case NLP_BLK_LSE: nlp_lse_eval(blk + k, val, wsp, part, x, sigma, lam, f_out, grad, gv, jv, hv); break;
+        case NLP_BLK_NORM: nlp_norm_eval(blk + k, val, wsp, part, x, sigma, lam, f_out, grad, gv, jv, hv); break;
         }
     }
 }

@@ -608,8 +608,9 @@ class Context:
         sqp_run or nlp_stream_begin.  Returns its number.  An nlp_terms.NlpSoftmaxBlock goes through
         sqphip_nlp_add_softmax_block, an nlp_terms.NlpRowBlock (several outputs, constraint rows) through
         sqphip_nlp_add_row_block, an nlp_terms.NlpCoxBlock through sqphip_nlp_add_cox_block, an nlp_terms.NlpLseBlock
-        (log-sum-exp rows) through sqphip_nlp_add_lse_block."""
-        from .nlp_terms import NlpCoxBlock, NlpLseBlock, NlpRowBlock, NlpSoftmaxBlock
+        (log-sum-exp rows) through sqphip_nlp_add_lse_block, an nlp_terms.NlpNormBlock (Euclidean norms) through
+        sqphip_nlp_add_norm_block."""
+        from .nlp_terms import NlpCoxBlock, NlpLseBlock, NlpNormBlock, NlpRowBlock, NlpSoftmaxBlock
         def i32(a):
             return _i(np.ascontiguousarray(a, dtype=np.int32))
 
@@ -635,7 +636,8 @@ class Context:
             return (N, d, cols, A, len(r), _l(r), i64(b.seg))
 
         symbol, args = "sqphip_nlp_add_block", scalar         # any other class
-        for cls, sym, fn in ((NlpLseBlock, "sqphip_nlp_add_lse_block", lse), (NlpCoxBlock, "sqphip_nlp_add_cox_block", cox),
+        # (a norm block has the argument list of a log-sum-exp block)
+        for cls, sym, fn in ((NlpNormBlock, "sqphip_nlp_add_norm_block", lse), (NlpLseBlock, "sqphip_nlp_add_lse_block", lse), (NlpCoxBlock, "sqphip_nlp_add_cox_block", cox),
                              (NlpRowBlock, "sqphip_nlp_add_row_block", rows), (NlpSoftmaxBlock, "sqphip_nlp_add_softmax_block", softmax)):
             if isinstance(b, cls):
                 symbol, args = sym, fn

@@ -49,6 +49,12 @@ plain affine factors.  Twice inside one factor stays an error.  SQRT and POWR ne
     row_block_eval       ... of its blocks with several outputs: the rows' values and Jacobian rows too, the Hessian of the
                          Lagrangian with sigma and lam
     lse_block_eval       ... of its log-sum-exp row blocks, likewise
+    NlpNormBlock         a Euclidean-norm row block: output r = sqrt(sum_{i in segment r} w_i (A_i'x_cols + b_i)^2) added to row r, any
+                         number of outputs over consecutive segments of the points, any number of them on one row
+                         (sqphip_nlp_add_norm_block)
+    norm_block_eval      ... of its Euclidean-norm row blocks, likewise
+    sum_of_norms_model, robust_lp_model, socp_synth, norm_scenario     Fermat-Weber location as norms on the objective; a robust
+                         linear programme with second-order-cone rows; a seeded cone programme; its scenarios (other shifts)
     geometric_program_model, gp_synth, gp_scenario     a geometric programme in log variables as one log-sum-exp row block; a
                          seeded one; its scenarios (other log-coefficients)
     neyman_pearson_model, rate_constrained_logistic_model     constraints on the data the objective is fitted to, as row blocks
@@ -226,6 +232,52 @@ class NlpLseBlock:
 
 
 @dataclasses.dataclass
+class NlpNormBlock:
+    """Output r adds sqrt(sum_{i in segment r} weight_i v_i^2), v_i = sum_j A[i, j] x_{cols[j]} + shift_i, to row rows[r] (0: the
+    objective, i: row i, a nonlinear one): the Euclidean norm of the consecutive points seg[r] .. seg[r + 1] - 1 (seg[0] = 0,
+    seg[R] = N, every segment at least one point), R = len(rows), 1 <= R <= N.  Rows may repeat: a sum of norms in the objective
+    is several outputs on row 0.  cols d distinct 1-based variables in any order (d <= 128), A [N, d]; shift [N] None: zeros,
+    weight [N] >= 0 None: ones (0 removes a point; a coefficient c > 0 on a norm is c^2 on its points).  An output whose value is
+    0 contributes nothing to the derivatives (the apex); a point with a zero row of A and the shift delta smooths the norm."""
+    cols: np.ndarray
+    A: np.ndarray
+    rows: np.ndarray
+    seg: np.ndarray
+    shift: np.ndarray | None = None
+    weight: np.ndarray | None = None
+
+    def __post_init__(self):
+        self.cols = _i64(np.atleast_1d(self.cols))
+        self.A = _f64(np.atleast_2d(self.A))
+        self.rows = _i64(np.atleast_1d(self.rows))
+        self.seg = _i64(np.atleast_1d(self.seg))
+        N, d = self.A.shape
+        R = len(self.rows)
+        if not 1 <= d <= MAX_BLOCK_COLS:
+            raise ValueError(f"d = {d} columns (1..{MAX_BLOCK_COLS})")
+        if N < 1:
+            raise ValueError(f"N = {N} points (at least 1)")
+        if len(self.cols) != d or len(np.unique(self.cols)) != d:
+            raise ValueError(f"cols: {d} distinct variables")
+        if not 1 <= R <= N:
+            raise ValueError(f"R = {R} outputs (1..{N})")
+        if self.seg.shape != (R + 1,):
+            raise ValueError(f"seg: R + 1 = {R + 1} values")
+        if self.seg[0] != 0:
+            raise ValueError(f"output 1: seg[0] = {int(self.seg[0])} (the first segment starts at point 0)")
+        if np.any(np.diff(self.seg) <= 0):
+            r = int(np.argmax(np.diff(self.seg) <= 0))
+            raise ValueError(f"output {r + 1}: the segment {int(self.seg[r])}..{int(self.seg[r + 1])} is "
+                             + ("empty" if self.seg[r + 1] == self.seg[r] else "decreasing"))
+        if self.seg[R] != N:
+            raise ValueError(f"output {R}: seg[R] = {int(self.seg[R])} (the last segment ends at N = {N})")
+        self.shift = np.zeros(N) if self.shift is None else _f64(self.shift)
+        self.weight = np.ones(N) if self.weight is None else _f64(self.weight)
+        if self.shift.shape != (N,) or self.weight.shape != (N,):
+            raise ValueError(f"shift and weight: {N} values each")
+
+
+@dataclasses.dataclass
 class NlpRowBlock:
     """Output r adds sum_{i < N} weight[r, i] kappa(sum_j A[i, j] x_{cols[j]} + shift_i) to row rows[r] (0: the objective, i: row
     i, a nonlinear one): one design matrix, R = len(rows) <= 8 distinct target rows.  kind, cols, A, exp, par as in NlpBlock;
@@ -281,7 +333,7 @@ class NlpTerms:
     fpar: np.ndarray | None = None     # [nfac] real exponent of a POWR factor (0 elsewhere); None: no POWR factor
     general: bool = False              # written for sqphip_nlp_attach_general (make_nlp_terms: needs_general); False: a model
                                        # of the older calls, which keep refusing what they refuse
-    blocks: list = dataclasses.field(default_factory=list)     # NlpBlock, NlpSoftmaxBlock, NlpRowBlock, NlpCoxBlock, NlpLseBlock: dense data blocks (at most 4)
+    blocks: list = dataclasses.field(default_factory=list)     # NlpBlock, NlpSoftmaxBlock, NlpRowBlock, NlpCoxBlock, NlpLseBlock, NlpNormBlock: dense data blocks (at most 4)
 
     @property
     def affine(self) -> bool:
@@ -354,9 +406,9 @@ def make_nlp_terms(n, m, num_linear, terms, g0=None, f0=0.0, xL=None, xU=None, g
     if len(p.blocks) > MAX_BLOCKS:
         raise ValueError(f"{len(p.blocks)} blocks (at most {MAX_BLOCKS})")
     for k, b in enumerate(p.blocks):
-        if isinstance(b, (NlpSoftmaxBlock, NlpRowBlock, NlpCoxBlock, NlpLseBlock)) and (b.cols.min() < 1 or b.cols.max() > n):
+        if isinstance(b, (NlpSoftmaxBlock, NlpRowBlock, NlpCoxBlock, NlpLseBlock, NlpNormBlock)) and (b.cols.min() < 1 or b.cols.max() > n):
             raise ValueError(f"block {k + 1}: a column outside 1..{n}")
-        if isinstance(b, (NlpRowBlock, NlpLseBlock)):
+        if isinstance(b, (NlpRowBlock, NlpLseBlock, NlpNormBlock)):
             if b.rows.min() < 0 or b.rows.max() > m:
                 raise ValueError(f"block {k + 1}: a row outside 0..{m}")
             if np.any((b.rows >= 1) & (b.rows <= num_linear)):
@@ -381,7 +433,7 @@ def nlp_terms_layout(p: NlpTerms) -> NlpTermsLayout:
     inrow = rows > 0
     jk = [(rows[inrow] - 1) * n + (avar[inrow] - 1)]
     for b in getattr(p, "blocks", []):
-        if isinstance(b, (NlpRowBlock, NlpLseBlock)):
+        if isinstance(b, (NlpRowBlock, NlpLseBlock, NlpNormBlock)):
             jk += [(i - 1) * n + (b.cols - 1) for i in b.rows.tolist() if i >= 1]
     jkey = np.unique(np.concatenate(jk))
     hk = []
@@ -755,11 +807,11 @@ def _cox_eval(b: NlpCoxBlock, x):
 def block_eval(p: NlpTerms, x, blocks=None):
     """(f, grad [n], H [n, n]) of the blocks of p at x: sum_i w_i kappa(u_i), A'(w kappa'), A' diag(w kappa'') A scattered to
     the blocks' columns.  Blocks with several outputs (NlpRowBlock) are row_block_eval's and log-sum-exp row blocks (NlpLseBlock)
-    lse_block_eval's, not counted here."""
+    lse_block_eval's, Euclidean-norm row blocks (NlpNormBlock) norm_block_eval's, not counted here."""
     x = _f64(x)
     f, g, H = 0.0, np.zeros(p.n), np.zeros((p.n, p.n))
     for b in (p.blocks if blocks is None else blocks):
-        if isinstance(b, (NlpRowBlock, NlpLseBlock)):
+        if isinstance(b, (NlpRowBlock, NlpLseBlock, NlpNormBlock)):
             continue
         if isinstance(b, NlpSoftmaxBlock):
             fb, gb, Hb = _softmax_eval(b, x)
@@ -913,6 +965,147 @@ def gp_scenario(p: NlpTerms, s: int, seed: int = 1, noise: float = 0.05) -> NlpT
     out = dataclasses.replace(p)
     out.blocks = [dataclasses.replace(b, shift=b.shift + noise * rng.standard_normal(len(b.shift))) if isinstance(b, NlpLseBlock) else b
                   for b in p.blocks]
+    return out
+
+
+def norm_block_eval(p: NlpTerms, x, sigma=1.0, lam=None, blocks=None):
+    """(f, grad [n], g [m], J [m, n], H [n, n]) of the Euclidean-norm row blocks of p at x: what they add to the objective, its
+    gradient, the rows' values and Jacobian rows, and to the Hessian of the Lagrangian, sum_r mu_r (A_r' diag(w / f_r) A_r -
+    G_r G_r' / f_r) with mu_r = sigma for row 0 and lam[i - 1] for row i (lam None: zeros).  The residuals of a segment are scaled
+    by the largest magnitude among its points of non-zero weight; a zero-weight point is masked out (its residual may be
+    anything); an output whose value is 0 (no weighted point, or all weighted residuals exactly zero) contributes the value 0
+    and nothing to the derivatives."""
+    x = _f64(x)
+    lam = np.zeros(p.m) if lam is None else _f64(lam)
+    f, g, gv, J, H = 0.0, np.zeros(p.n), np.zeros(p.m), np.zeros((p.m, p.n)), np.zeros((p.n, p.n))
+    for b in (p.blocks if blocks is None else blocks):
+        if not isinstance(b, NlpNormBlock):
+            continue
+        c = b.cols - 1
+        for r, i in enumerate(b.rows.tolist()):
+            s0, s1 = int(b.seg[r]), int(b.seg[r + 1])
+            on = b.weight[s0:s1] != 0.0
+            Ar, wr = b.A[s0:s1][on], b.weight[s0:s1][on]
+            vr = Ar @ x[c] + b.shift[s0:s1][on]
+            mr = np.abs(vr).max() if len(vr) else 0.0
+            if mr == 0.0:
+                continue                                # the apex: value 0, no derivative
+            y = vr / mr
+            sr = np.sqrt(np.sum(wr * y * y))
+            val = float(mr * sr)
+            Gr = Ar.T @ (wr * y / sr)
+            mu = float(sigma) if i == 0 else lam[i - 1]
+            if i == 0:
+                f += val
+                np.add.at(g, c, Gr)
+            else:
+                gv[i - 1] += val
+                np.add.at(J[i - 1], c, Gr)
+            H[np.ix_(c, c)] += Ar.T @ ((mu * wr / val)[:, None] * Ar) + (-mu / val) * np.outer(Gr, Gr)
+    return f, g, gv, J, H
+
+
+def sum_of_norms_model(anchors, weights=None, smooth=0.0, bounds=(-np.inf, np.inf), ridge=0.0, x0=None) -> NlpTerms:
+    """Fermat-Weber location: min sum_k w_k sqrt(|x - a_k|^2 + smooth^2) + ridge sum_j x_j^2 over x in R^dim, anchors [K, dim], weights [K] > 0
+    (None: ones).  One NlpNormBlock with K outputs on row 0: output k owns the dim points x_j - a_kj and, with smooth != 0, one
+    more point with a zero row of A and the shift smooth; w_k enters as the weight w_k^2 of the points of output k.  No
+    constraint rows.  From x0 (None: the weighted mean of the anchors)."""
+    a = _f64(np.atleast_2d(anchors))
+    K, dim = a.shape
+    w = np.ones(K) if weights is None else _f64(weights)
+    if w.shape != (K,) or not np.all(w > 0):
+        raise ValueError(f"sum_of_norms_model: {K} positive weights")
+    per = dim + (1 if smooth else 0)
+    A, S = np.zeros((K * per, dim)), np.zeros(K * per)
+    for k in range(K):
+        A[k * per:k * per + dim] = np.eye(dim)
+        S[k * per:k * per + dim] = -a[k]
+        if smooth:
+            S[k * per + dim] = float(smooth)
+    blk = NlpNormBlock(np.arange(1, dim + 1), A, np.zeros(K, np.int64), np.arange(K + 1) * per, S, np.repeat(w * w, per))
+    lo, hi = bounds
+    start = (w @ a) / w.sum() if x0 is None else x0
+    terms = [(0, float(ridge), [(j + 1, POW, 2)]) for j in range(dim)] if ridge else []
+    return make_nlp_terms(dim, 0, 0, terms, xL=np.broadcast_to(_f64(lo), (dim,)).copy(), xU=np.broadcast_to(_f64(hi), (dim,)).copy(),
+                          x0=start, blocks=[blk])
+
+
+def robust_lp_model(c, a, P, kappa, b, bounds=(-np.inf, np.inf), smooth=0.0, ridge=0.0, x0=None) -> NlpTerms:
+    """A robust linear programme: min c'x + ridge sum_j x_j^2  s.t.  a_k'x + kappa_k sqrt(|P_k x|^2 + smooth^2) <= b_k, lo <= x <= hi
+    -- the worst case of a_k'x over an ellipsoid of coefficients.  c [n], a [K, n], P a list of K matrices [l_k, n], kappa [K] > 0,
+    b [K].  The K rows are nonlinear rows 1..K: the linear part a_k'x is plain terms on the row, the norm is output k of one
+    NlpNormBlock on the variables in use, kappa_k in the weights as kappa_k^2; with smooth != 0 every output gets a point with a
+    zero row of A and the shift smooth.  From x0 (None: zeros)."""
+    c, a, b_, kap = _f64(c), _f64(np.atleast_2d(a)), _f64(np.atleast_1d(b)), _f64(np.atleast_1d(kappa))
+    n, K = len(c), len(a)
+    if a.shape != (K, n) or len(P) != K or b_.shape != (K,) or kap.shape != (K,) or not np.all(kap > 0):
+        raise ValueError(f"robust_lp_model: a [{K}, {n}], {K} matrices P, kappa > 0 and b [{K}]")
+    A, W, S, seg = [], [], [], [0]
+    for k in range(K):
+        Pk = _f64(np.atleast_2d(P[k]))
+        if Pk.shape[1] != n or len(Pk) < 1:
+            raise ValueError(f"robust_lp_model: P[{k}] has {n} columns and at least one row")
+        rows_k = len(Pk) + (1 if smooth else 0)
+        A.append(Pk); S.append(np.zeros(len(Pk)))
+        if smooth:
+            A.append(np.zeros((1, n))); S.append(np.array([float(smooth)]))
+        W.append(np.full(rows_k, kap[k] ** 2)); seg.append(seg[-1] + rows_k)
+    A = np.vstack(A)
+    used = np.flatnonzero(np.any(A != 0.0, axis=0))
+    if len(used) == 0:
+        used = np.arange(1)
+    blk = NlpNormBlock(used + 1, A[:, used], np.arange(1, K + 1), seg, np.concatenate(S), np.concatenate(W))
+    terms = [(0, float(c[j]), [(j + 1, POW)]) for j in np.flatnonzero(c)]
+    terms += [(k + 1, float(a[k, j]), [(j + 1, POW)]) for k in range(K) for j in np.flatnonzero(a[k])]
+    if ridge:
+        terms += [(0, float(ridge), [(j + 1, POW, 2)]) for j in range(n)]
+    lo, hi = bounds
+    return make_nlp_terms(n, K, 0, terms, xL=np.broadcast_to(_f64(lo), (n,)).copy(), xU=np.broadcast_to(_f64(hi), (n,)).copy(),
+                          gL=np.full(K, -np.inf), gU=b_, x0=np.zeros(n) if x0 is None else x0, blocks=[blk])
+
+
+def socp_synth(n: int, lens, seed: int = 1) -> NlpTerms:
+    """A seeded second-order-cone programme on n variables: min c'x + 1e-3 sum x_j^2 + sum of lens[0] norms of 2 points each on
+    the objective (a group penalty |B_g x - t_g|), and a cone row a_k'x + |P_k x + s_k| <= b_k of lens[k] points for every k >= 1,
+    smoothed by one more point with the shift 1e-2 each.  The entries of P, B are N(0, 1) / sqrt(n) with about half of them zero,
+    s, t are 0.3 N(0, 1), and b_k puts x = 0 strictly inside (b_k = |s_k| + 0.5); -3 <= x <= 3, from x = 0."""
+    rng = np.random.default_rng(int(seed))
+    n = int(n)
+    groups = int(lens[0])
+    A, S, rows, seg = [], [], [], [0]
+    for g in range(groups):
+        B = rng.standard_normal((2, n)) / np.sqrt(n) * (rng.random((2, n)) < 0.5)
+        A += [B, np.zeros((1, n))]; S += [0.3 * rng.standard_normal(2), [1e-2]]
+        rows.append(0); seg.append(seg[-1] + 3)
+    K = len(lens) - 1
+    a = rng.standard_normal((K, n)) / np.sqrt(n)
+    gU = np.zeros(K)
+    for k in range(K):
+        L = int(lens[k + 1])
+        Pk = rng.standard_normal((L, n)) / np.sqrt(n) * (rng.random((L, n)) < 0.5)
+        sk = 0.3 * rng.standard_normal(L)
+        A += [Pk, np.zeros((1, n))]; S += [sk, [1e-2]]
+        rows.append(k + 1); seg.append(seg[-1] + L + 1)
+        gU[k] = np.sqrt(sk @ sk + 1e-4) + 0.5
+    A, S = np.vstack(A), np.concatenate([np.atleast_1d(v) for v in S])
+    used = np.flatnonzero(np.any(A != 0.0, axis=0))
+    blk = NlpNormBlock(used + 1, A[:, used], rows, seg, S)
+    c = rng.standard_normal(n)
+    terms = [(0, float(c[j]), [(j + 1, POW)]) for j in range(n)] + [(0, 1e-3, [(j + 1, POW, 2)]) for j in range(n)]
+    terms += [(k + 1, float(a[k, j]), [(j + 1, POW)]) for k in range(K) for j in range(n)]
+    return make_nlp_terms(n, K, 0, terms, xL=np.full(n, -3.0), xU=np.full(n, 3.0), gL=np.full(K, -np.inf), gU=gU, x0=np.zeros(n), blocks=[blk])
+
+
+def norm_scenario(p: NlpTerms, s: int, seed: int = 1, noise: float = 0.05) -> NlpTerms:
+    """Scenario s of a model with Euclidean-norm row blocks (s = 0 or noise = 0: p itself): every shift of a point with a
+    non-zero row of A moved by noise N(0, 1) -- other anchors, targets, nominal loads; the smoothing points stay.  Structure,
+    bounds and start stay."""
+    if s == 0 or noise == 0:
+        return p
+    rng = np.random.default_rng(int(seed) * 1000 + int(s))
+    out = dataclasses.replace(p)
+    out.blocks = [dataclasses.replace(b, shift=b.shift + noise * rng.standard_normal(len(b.shift)) * np.any(b.A != 0.0, axis=1))
+                  if isinstance(b, NlpNormBlock) else b for b in p.blocks]
     return out
 
 
